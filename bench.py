@@ -2,6 +2,7 @@
 """bench.py — train-step throughput of the ST-DADK interpolation hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload c2|default|c4]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one optimisation step on one mini-batch of synthetic KAUST-shaped observations resident
 in HBM: feature build (multi-resolution Wendland + Gaussian bases) -> MLP forward -> MSE -> backward
@@ -12,12 +13,18 @@ rank 0's line.  Gradient exchange per step (--dp-mode): `shard` = reduce-scatter
 `allreduce` = one all-reduce + replicated optimiser (`auto` = whichever is faster in a 100-step calibration, both times
 in `dp_mode_calibration`); default `shard`, the other mode is reported beside the headline.
 Rank 0 prints ONE JSON line:
-  value      whole-job observations/s: the MEDIAN of >= 10 timed windows of K steps each (every window bracketed by
-             barrier + synchronize, max over ranks); min / max of the windows beside it
+  value        whole-job observations/s over the K timed steps (the timed region is bracketed by barrier +
+               synchronize, max over ranks; --windows M splits the K steps into M windows and takes the median one)
+  ms_per_step  milliseconds of one timed step (the same window as `value`)
+A plain run does only that: set-up, W warm-up steps, K timed steps, the line.  --dump-outputs DIR writes what the
+last timed step left behind for a caller -- every parameter and its EMA shadow -- and the mean batch objective of
+the run's W + K steps as DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed, seeded sample of each array beyond that).  --full adds,
+after the timed steps:
   roofline   the dominant kernel of the timed step: average launch duration measured live with HIP
              events on the launch stream (stdadk_profile_*), algorithmic bytes/flops per launch
   rbf_build  the standalone materialising feature builder (the "RBF-build GB/s" of BASELINE.json)
-  cpu_baseline  the oracle's torch-CPU port of the reference's batch body on this box's host cores
+  batch_sweep, bf16_mlp, variants, N > 1 weak-scaling lines: other sizes / precisions / objectives (never `value`)
+  cpu_baseline  the oracle's torch-CPU port of the reference's batch body on the host's cores
 """
 import argparse
 import gc
@@ -236,6 +243,37 @@ def kernel_work(name, B, D, H, P_flat, nnz_pairs, Kt, Q=1):
     return None
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, model, eng, loss, write=True, budget=DUMP_BUDGET_BYTES):
+    """What the timed path leaves a caller after its last step, as `out_dir/<name>.npy`: every parameter
+    (`param.<name>`), its EMA shadow as swap_in_ema() hands it out (`ema.<name>`) and the mean batch objective of all
+    the run's steps, warm-up and timed (`mean_loss`, float64: TrainStep.mean_loss(), as `final_mean_loss`).  Beyond `budget` bytes in all, each array is replaced by the same fixed, seeded
+    sample of its flattened entries (a fraction of every array; the indices depend only on its name and size).
+    Every rank must call this (the EMA of a sharded optimiser is all-gathered); only `write` ranks write."""
+    import zlib
+    def host(p):                                             # a copy: the EMA swap below rewrites the parameters
+        return p.detach().to("cpu", torch.float32, copy=True).numpy()
+    arrays = {f"param.{k}": host(p) for k, p in model.named_parameters()}
+    if eng.ema is not None:
+        eng.swap_in_ema()
+        arrays.update({f"ema.{k}": host(p) for k, p in model.named_parameters()})
+        eng.swap_in_ema()
+    arrays["mean_loss"] = np.array([loss], dtype=np.float64)
+    if not write:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes + 128 for a in arrays.values())          # + the .npy header of each file
+    frac = 1.0 if total <= budget else (budget - 128 * len(arrays)) / sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if frac < 1.0 and a.size > 1:
+            rng = np.random.default_rng(zlib.crc32(name.encode()) ^ a.size)
+            k = max(1, int(a.size * frac))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def self_launch(n, argv, script=None):
     """`python bench.py --gpus N` without a launcher: start the N ranks as child processes (RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* in their environment, rendezvous on 127.0.0.1) and relay rank 0's JSON line.  Called before
@@ -294,19 +332,29 @@ def main():
     ap.add_argument("--dense", action="store_true", help="force the materialising (dense) kernels")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="do not overlap the next batch's gather + binning with the current step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--clock-warmup-ms", type=float, default=150.0,
                     help="milliseconds of an unrelated kernel (the standalone feature builder) before the warm-up steps, "
                          "to leave idle clocks; 0 = off")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the extra per-GPU batch sizes (N = 1 only)")
-    ap.add_argument("--windows", type=int, default=10,
-                    help="timed windows of --steps steps each; `value` is the median window (>= 1)")
+    ap.add_argument("--no-sweep", action="store_true",
+                    help="--full: skip the extra batch sizes, precisions and variants (N = 1 only)")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="split the --steps timed steps into this many consecutive windows; `value` and `ms_per_step` "
+                         "are the median window's (default 1: the whole timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the per-kernel roofline, the standalone feature builder, "
+                         "the other batch sizes / precisions / variants, the N > 1 extra lines and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the parameters and EMA shadow after the last timed step, and the mean objective of "
+                         "the warm-up and timed steps, as DIR/<name>.npy")
     ap.add_argument("--dp-mode", default="shard", choices=["shard", "allreduce", "auto"],
                     help="N > 1: gradient exchange of the headline line (the other mode is reported beside it); auto = "
                          "whichever of the two is faster in a short calibration on this machine (both times reported; "
                          "not the default: in the two-rank gloo rehearsal the second engine of the calibration left "
                          "the first one slower)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -437,16 +485,16 @@ def main():
             run(0, args.warmup)
             torch.cuda.synchronize()
         dp_calibration["chosen"] = args.dp_mode
-    # >= 1 timed windows of EXACTLY --steps steps, each bracketed by barrier + synchronize on both sides and reduced
-    # with MAX over ranks; `value` is the median window (a 20-step window is 2.4 ms: one window alone moves by a few
-    # per cent from run to run with the chip's clock state), the fastest and slowest window are reported beside it
-    def timed_window(k0):
+    # EXACTLY --steps timed steps, in --windows consecutive windows (default one), each bracketed by barrier +
+    # synchronize on both sides and reduced with MAX over ranks; `value` / `ms_per_step` are the median window's (per
+    # step), the fastest and slowest window are reported beside it
+    def timed_window(k0, k):
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run(k0, args.steps)
+        run(k0, k)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -457,10 +505,52 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = tmax.item()
         return dt
-    n_win = max(1, args.windows)
-    win_s = [timed_window(args.warmup + w * args.steps) for w in range(n_win)]
-    el = sorted(win_s)[(n_win - 1) // 2]                       # median window (lower median for an even count)
+    n_win = max(1, min(args.windows, args.steps))
+    win_k = [args.steps // n_win + (1 if w < args.steps % n_win else 0) for w in range(n_win)]
+    win_s = [timed_window(args.warmup + sum(win_k[:w]), win_k[w]) for w in range(n_win)]
+    per_step_s = [t_ / k_ for t_, k_ in zip(win_s, win_k)]
+    el = sorted(per_step_s)[(n_win - 1) // 2]                  # median window (lower median for an even count), s/step
     loss = eng.mean_loss()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, eng, loss, write=(rank == 0))
+    ms_step = el * 1e3
+    head = {
+        "metric": "train-step samples/sec (obs points/sec)", "value": args.gpus * B / el,
+        "value_windows": {"n": n_win, "steps_each": win_k, "statistic": "median window",
+                          "min": args.gpus * B / max(per_step_s), "max": args.gpus * B / min(per_step_s),
+                          "ms_per_step_each": [round(w * 1e3, 5) for w in per_step_s]},
+        "unit": "obs/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": wl["name"], "per_gpu_batch": B, "global_batch": B * args.gpus,
+                   "n_obs_per_gpu": n_obs, "dropout": args.dropout, "layernorm": True,
+                   "optimizer": "AdamW lr 2e-2 wd 5e-4 clip 10 + EMA",
+                   "path": (("index-window layer 1 (compact support) + " if eng.uses_window
+                             else "materialised features + dense ") +
+                            ("fp32 MFMA MLP" if args.dtype == "f32" else
+                             "bf16-operand MFMA MLP after the first layer (fp32 accumulate / LayerNorm / master weights)")),
+                   "hipgraph": bool(eng.use_graph),
+                   "batch_preparation": "pipelined on a side stream" if (eng.uses_window and not args.no_pipeline
+                                                                          and not eng.use_graph) else "in the step",
+                   "device_warmup_ms_before_warmup_steps": args.clock_warmup_ms,
+                   "parallelism": f"dp{args.gpus}",
+                   "gradient_exchange": ("none (one GPU)" if world == 1 else
+                                         ("reduce-scatter + sharded AdamW/EMA + all-gather" if shard
+                                          else "all-reduce + replicated AdamW/EMA"))},
+        "final_mean_loss": loss,
+    }
+    if world > 1 and dp_calibration:
+        head["dp_mode_calibration"] = dp_calibration
+    if world > 1 and dp_fallback:
+        head["dp_mode_fallback"] = {"requested": "shard", "used": "allreduce", "error": dp_fallback}
+    if not args.full:
+        # a plain run: the headline line and nothing else
+        if rank == 0:
+            print(json.dumps(head))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- per-kernel device time of the step, live, with HIP events on the launch stream.  Every
     # rank runs these steps (they contain the gradient all-reduce); rank 0 reports.
@@ -666,30 +756,8 @@ def main():
         del feats_big, cb, tb_
         Q = model.output_dim
         floors = step_floors(B, H, Kt, Q, P_flat, nnz / B)
-        ms_step = el / args.steps * 1e3
         out = {
-            "metric": "train-step samples/sec (obs points/sec)", "value": args.gpus * B * args.steps / el,
-            "value_windows": {"n": n_win, "steps_each": args.steps, "statistic": "median window",
-                              "min": args.gpus * B * args.steps / max(win_s), "max": args.gpus * B * args.steps / min(win_s),
-                              "ms_per_step_each": [round(w / args.steps * 1e3, 5) for w in win_s]},
-            "unit": "obs/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": el / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": wl["name"], "per_gpu_batch": B, "global_batch": B * args.gpus,
-                       "n_obs_per_gpu": n_obs, "dropout": args.dropout, "layernorm": True,
-                       "optimizer": "AdamW lr 2e-2 wd 5e-4 clip 10 + EMA",
-                       "path": (("index-window layer 1 (compact support) + " if eng.uses_window
-                                 else "materialised features + dense ") +
-                                ("fp32 MFMA MLP" if args.dtype == "f32" else
-                                 "bf16-operand MFMA MLP after the first layer (fp32 accumulate / LayerNorm / master weights)")),
-                       "hipgraph": bool(eng.use_graph),
-                       "batch_preparation": "pipelined on a side stream" if (eng.uses_window and not args.no_pipeline
-                                                                              and not eng.use_graph) else "in the step",
-                       "device_warmup_ms_before_warmup_steps": args.clock_warmup_ms,
-                       "parallelism": f"dp{args.gpus}",
-                       "gradient_exchange": ("none (one GPU)" if world == 1 else
-                                             ("reduce-scatter + sharded AdamW/EMA + all-gather" if shard
-                                              else "all-reduce + replicated AdamW/EMA"))},
+            **head,
             "roofline": roof,
             "rbf_build": {"bound": "hbm", "achieved": rbf_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                           "frac": rbf_gbs / HBM_PEAK_GBS, "bytes_per_obs": 12 + 4 * D, "avg_launch_us": t_rbf * 1e6,
@@ -708,15 +776,10 @@ def main():
                                "(roofline.event_bracket_of_an_empty_launch_us), which the rocprofv3 averages in profiles/ do not",
             "kernel_time_us_per_step": round(sum(r[3] for r in per_step), 1),
             "nonzero_obs_knot_pairs_per_obs": nnz / B,
-            "final_mean_loss": loss,
         }
         if world > 1:
             # the one collective of the path, timed with events around it on the step's stream (rank 0's view;
             # it includes waiting for the slowest rank to arrive)
-            if dp_calibration:
-                out["dp_mode_calibration"] = dp_calibration
-            if dp_fallback:
-                out["dp_mode_fallback"] = {"requested": "shard", "used": "allreduce", "error": dp_fallback}
             out["collectives"] = {"dp_mode": args.dp_mode, "ms_per_step": allreduce_ms, "gradient_bytes": 4 * P_flat,
                                   "algorithm_bandwidth_GBs": 4 * P_flat / (allreduce_ms * 1e-3) / 1e9 if allreduce_ms else None,
                                   "note": "event brackets on the step's stream around every collective of a step (rank 0: "

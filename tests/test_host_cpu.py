@@ -423,3 +423,44 @@ def test_bench_self_launch_starts_the_ranks_and_relays_failures(tmp_path, capfd)
     t0 = __import__("time").perf_counter()
     assert bench.self_launch(2, ["--fail"], script=str(stub)) == 7
     assert __import__("time").perf_counter() - t0 < 30                                 # rank 0 was not waited for
+
+
+def test_bench_dump_outputs_is_bounded_and_reproducible(tmp_path):
+    """bench.py --dump-outputs: every parameter and its EMA shadow under the model's names plus the mean objective;
+    beyond the byte budget each array is the same seeded sample from run to run, and the engine's live weights and
+    shadow are left as they were."""
+    import bench
+    torch.manual_seed(3)
+    model = torch.nn.Sequential(torch.nn.Linear(300, 200), torch.nn.Linear(200, 1))
+
+    class _Eng:                                     # the two members of TrainStep the dump uses
+        def __init__(self):
+            self.ema = [p.detach().clone() + 1.0 for p in model.parameters()]
+
+        def swap_in_ema(self):
+            with torch.no_grad():
+                for p, e in zip(model.parameters(), self.ema):
+                    tmp = p.detach().clone()
+                    p.copy_(e)
+                    e.copy_(tmp)
+
+    eng = _Eng()
+    before = [p.detach().clone() for p in model.parameters()]
+    bench.dump_outputs(str(tmp_path / "a"), model, eng, 0.25)
+    assert all(torch.equal(p, b) for p, b in zip(model.parameters(), before))
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == sorted([f"param.{k}.npy" for k, _ in model.named_parameters()] +
+                           [f"ema.{k}.npy" for k, _ in model.named_parameters()] + ["mean_loss.npy"])
+    w = np.load(tmp_path / "a" / "param.0.weight.npy")
+    assert w.dtype == np.float32 and np.array_equal(w, before[0].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "ema.0.weight.npy"), before[0].numpy() + 1.0)
+    assert np.load(tmp_path / "a" / "mean_loss.npy").tolist() == [0.25]
+    # a budget below the full size: seeded samples, within the budget, identical in a second run
+    budget = 200_000
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), model, eng, 0.25, budget=budget)
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= budget
+    for f in (tmp_path / "b").iterdir():
+        assert np.array_equal(np.load(f), np.load(tmp_path / "c" / f.name))
+    ws = np.load(tmp_path / "b" / "param.0.weight.npy")
+    assert 0 < ws.size < w.size and np.isin(ws, w.reshape(-1)).all()

@@ -21,5 +21,5 @@ if [ ! -f obj_asan/api.o ] || [ api.cpp -nt obj_asan/api.o ] || [ ../../include/
   pids+=($!)
 fi
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait $p; done
-$HIPCC -shared -fPIC --offload-arch=gfx950 -fsanitize=address,undefined -shared-libsan obj_asan/*.o -o ../lib/libstdadk_asan.so
+$HIPCC -shared -fPIC --offload-arch=gfx950 -fsanitize=address,undefined -fno-gpu-sanitize -shared-libsan obj_asan/*.o -o ../lib/libstdadk_asan.so
 echo "built $(cd ../lib && pwd)/libstdadk_asan.so"

@@ -3,8 +3,8 @@ set -uo pipefail
 cd "$(dirname "$0")/.."
 O=gpurun_out/r3n; mkdir -p $O
 python -m pytest tests -m gpu -q 2>&1 | tail -4
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; tail -2 $O/bench_default.err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench_driver_args.err; echo "bench rc=$?"
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; tail -2 $O/bench_default.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench_driver_args.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 for f in ("bench_default","bench_driver_args"):

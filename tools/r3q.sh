@@ -3,9 +3,9 @@ set -uo pipefail
 cd "$(dirname "$0")/.."
 O=gpurun_out/r3q; mkdir -p $O
 python -c "import __graft_entry__ as g; g.build(); g.smoke()" 2>&1 | tail -2
-python bench.py --workload c4 --no-cpu-baseline --no-sweep > $O/bench_c4.json 2> $O/bench_c4.err; echo "c4 rc=$?"
-python bench.py --workload c3 --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err; echo "c3 rc=$?"
-python bench.py --workload c4 --batch 16384 --no-cpu-baseline --no-sweep > $O/bench_c4_b16384.json 2> $O/bench_c4_b16384.err; echo "c4 16384 rc=$?"
+python bench.py --full --workload c4 --no-cpu-baseline --no-sweep > $O/bench_c4.json 2> $O/bench_c4.err; echo "c4 rc=$?"
+python bench.py --full --workload c3 --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err; echo "c3 rc=$?"
+python bench.py --full --workload c4 --batch 16384 --no-cpu-baseline --no-sweep > $O/bench_c4_b16384.json 2> $O/bench_c4_b16384.err; echo "c4 16384 rc=$?"
 python - <<'PY'
 import json
 for f in ("bench_c4","bench_c3","bench_c4_b16384"):

@@ -5,9 +5,9 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/r3x; mkdir -p $O
 python -c "import __graft_entry__ as g; g.build(); g.smoke()" 2>&1 | tail -1
 timeout -k 10 900 python -m pytest tests -m gpu -q > $O/tests.log 2>&1; tail -2 $O/tests.log
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "default rc=$?"
-STNF_BENCH_BACKEND=gloo STNF_BENCH_ONE_GPU=1 timeout -k 10 600 python bench.py --gpus 2 --steps 20 --warmup 5 --windows 2 > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err; echo "2rank rc=$?"
-STNF_BENCH_BACKEND=gloo STNF_BENCH_ONE_GPU=1 timeout -k 10 600 python bench.py --gpus 2 --steps 20 --warmup 5 --windows 2 --dp-mode allreduce > $O/bench_2rank_gloo_ar.json 2> $O/bench_2rank_gloo_ar.err; echo "2rank allreduce rc=$?"
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "default rc=$?"
+STNF_BENCH_BACKEND=gloo STNF_BENCH_ONE_GPU=1 timeout -k 10 600 python bench.py --full --gpus 2 --steps 20 --warmup 5 --windows 2 > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err; echo "2rank rc=$?"
+STNF_BENCH_BACKEND=gloo STNF_BENCH_ONE_GPU=1 timeout -k 10 600 python bench.py --full --gpus 2 --steps 20 --warmup 5 --windows 2 --dp-mode allreduce > $O/bench_2rank_gloo_ar.json 2> $O/bench_2rank_gloo_ar.err; echo "2rank allreduce rc=$?"
 python - <<'PY'
 import json
 for f in ("bench_default","bench_2rank_gloo","bench_2rank_gloo_ar"):

@@ -2,7 +2,7 @@
 set -uo pipefail
 cd "$(dirname "$0")/.."
 O=gpurun_out/r3y; mkdir -p $O
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo rc=$?
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo rc=$?
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r3y/bench_default.json").read().strip().splitlines()[-1])
