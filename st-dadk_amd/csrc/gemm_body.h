@@ -449,9 +449,14 @@ __device__ __forceinline__ float reduce_job_block(const ReduceGroup &grp, int bl
 // Finishing step of one K slice of a grouped job's output tile (FinArgs): once the slice's slab stores
 // (slab_store: device scope) are acknowledged the tile's arrival counter is advanced, and the workgroup that finds
 // the other splits - 1 slices already there sums the tile over the slabs in slice order s = 0, 1, ... (the wide
-// reduce job's order), writes C and the tile's squared-norm slot.
+// reduce job's order), writes C and the tile's squared-norm slot.  Hand-over: every wave drains its sc1 slab
+// stores (vmcnt(0)) before the barrier ahead of the relaxed agent-scope counter add; the reducer reads every slab
+// word with sc1 loads (slab_load2, or the relaxed agent-scope load of the unpaired path), so it needs no agent-scope
+// acquire fence.  A workgroup-scope release emits no vector-memory wait and is no substitute for the drain (the wait
+// after the tile's last store sat in a branch arm that the store's path jumped past); tests/test_kernel_isa.py
+// checks the ordering on every control-flow path of the compiled kernels.
 __device__ __forceinline__ void gemm_tile_finish(const GemmArgs &g, int bx, int by, int *cnt, float *slot, float *lds) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      // this wave's slab stores have been acknowledged
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's slab stores have been acknowledged
   __syncthreads();
   int *flag = reinterpret_cast<int *>(lds);
   if (threadIdx.x == 0) flag[0] = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

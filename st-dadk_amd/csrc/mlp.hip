@@ -1662,6 +1662,19 @@ static int train_step_impl(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
                  "train_step: optimiser descriptor incomplete");
   STDADK_REQUIRE(o->max_norm <= 0.f || o->sumsq_parts, STDADK_E_ARG, "train_step: max_norm > 0 needs sumsq_parts");
   if (B == 0) return 0;
+  // the NEXT batch is validated and planned before anything of this step is enqueued: a call that fails on it
+  // leaves the parameters, moments, EMA, step counter and loss sum as they were
+  Ctx cn;
+  bool bin_next = false;
+  if (next_idx && next_B > 0 && next_workspace && next_binned) {
+    bool window_n = false;
+    int rc = step_common(cn, b, d, next_B, next_workspace, next_workspace_bytes, flags & ~STDADK_FLAG_PREBINNED,
+                         &window_n);
+    if (rc) return rc;
+    bin_next = window_n && bin_small_eligible((int)next_B, cn.pl.G) && coords && t && (b->p == 0 || X);
+    STDADK_REQUIRE(!bin_next || (next_y_cols >= 0 && next_y_cols <= d->out_dim && (next_y_cols == 0 || y)),
+                   STDADK_E_ARG, "train_step: next_y_cols=%d must be in 0..Q with y given", next_y_cols);
+  }
   const bool clip = o->max_norm > 0.f;
   const bool sparse = sparsity && sparsity->kind != STDADK_SPARSITY_NONE;
   const float *sq_parts = nullptr;   // where the step's own launches left the squared-norm partials, if they did
@@ -1691,26 +1704,18 @@ static int train_step_impl(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
     rc = stdadk_step_advance(o->step_dev, stream);
     if (rc) return rc;
   }
-  if (next_idx && next_B > 0 && next_workspace && next_binned) {
+  if (bin_next) {
     // the NEXT batch's binning inside this step's optimiser launch (optim.hip: adamw_bin_kernel), when it is the
     // one-launch binning of small batches; the caller then steps on `next_workspace` with STDADK_FLAG_PREBINNED
-    Ctx cn;
-    bool window_n = false;
-    rc = step_common(cn, b, d, next_B, next_workspace, next_workspace_bytes, flags & ~STDADK_FLAG_PREBINNED, &window_n);
-    if (rc) return rc;
-    if (window_n && bin_small_eligible((int)next_B, cn.pl.G) && coords && t && (b->p == 0 || X)) {
-      STDADK_REQUIRE(next_y_cols >= 0 && next_y_cols <= d->out_dim && (next_y_cols == 0 || y), STDADK_E_ARG,
-                     "train_step: next_y_cols=%d must be in 0..Q with y given", next_y_cols);
-      const BinBuffers bb = plan_bins(cn.ws, cn.pl);
-      const BinSmallArgs ba = bin_small_args(coords, t, next_y_cols > 0 ? y : nullptr, next_y_cols, X, b->p, (int)next_B,
-                                             cn.pl.G, bb, next_idx);
-      rc = adamw_ema_with_binning(o->p, o->g, o->m, o->v, o->ema, o->n, o->lr, o->lr_dev, o->beta1, o->beta2, o->eps,
-                                  o->weight_decay, o->step_dev, o->max_norm, clip ? parts : nullptr, n_parts,
-                                  o->ema_decay, o->shadow, o->nonfinite_step ? loss_sum : nullptr, o->nonfinite_step,
-                                  stream, ba);
-      if (rc == 0) *next_binned = 1;
-      return rc;
-    }
+    const BinBuffers bb = plan_bins(cn.ws, cn.pl);
+    const BinSmallArgs ba = bin_small_args(coords, t, next_y_cols > 0 ? y : nullptr, next_y_cols, X, b->p, (int)next_B,
+                                           cn.pl.G, bb, next_idx);
+    rc = adamw_ema_with_binning(o->p, o->g, o->m, o->v, o->ema, o->n, o->lr, o->lr_dev, o->beta1, o->beta2, o->eps,
+                                o->weight_decay, o->step_dev, o->max_norm, clip ? parts : nullptr, n_parts,
+                                o->ema_decay, o->shadow, o->nonfinite_step ? loss_sum : nullptr, o->nonfinite_step,
+                                stream, ba);
+    if (rc == 0) *next_binned = 1;
+    return rc;
   }
   return stdadk_adamw_ema_f32(o->p, o->g, o->m, o->v, o->ema, o->n, o->lr, o->lr_dev, o->beta1, o->beta2, o->eps,
                               o->weight_decay, 1, o->step_dev, o->max_norm, clip ? parts : nullptr, n_parts,

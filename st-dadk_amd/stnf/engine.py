@@ -701,6 +701,9 @@ class TrainStep:
         B = idx.numel()
         if B > self.max_batch:
             raise RuntimeError(f"batch {B} > max_batch {self.max_batch}")
+        if next_idx is not None and next_idx.numel() > self.max_batch:
+            # (its preparation would not fit the second workspace: refused before this step is enqueued)
+            raise RuntimeError(f"next batch {next_idx.numel()} > max_batch {self.max_batch}")
         self._check_bf16_current()
         if global_rows is None:
             global_rows = B * self.world
