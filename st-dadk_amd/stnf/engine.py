@@ -12,10 +12,10 @@ runs the same arithmetic as one chain of HIP kernels on one stream with
     count-weighted so a ragged last batch still equals the global-batch mean
     (SURVEY.md §7 "DDP equivalence"), with the clip norm taken after the reduction.
 """
-import math
-import weakref
-
+import collections
+import ctypes
 import os
+import weakref
 
 import torch
 import torch.distributed as dist
@@ -67,7 +67,6 @@ def _rank_seed(base, rank):
 
 def _wait(stream, ev):
     if isinstance(ev, _LightEvent):
-        import ctypes
         if ev.recorded:
             rc = _LightEvent._hip.hipStreamWaitEvent(ctypes.c_void_p(stream.cuda_stream), ev.h, 0)
             if rc:
@@ -82,7 +81,6 @@ class _LightEvent:
     _hip = None
 
     def __init__(self):
-        import ctypes
         if _LightEvent._hip is None:
             _LightEvent._hip = ctypes.CDLL("libamdhip64.so")
         self.h = ctypes.c_void_p()
@@ -92,7 +90,6 @@ class _LightEvent:
         self.recorded = False
 
     def record(self, stream):
-        import ctypes
         rc = _LightEvent._hip.hipEventRecord(self.h, ctypes.c_void_p(stream.cuda_stream))
         if rc:
             raise RuntimeError(f"hipEventRecord failed: {rc}")
@@ -112,6 +109,44 @@ def _event_factory():
         return _LightEvent
     except (OSError, RuntimeError, AttributeError):
         return torch.cuda.Event
+
+
+# the batch announced by `next_idx`: key of the CALLER's index tensor, the workspace it is (being) binned into, the
+# contiguous indices (kept alive until that step) and whether the previous step's optimiser launch binned it
+_Announced = collections.namedtuple("_Announced", "key ws_index idx inline")
+
+
+def _idx_key(idx):
+    return (idx.data_ptr(), idx.numel(), idx.stride(0) if idx.dim() else 1)
+
+
+class _GraphRunner:
+    """A launch chain replayed from a hipGraph.  The first call runs it eagerly (HIP loads code objects and applies
+    the kernels' LDS attributes on first launch, neither of which may happen inside a stream capture); after that it is
+    captured once per `key` and replayed.  `first`: the runner whose eager first call counts for this one too."""
+
+    def __init__(self, first=None):
+        self.first = first or self
+        self.warm, self.key, self.graph = False, None, None
+
+    def stale(self, key):
+        return self.graph is None or self.key != key
+
+    def run(self, key, enqueue, before_replay=None):
+        if not self.first.warm:
+            self.first.warm = True
+            enqueue()
+            return
+        if self.stale(key):
+            # whatever the chain reads from device scalars (lr, step) a replay advances; capture executes nothing
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                enqueue()
+            self.key, self.graph = key, g
+        if before_replay is not None:
+            before_replay()
+        self.graph.replay()
 
 
 class TrainStep:
@@ -202,8 +237,7 @@ class TrainStep:
         self.flat, self.offsets = flatten_parameters(model, transpose_first=True,
                                                      pad_multiple=32 * self.world if self.shard else 4)
         self.grad = torch.zeros_like(self.flat)
-        self._shard_cache = None        # cached slices / descriptors of the sharded optimiser (_shard_views)
-        self._adam_groups = None        # cached descriptors of the two-group optimiser launch (_enqueue_optimizer)
+        self._plan = None               # cached slices / descriptors of the optimiser's parameter groups (_adam_plan)
         self._knot_train = None         # ... and of the knot penalties
         self.chunk = self.flat.numel() // self.world if self.shard else self.flat.numel()
         self.lo = self.rank * self.chunk if self.shard else 0
@@ -263,7 +297,6 @@ class TrainStep:
         # are registered first, so they occupy the head [0, knot_end) of the flat buffers
         self.learnable = bool(model.spatial_basis.learnable)
         self.knot_end = 0
-        self.knot_train = None
         if self.learnable:
             sb = model.spatial_basis
             (nc, oc, kc), (nl, ol, kl) = self.offsets[0], self.offsets[1]
@@ -287,7 +320,6 @@ class TrainStep:
         B = self.max_batch
         self.ws = torch.empty(N.step_workspace_bytes(self.state.basis, self.state.desc, B, self.state.flags) // 4,
                               device=self.dev)
-        self.y_pred = torch.empty(B, model.output_dim, device=self.dev)
         self.loss_sum = torch.zeros(1, device=self.dev)       # running sum of squared errors
         self.sumsq = torch.zeros(N.SUMSQ_PARTS, device=self.dev)
         self.lr_dev = torch.full((1,), self.lr, device=self.dev)
@@ -307,14 +339,12 @@ class TrainStep:
                            group=process_group)
             self.base_seed = int(bs.item())
         self.seed = _rank_seed(self.base_seed, self.rank)
-        # graph
+        # graph: step() and step_indexed() capture their own chains and share the eager first call
         self.use_graph = bool(use_graph)
-        self._graph = None
+        self._graph = _GraphRunner()
         self._g_in = None
-        self._g_B = None
-        self._warm = False
         self._ix = None
-        self._ix_graph = None
+        self._ix_graph = _GraphRunner(self._graph)
         # the one-call step applies with a single parameter group on one GPU (data-parallel training needs
         # the all-reduce between backward and optimiser; learnable knots / the delta head have extra kernels there)
         self._whole_step = (not self.distributed and self.world == 1 and not self.learnable
@@ -322,7 +352,7 @@ class TrainStep:
         self._optim = None
         self._sumsq512 = torch.zeros(N.GRADSQ_PARTS, device=self.dev)
         self._pipe = None          # two workspaces + side stream of the pipelined batch preparation
-        self._prepared = None      # ((idx data_ptr, numel, stride), workspace index, idx tensor, inline) of the announced batch
+        self._prepared = None      # the announced batch (_Announced)
         # small batches of the one-call step: the next batch is binned inside this step's optimiser launch
         # (False or STNF_NO_INLINE_PREP=1: on the side stream, as for every other step kind)
         self.inline_prep = bool(inline_prep) and os.environ.get("STNF_NO_INLINE_PREP", "") != "1"
@@ -334,7 +364,6 @@ class TrainStep:
             self.sumsq = self._sumsq_all[:N.SUMSQ_PARTS]
             if self.learnable:
                 self.sumsq_basis = self._sumsq_all[N.SUMSQ_PARTS:]
-        self._rs_native = None     # does the backend have reduce_scatter_tensor (gloo: emulated by all-reduce + slice)
         # non-finite guard: first (1-based) step whose objective left the accumulator NaN/inf, 0 = none so far
         self.nonfinite = torch.zeros(1, device=self.dev, dtype=torch.int32) if nonfinite_guard else None
         self.stopped_at = None     # run_epoch(check_every=...): index of the batch it stopped after, or None
@@ -449,84 +478,91 @@ class TrainStep:
         self.allreduce_events.append((e0, e1))
         return out
 
-    # ---- sharded optimiser (shard_optimizer=True) ---------------------------------------------------------
-    def _local(self, a, b):
-        """This rank's part of the flat range [a, b): (start, stop) in flat coordinates, stop <= start if empty."""
-        return max(a, self.lo), min(b, self.hi)
-
-    def _shard_views(self):
-        """Slices and optimiser descriptors of this rank's part of the flat buffers -- rebuilt only when a buffer, a
-        boundary or a rate changes (a dozen slices and up to 14 address checks per step otherwise, on a path whose
-        host side also has three collectives to enqueue per step)."""
-        ke, lo = self.knot_end, self.lo
-        ema = self.ema
+    # ---- optimiser half of a step: replicated on every rank, or on this rank's slice (shard_optimizer=True) -----
+    def _adam_plan(self):
+        """The optimiser's view of the flat range [lo, hi) (everything when replicated, this rank's slice when sharded):
+        (arguments of the sum-of-squares launch, parameter groups).  The MLP group comes first; learnable knots, the
+        head [0, knot_end) of the flat buffers, form the second with their own rate and clip norm.  The sum of squares
+        reads the gradient slice of EVERY group, an empty one included (a rank that holds nothing of a group
+        contributes zeros to its global clip norm); `groups` has an N.make_adam_group descriptor for each non-empty
+        one, moments / EMA shadow indexed from `lo`.  Rebuilt only when a buffer, a boundary or a rate changes: up to
+        14 buffer addresses and 10 slices, per step they were a quarter of the host time of a path that is host-bound."""
+        ema, ke, lo, hi = self.ema, self.knot_end, self.lo, self.hi
         key = (self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-               ema.data_ptr() if ema is not None else 0, lo, self.hi, ke, self.lr, self.grad_clip, id(self.lr_dev)) + \
-              ((self.basis_lr, self.basis_clip, id(self.basis_lr_dev)) if ke else ())
-        c = self._shard_cache
-        if c is not None and c["key"] == key:
-            return c
+               ema.data_ptr() if ema is not None else 0, lo, hi, ke, self.lr, self.grad_clip, id(self.lr_dev),
+               self.shard) + ((self.basis_lr, self.basis_clip, id(self.basis_lr_dev)) if ke else ())
+        if self._plan is not None and self._plan[0] == key:
+            return self._plan[1]
         clip = self.grad_clip > 0
-        a0, b0 = self._local(ke, self.flat.numel())
-        a1, b1 = self._local(0, ke) if ke else (0, 0)
-
-        def bufs(a, b):
-            return (self.flat[a:b], self.grad[a:b], self.m[a - lo:b - lo], self.v[a - lo:b - lo],
+        # replicated: the optimiser kernel re-rounds the bf16 operand copies of the MLP weights it has just stepped;
+        # sharded: they are refreshed from the gathered parameters
+        spans = [(max(ke, lo), min(self.flat.numel(), hi), self.lr, self.lr_dev, self.grad_clip, self.sumsq,
+                  not self.shard)]
+        if ke:
+            spans.append((max(0, lo), min(ke, hi), self.basis_lr, self.basis_lr_dev, self.basis_clip, self.sumsq_basis,
+                          False))
+        sq, groups = [], []
+        for a, b, lr, lr_dev, max_norm, parts, shadowed in spans:
+            b = max(a, b)
+            sq += [self.grad[a:b], parts]
+            if b == a:
+                continue
+            bufs = (self.flat[a:b], self.grad[a:b], self.m[a - lo:b - lo], self.v[a - lo:b - lo],
                     ema[a - lo:b - lo] if ema is not None else None)
-        c = {"key": key, "g_mlp": self.grad[a0:max(b0, a0)], "g_knot": self.grad[a1:max(b1, a1)] if ke else None,
-             "groups": [], "single": None}
-        if b0 > a0:
-            c["groups"].append(N.make_adam_group(*bufs(a0, b0), self.lr, self.lr_dev, self.grad_clip if clip else 0.0,
-                                                 self.sumsq if clip else None))
-        if ke and b1 > a1:
-            c["groups"].append(N.make_adam_group(*bufs(a1, b1), self.basis_lr, self.basis_lr_dev,
-                                                 self.basis_clip if clip else 0.0, self.sumsq_basis if clip else None))
-        if len(c["groups"]) == 1:
-            mlp = b0 > a0
-            c["single"] = (bufs(a0, b0) if mlp else bufs(a1, b1), c["groups"][0].lr, c["groups"][0].max_norm,
-                           self.sumsq if mlp else self.sumsq_basis, self.lr_dev if mlp else self.basis_lr_dev)
-        self._shard_cache = c
-        return c
+            # (unclipped, max_norm = 0, nothing reads the partials: the sharded descriptors have never named them then,
+            # every other launch does; kept as it was)
+            gr = N.make_adam_group(*bufs, lr, lr_dev, max_norm, None if self.shard and not clip else parts,
+                                   shadow=self._shadow(a) if shadowed else None)
+            gr.tensors = bufs + (lr_dev, parts)      # what N.adamw_ema takes when the group is stepped alone
+            groups.append(gr)
+        self._plan = (key, (sq, groups))
+        return self._plan[1]
 
-    def _shard_sumsq(self):
-        """Sum of squares of the REDUCED gradient on this rank's slice, per parameter group, into the 2 x 256
-        partials of `_sumsq_all` (a group this rank holds nothing of contributes zeros); advances the device step
-        counter once.  The SUM of the ranks' partial vectors gives the global clip norms."""
+    # (`_shard_*`: the plan's range is this rank's shard -- everything when the optimiser is replicated; the virtual-rank
+    # tests and tools/asan_driver.py drive these two halves by hand under these names)
+    def _shard_sumsq(self, plan=None):
+        """Sum of squares of the (reduced) gradient per parameter group, into the 256 clip-norm partials of each
+        (sharded: the SUM of the ranks' partial vectors in `_sumsq_all` gives the global norms); advances the device
+        step counter once."""
         if self.grad_clip <= 0:
             N.step_advance(self.step_dev)
             return
-        c = self._shard_views()
-        if self.knot_end:
-            N.sumsq2(c["g_mlp"], self.sumsq, c["g_knot"], self.sumsq_basis, step_inc=self.step_dev)
-        else:
-            N.sumsq(c["g_mlp"], self.sumsq, step_inc=self.step_dev)
+        sq = (plan or self._adam_plan())[0]
+        (N.sumsq2 if len(sq) == 4 else N.sumsq)(*sq, step_inc=self.step_dev)
 
-    def _shard_adamw(self):
-        """AdamW + EMA on this rank's slice (moments / EMA shadow indexed from `lo`), each group with its own learning
-        rate and its GLOBAL clip norm (the summed partials in `_sumsq_all`)."""
-        c = self._shard_views()
+    def _shard_adamw(self, plan=None):
+        """AdamW + EMA of the plan's groups in one launch, each with its own learning rate and clip norm."""
+        groups = (plan or self._adam_plan())[1]
         watch = self.loss_sum if self.nonfinite is not None else None
-        groups = c["groups"]
         if len(groups) == 2:
             N.adamw_ema2(groups[0], groups[1], self.betas, self.eps, self.wd, self.step_count + 1,
                          ema_decay=self.ema_decay, step_dev=self.step_dev, loss_watch=watch,
                          nonfinite_step=self.nonfinite)
         elif groups:
-            (p_, g_, m_, v_, e_), lr, max_norm, parts, lr_dev = c["single"]
-            N.adamw_ema(p_, g_, m_, v_, e_, lr, self.betas, self.eps, self.wd, self.step_count + 1, max_norm=max_norm,
-                        sumsq_parts=parts, ema_decay=self.ema_decay, lr_dev=lr_dev, step_dev=self.step_dev,
-                        loss_watch=watch, nonfinite_step=self.nonfinite)
+            gr = groups[0]
+            p_, g_, m_, v_, e_, lr_dev, parts = gr.tensors
+            N.adamw_ema(p_, g_, m_, v_, e_, gr.lr, self.betas, self.eps, self.wd, self.step_count + 1,
+                        max_norm=gr.max_norm, sumsq_parts=parts, ema_decay=self.ema_decay, lr_dev=lr_dev,
+                        step_dev=self.step_dev, shadow=gr._keep, loss_watch=watch, nonfinite_step=self.nonfinite)
+
+    def _enqueue_optimizer(self):
+        """Split path, second half: clip norm(s) of the (reduced) gradient, AdamW + EMA; advances the device
+        step counter once."""
+        plan = self._adam_plan()
+        self._shard_sumsq(plan)
+        self._shard_adamw(plan)
 
     def _enqueue_sharded_optimizer(self):
         """reduce-scatter(gradient) -> local sum of squares -> all-reduce(2 x 256 partials) -> AdamW/EMA on the slice
         -> all-gather(parameters) [-> bf16 operand copies re-rounded from the gathered master weights]."""
         mine = self.grad[self.lo:self.hi]
         self._timed(lambda: D.reduce_scatter_gradients(self.grad, mine, self.pg))
-        self._shard_sumsq()
+        plan = self._adam_plan()
+        self._shard_sumsq(plan)
         if self.grad_clip > 0:
             n = 2 * N.SUMSQ_PARTS if self.knot_end else N.SUMSQ_PARTS
             self._timed(lambda: D.allreduce_gradients(self._sumsq_all[:n], self.pg))
-        self._shard_adamw()
+        self._shard_adamw(plan)
         self._timed(lambda: D.allgather_parameters(self.flat, self.flat[self.lo:self.hi], self.pg))
         if self._shadow_regions:
             self.refresh_bf16()
@@ -582,50 +618,6 @@ class TrainStep:
             m = self.model
             N.sparsity(self._sparsity, self._w0t, self._g_w0t, True, m.p, m.k_spatial, m.k_temporal,
                        grad_scale=1.0 / self.world, loss_scale=float(B * Q), loss_sum=self.loss_sum)
-
-    def _enqueue_optimizer(self):
-        """Split path, second half: clip norm(s) of the (reduced) gradient, AdamW + EMA; advances the device
-        step counter once."""
-        ke = self.knot_end
-        watch = self.loss_sum if self.nonfinite is not None else None
-        if ke and self.grad_clip > 0:
-            # learnable knots: both groups' clip norms in one launch, both AdamW/EMA updates in one launch.
-            # The two group descriptors (14 buffer addresses, 10 slices) only change when a buffer or a rate does:
-            # rebuilt per step they were a quarter of this path's host time, and this path is host-bound.
-            ema = self.ema
-            key = (self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                   ema.data_ptr() if ema is not None else 0, self.lr, self.basis_lr, self.grad_clip, self.basis_clip,
-                   ke, id(self.lr_dev), id(self.basis_lr_dev), len(self._shadow_regions))
-            if self._adam_groups is None or self._adam_groups[0] != key:
-                g_mlp = N.make_adam_group(self.flat[ke:], self.grad[ke:], self.m[ke:], self.v[ke:],
-                                          ema[ke:] if ema is not None else None, self.lr, self.lr_dev, self.grad_clip,
-                                          self.sumsq, shadow=self._shadow(ke))
-                g_knot = N.make_adam_group(self.flat[:ke], self.grad[:ke], self.m[:ke], self.v[:ke],
-                                           ema[:ke] if ema is not None else None, self.basis_lr, self.basis_lr_dev,
-                                           self.basis_clip, self.sumsq_basis)
-                self._adam_groups = (key, g_mlp, g_knot, self.grad[ke:], self.grad[:ke])
-            _, g_mlp, g_knot, gv_mlp, gv_knot = self._adam_groups
-            N.sumsq2(gv_mlp, self.sumsq, gv_knot, self.sumsq_basis, step_inc=self.step_dev)
-            N.adamw_ema2(g_mlp, g_knot, self.betas, self.eps, self.wd, self.step_count + 1,
-                         ema_decay=self.ema_decay, step_dev=self.step_dev, loss_watch=watch,
-                         nonfinite_step=self.nonfinite)
-            return
-        if self.grad_clip > 0:
-            N.sumsq(self.grad[ke:], self.sumsq, step_inc=self.step_dev)
-            if ke:
-                N.sumsq(self.grad[:ke], self.sumsq_basis)
-        else:
-            N.step_advance(self.step_dev)
-        ema = self.ema
-        N.adamw_ema(self.flat[ke:], self.grad[ke:], self.m[ke:], self.v[ke:], ema[ke:] if ema is not None else None,
-                    self.lr, self.betas, self.eps, self.wd, self.step_count + 1, max_norm=self.grad_clip,
-                    sumsq_parts=self.sumsq, ema_decay=self.ema_decay, lr_dev=self.lr_dev, step_dev=self.step_dev,
-                    shadow=self._shadow(ke), loss_watch=watch, nonfinite_step=self.nonfinite)
-        if ke:
-            N.adamw_ema(self.flat[:ke], self.grad[:ke], self.m[:ke], self.v[:ke], ema[:ke] if ema is not None else None,
-                        self.basis_lr, self.betas, self.eps, self.wd, self.step_count + 1, max_norm=self.basis_clip,
-                        sumsq_parts=self.sumsq_basis, ema_decay=self.ema_decay, lr_dev=self.basis_lr_dev,
-                        step_dev=self.step_dev)
 
     def set_virtual_rank(self, rank):
         """Tests of the data-parallel arithmetic on one GPU: play rank `rank` of `world_size` (dropout stream
@@ -713,7 +705,7 @@ class TrainStep:
                         torch.empty(B, 2, device=self.dev), torch.empty(B, device=self.dev),
                         torch.empty(B, yc, device=self.dev),
                         torch.empty(B, p, device=self.dev) if p > 0 else None)
-            self._ix_graph = None
+            self._ix_graph.graph = None
         ib, cb, tb, yb, xb = self._ix
         t_all = t_all.view(-1)
         Xa = X_all if p > 0 else None
@@ -723,8 +715,7 @@ class TrainStep:
         src = ib if graphed else (idx if idx.is_contiguous() else idx.contiguous())
         if self.uses_window and not graphed and (next_idx is not None or self._prepared is not None):
             # announcements are keyed on the CALLER's tensors (a .contiguous() copy has a new address every call)
-            self._step_pipelined(coords_all, t_all, y_all, Xa, src, next_idx, B, global_rows,
-                                 key=(idx.data_ptr(), idx.numel(), idx.stride(0) if idx.dim() else 1))
+            self._step_pipelined(coords_all, t_all, y_all, Xa, src, next_idx, B, global_rows, _idx_key(idx))
             self._stepped(B)
             return
 
@@ -738,19 +729,7 @@ class TrainStep:
 
         if graphed:
             ib.copy_(idx)
-        if graphed:
-            if not self._warm:
-                self._warm = True
-                enqueue()
-            else:
-                key = (B, global_rows, coords_all.data_ptr(), t_all.data_ptr(), y_all.data_ptr())
-                if self._ix_graph is None or self._ix_graph[0] != key:
-                    torch.cuda.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        enqueue()
-                    self._ix_graph = (key, g)
-                self._ix_graph[1].replay()
+            self._ix_graph.run((B, global_rows, coords_all.data_ptr(), t_all.data_ptr(), y_all.data_ptr()), enqueue)
         else:
             enqueue()
         self._stepped(B)
@@ -795,9 +774,9 @@ class TrainStep:
                     break
         return self.mean_loss()
 
-    def _step_pipelined(self, coords_all, t_all, y_all, Xa, idx, next_idx, B, global_rows, key=None):
+    def _step_pipelined(self, coords_all, t_all, y_all, Xa, idx, next_idx, B, global_rows, key):
         """Step on a batch that was (or is now) binned into one of two workspaces, and batch
-        preparation of `next_idx` on the side stream into the other one."""
+        preparation of `next_idx` on the side stream into the other one.  `key`: _idx_key of the caller's `idx`."""
         main = torch.cuda.current_stream(self.dev)
         if self._pipe is None:
             # events without the system-scope fence (both streams are on this device): 3 us per step
@@ -806,47 +785,36 @@ class TrainStep:
             self._pipe = dict(ws=[self.ws, torch.empty_like(self.ws)], stream=torch.cuda.Stream(device=self.dev),
                               announce=mk(), binned=mk(), last=1)
         pp = self._pipe
-        st = self.state
         prep = self._prepared
         self._prepared = None
-        if key is None:
-            key = (idx.data_ptr(), idx.numel(), idx.stride(0) if idx.dim() else 1)
-        if prep is not None and prep[0] == key:
-            wsi, prebinned = prep[1], True
-            if not prep[3]:
+        if prep is not None and prep.key == key:
+            wsi, prebinned = prep.ws_index, True
+            if not prep.inline:
                 _wait(main, pp["binned"])       # (prepared inside the previous step's optimiser launch: same stream)
         else:
             wsi, prebinned = 1 - pp["last"], False        # not announced: bin inside the step, in place
-            if prep is not None and not prep[3]:
+            if prep is not None and not prep.inline:
                 # another batch was announced: the side stream may still be binning it into exactly this workspace
                 _wait(main, pp["binned"])
-        # one-call step on a small batch: the NEXT batch is binned by extra workgroups of this step's optimiser launch
-        # (no side stream, no cross-stream packets in the main queue: DESIGN.md section 8, "the bubble between steps")
-        inline = (next_idx is not None and self._whole_step and self.inline_prep and not self.distributed
-                  and next_idx.numel() <= 8192 and next_idx.dtype == torch.int64)
-        if inline:
-            nxt = next_idx if next_idx.is_contiguous() else next_idx.contiguous()
-            wsj = 1 - wsi
-            me = idx if idx.is_contiguous() else idx.contiguous()
-            done = self._enqueue(Xa, coords_all, t_all, y_all, B, global_rows, idx=me, ws=pp["ws"][wsi],
-                                 prebinned=prebinned, nxt=(nxt, pp["ws"][wsj]))
-            if done:
-                self._prepared = ((next_idx.data_ptr(), next_idx.numel(), next_idx.stride(0) if next_idx.dim() else 1),
-                                  wsj, nxt, True)
-                pp["last"] = wsi
-                return
-            # (the library did not take it -- e.g. more than 64 x 64 cells: the step itself is done, prepare as usual)
-            pp["announce"].record(main)
-            _wait(pp["stream"], pp["announce"])
-            with torch.cuda.stream(pp["stream"]):
-                N.bin_batch(st.basis, st.desc, coords_all, t_all, Xa, y_all, nxt, pp["ws"][wsj], st.flags)
-                pp["binned"].record(pp["stream"])
-            self._prepared = ((next_idx.data_ptr(), next_idx.numel(), next_idx.stride(0) if next_idx.dim() else 1),
-                              wsj, nxt, False)
-            pp["last"] = wsi
-            return
+        resident = (coords_all, t_all, y_all, Xa)
+        nxt = None
         if next_idx is not None:
             nxt = next_idx if next_idx.is_contiguous() else next_idx.contiguous()
+        # one-call step on a small batch: the NEXT batch is binned by extra workgroups of this step's optimiser launch
+        # (no side stream, no cross-stream packets in the main queue: DESIGN.md section 8, "the bubble between steps")
+        if (nxt is not None and self._whole_step and self.inline_prep and not self.distributed
+                and nxt.numel() <= 8192 and nxt.dtype == torch.int64):
+            me = idx if idx.is_contiguous() else idx.contiguous()
+            if self._enqueue(Xa, coords_all, t_all, y_all, B, global_rows, idx=me, ws=pp["ws"][wsi],
+                             prebinned=prebinned, nxt=(nxt, pp["ws"][1 - wsi])):
+                self._prepared = _Announced(_idx_key(next_idx), 1 - wsi, nxt, True)
+            else:
+                # the library did not take it -- e.g. more than 64 x 64 cells: the step itself is done, prepare as usual
+                pp["announce"].record(main)
+                self._announce_on_side_stream(next_idx, nxt, 1 - wsi, resident)
+            pp["last"] = wsi
+            return
+        if nxt is not None:
             # the side stream starts after everything enqueued on the main stream so far: the step that last
             # used that workspace (the previous one), AND whatever produced `next_idx` and the resident arrays
             # (a device randperm at the start of an epoch is a multi-kernel sort on the main stream)
@@ -858,41 +826,38 @@ class TrainStep:
             self._enqueue(None, None, None, y_all, B, global_rows, ws=pp["ws"][wsi], prebinned=True)
         else:
             self._enqueue(Xa, coords_all, t_all, y_all, B, global_rows, idx=idx, ws=pp["ws"][wsi])
-        if next_idx is not None:
-            wsj = 1 - wsi
-            _wait(pp["stream"], pp["announce"])
-            with torch.cuda.stream(pp["stream"]):
-                N.bin_batch(st.basis, st.desc, coords_all, t_all, Xa, y_all, nxt, pp["ws"][wsj], st.flags)
-                pp["binned"].record(pp["stream"])
-            self._prepared = ((next_idx.data_ptr(), next_idx.numel(), next_idx.stride(0) if next_idx.dim() else 1),
-                              wsj, nxt, False)
+        if nxt is not None:
+            self._announce_on_side_stream(next_idx, nxt, 1 - wsi, resident)
         pp["last"] = wsi
 
+    def _announce_on_side_stream(self, next_idx, nxt, wsj, resident):
+        """Bin rows `nxt` (the contiguous `next_idx`) of the resident arrays into workspace `wsj` on the side stream,
+        behind the `announce` event that the caller has recorded on the main stream."""
+        pp, st = self._pipe, self.state
+        coords_all, t_all, y_all, Xa = resident
+        _wait(pp["stream"], pp["announce"])
+        with torch.cuda.stream(pp["stream"]):
+            N.bin_batch(st.basis, st.desc, coords_all, t_all, Xa, y_all, nxt, pp["ws"][wsj], st.flags)
+            pp["binned"].record(pp["stream"])
+        self._prepared = _Announced(_idx_key(next_idx), wsj, nxt, False)
+
     def _step_graph(self, X, coords, t, y, B, global_rows):
-        if not self._warm:
-            # the first step runs eagerly: HIP loads code objects and applies the kernels' LDS
-            # attributes on first launch, neither of which may happen inside a stream capture
-            self._warm = True
-            self._enqueue(X, coords, t, y, B, global_rows)
-            return
-        if self._graph is None or self._g_B != (B, global_rows, y.shape[1]):
-            p = self.model.p
-            self._g_in = (torch.empty(B, p, device=self.dev) if p > 0 else None,
-                          torch.empty(B, 2, device=self.dev), torch.empty(B, device=self.dev),
-                          torch.empty(B, y.shape[1], device=self.dev))
-            self._g_B = (B, global_rows, y.shape[1])
-            # AdamW and the dropout generator read lr / step from device scalars, so a replay
-            # advances them; capture itself executes nothing
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._enqueue(self._g_in[0], self._g_in[1], self._g_in[2], self._g_in[3], B, global_rows)
-            self._graph = g
-        gi = self._g_in
-        if gi[0] is not None:
-            gi[0].copy_(X)
-        gi[1].copy_(coords); gi[2].copy_(t); gi[3].copy_(y)
-        self._graph.replay()
+        g, key = self._graph, (B, global_rows, y.shape[1])
+        ins = (X, coords, t, y)             # the eager first step reads the caller's tensors
+        if g.warm:
+            if g.stale(key):                # static inputs of the capture that run() is about to make
+                p = self.model.p
+                self._g_in = (torch.empty(B, p, device=self.dev) if p > 0 else None,
+                              torch.empty(B, 2, device=self.dev), torch.empty(B, device=self.dev),
+                              torch.empty(B, y.shape[1], device=self.dev))
+            ins = self._g_in
+
+        def copy_in():
+            for dst, src in zip(self._g_in, (X, coords, t, y)):
+                if dst is not None:
+                    dst.copy_(src)
+
+        g.run(key, lambda: self._enqueue(*ins, B, global_rows), before_replay=copy_in)
 
     def mean_loss(self, reset=True):
         """Mean batch objective (MSE, or check loss + penalties) over the rows seen since the last
@@ -955,8 +920,7 @@ class Predictor:
         self.ws = torch.empty(N.step_workspace_bytes(self.state.basis, self.state.desc, self.chunk,
                                                      self.state.flags) // 4, device=self.dev)
         self.use_graph = use_graph
-        self._graph = None
-        self._warm = False
+        self._graph = _GraphRunner()
         self._in = (torch.empty(self.chunk, 2, device=self.dev), torch.empty(self.chunk, device=self.dev))
         self._out = torch.empty(self.chunk, model.output_dim, device=self.dev)
 
@@ -975,7 +939,7 @@ class Predictor:
         if key != self._state_key:
             self.state = self.model._step_state(self.dev, force_dense=self.force_dense, training=False)
             self._state_key = key
-            self._graph = None
+            self._graph.graph = None
 
     def _enqueue(self, coords, t, out, B):
         st = self.state
@@ -1036,18 +1000,15 @@ class Predictor:
         out = torch.empty(n, self.model.output_dim, device=self.dev)
         for s in range(0, n, self.chunk):
             B = min(self.chunk, n - s)
-            if self.use_graph and B == self.chunk and not self._warm:
-                self._warm = True           # first full chunk eagerly (see TrainStep._step_graph)
-                self._enqueue(coords[s:s + B], t[s:s + B], out[s:s + B], B)
-            elif self.use_graph and B == self.chunk:
-                if self._graph is None:
-                    torch.cuda.synchronize()
-                    self._graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self._graph):
-                        self._enqueue(self._in[0], self._in[1], self._out, B)
-                self._in[0].copy_(coords[s:s + B]); self._in[1].copy_(t[s:s + B])
-                self._graph.replay()
+            here = (coords[s:s + B], t[s:s + B], out[s:s + B])
+            if not (self.use_graph and B == self.chunk):
+                self._enqueue(*here, B)
+                continue
+            # full chunks: the first one eagerly and in place, the later ones replayed on the static buffers
+            replay = self._graph.warm
+            ins = (self._in[0], self._in[1], self._out) if replay else here
+            self._graph.run(None, lambda: self._enqueue(*ins, B),
+                            before_replay=lambda: (self._in[0].copy_(here[0]), self._in[1].copy_(here[1])))
+            if replay:
                 out[s:s + B].copy_(self._out)
-            else:
-                self._enqueue(coords[s:s + B], t[s:s + B], out[s:s + B], B)
         return out

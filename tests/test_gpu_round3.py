@@ -502,7 +502,7 @@ def test_next_batch_binned_inside_the_optimiser_launch(name, B, dtype):
             if i == 1:
                 # (6 000 rows take a 128 x 128 cell grid: the library declines, the engine prepares on the side stream)
                 # (STNF_NO_INLINE_PREP=1 in the environment switches it off for every engine)
-                assert eng._prepared is not None and eng._prepared[3] == (eng.inline_prep and B <= 4096)
+                assert eng._prepared is not None and eng._prepared.inline == (eng.inline_prep and B <= 4096)
         torch.cuda.synchronize()
         res.append((eng.flat.clone(), eng.mean_loss(), int(eng.step_dev.item())))
     assert res[0][2] == res[1][2] == len(batches)
