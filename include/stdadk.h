@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STDADK_ABI_VERSION 8
+#define STDADK_ABI_VERSION 9
 #define STDADK_MAX_HIDDEN 8
 #define STDADK_MAX_LEVELS 8
 #define STDADK_SUMSQ_PARTS 256 /* partial sums written by stdadk_sumsq_f32 */
@@ -475,6 +475,45 @@ int stdadk_train_step_next_f32(const stdadk_basis_desc *basis, const stdadk_mlp_
                                size_t workspace_bytes, uint64_t drop_seed, int32_t flags, const stdadk_optim_desc *opt,
                                const int64_t *next_idx, int64_t next_B, int32_t next_y_cols, void *next_workspace,
                                size_t next_workspace_bytes, int32_t *next_binned, stdadk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Validation (ABI 9): evaluate_model and the validation half of train_model's epoch
+ * (scripts/train_st_interp.py:737-806,884-961) on rows idx[b] (int64, device) of the RESIDENT arrays, forward only.
+ *
+ * The rows are binned exactly as stdadk_bin_batch_f32 / the indexed training step bin them (window path), or gathered
+ * into the workspace (materialising path); the forward runs in eval mode (no dropout, nothing saved for a backward);
+ * then a metrics pass reads the predictions and the carried targets in the workspace's own row order and ADDS into
+ * `acc`, STDADK_EVAL_SLOTS doubles on the device:
+ *   acc[STDADK_EVAL_OBJECTIVE] += batch_weight * sum of the training objective's element terms (NULL loss: squared
+ *                                 errors; PINBALL: check loss + prediction-level non-crossing penalty, the arithmetic
+ *                                 of stdadk_loss_f32).  batch_weight = 1/(B*Q) makes a sequence of calls accumulate the
+ *                                 SUM OF BATCH MEANS the reference divides by len(val_loader), ragged last batch included
+ *   acc[STDADK_EVAL_SSE], acc[STDADK_EVAL_SAE] += squared / absolute error of output column `metric_col` against its
+ *                                 target (column metric_col of y, or the single column when loss->y_cols == 1)
+ *   acc[STDADK_EVAL_ROWS] += B;   acc[STDADK_EVAL_BATCHES] += 1
+ *   acc[STDADK_EVAL_CHECK + q] += sum_b max((tau_q-1) e, tau_q e), e = y - y_pred[:,q], q < Q  (tau = 0.5 without a
+ *                                 PINBALL descriptor)
+ * Deterministic: per-workgroup partial sums in a fixed order, finished in double in a fixed order by one workgroup of
+ * a second launch -- the same call on the same data gives the same bits (no atomics).  `params` may point into ANY
+ * buffer of the parameters' layout (the live weights or an EMA shadow).  y_pred (optional, NULL = skip): predictions
+ * [B,Q] in the caller's order, row b <-> idx[b].  Workspace: stdadk_eval_workspace_bytes (the step workspace -- the full
+ * plan of a training step, so that binning and forward are shared as they are -- plus the partials and the gather buffers).  No host read, no allocation, capturable.
+ * ------------------------------------------------------------------------------------------ */
+#define STDADK_EVAL_OBJECTIVE 0
+#define STDADK_EVAL_SSE 1
+#define STDADK_EVAL_SAE 2
+#define STDADK_EVAL_ROWS 3
+#define STDADK_EVAL_BATCHES 4
+#define STDADK_EVAL_CHECK 5
+#define STDADK_EVAL_SLOTS 16
+size_t stdadk_eval_workspace_bytes(const stdadk_basis_desc *basis, const stdadk_mlp_desc *mlp, int64_t B,
+                                   int32_t flags);
+int stdadk_eval_indexed_f32(const stdadk_basis_desc *basis, const stdadk_mlp_desc *mlp,
+                            const stdadk_mlp_tensors *params, const float *coords_all, const float *t_all,
+                            const float *X_all, const float *y_all, const int64_t *idx, int64_t B,
+                            const stdadk_loss_desc *loss, int32_t metric_col, double batch_weight, double *acc,
+                            float *y_pred, void *workspace, size_t workspace_bytes, int32_t flags,
+                            stdadk_stream_t stream);
 
 /* A10 on a site x time prediction grid (the dense inference callers loop over time slices with the SAME S
  * sites in each, scripts/train_st_interp.py:1091-1107,1232-1248,1378-1409).  Layer 0's pre-activation of row

@@ -59,4 +59,21 @@ __device__ __forceinline__ float loss_elem(const LossDev &L, int Q, int q, float
   return term;
 }
 
+// One (row, q) element of the check loss on its own (validation metrics): max((tau-1) e, tau e), e = y - y_pred.
+__device__ __forceinline__ float check_elem(float tau, float yq, float yt) {
+  const float e = yt - yq;
+  return fmaxf((tau - 1.0f) * e, tau * e);
+}
+
+// Validation metrics of one batch (eval.hip): values a workgroup leaves per partial -- objective, squared and absolute
+// error of the metric column, per-level check loss.
+constexpr int EVAL_V_OBJ = 0, EVAL_V_SSE = 1, EVAL_V_SAE = 2, EVAL_V_CHECK = 3;
+constexpr int EVAL_VALS = EVAL_V_CHECK + STDADK_MAX_Q;
+constexpr int EVAL_MAX_WG = 1024;
+int eval_partials_blocks(int64_t B);
+// yp [B,Q] and y [B, L.y_cols] in the SAME row order (any); part: EVAL_MAX_WG * EVAL_VALS doubles of scratch;
+// acc: the STDADK_EVAL_SLOTS doubles stdadk_eval_indexed_f32 adds into.
+int launch_eval_metrics(const LossDev &L, const float *yp, const float *y, int64_t B, int Q, int metric_col,
+                        double batch_weight, double *part, double *acc, hipStream_t st);
+
 }  // namespace stdadk

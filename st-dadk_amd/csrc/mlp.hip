@@ -16,6 +16,7 @@
 #include "bin_body.h"
 #include "knots.h"
 #include "basis.h"
+#include "loss.h"
 
 #include <stdlib.h>
 
@@ -1797,4 +1798,84 @@ extern "C" int stdadk_train_fwd_bwd_indexed_f32(const stdadk_basis_desc *b, cons
   STDADK_REQUIRE(idx || B == 0, STDADK_E_ARG, "train_fwd_bwd_indexed: idx is NULL");
   return train_fwd_bwd_impl(b, d, P, G, coords_all, t_all, X_all, y_all, idx, B, grad_scale, loss, loss_sum, y_pred,
                             workspace, workspace_bytes, drop_seed, step_dev, flags, stream, aux_stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// validation: indexed forward-only pass + deterministic metrics (eval.hip)
+// ---------------------------------------------------------------------------------------------
+namespace stdadk {
+// the evaluation workspace: [ step plan | metric partials (doubles) | gather buffers of the materialising path ]
+struct EvalPlan {
+  size_t step_bytes, part, coords, t, y, X, total;     // byte offsets
+};
+static EvalPlan eval_plan(size_t step_bytes, int64_t B, int Q, int p) {
+  EvalPlan e;
+  size_t off = align_up(step_bytes, 256);
+  e.step_bytes = step_bytes;
+  auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes > 0 ? bytes : 1, 256); return o; };
+  e.part = take((size_t)EVAL_MAX_WG * EVAL_VALS * sizeof(double));
+  e.coords = take((size_t)B * 2 * sizeof(float));
+  e.t = take((size_t)B * sizeof(float));
+  e.y = take((size_t)B * Q * sizeof(float));
+  e.X = take((size_t)B * (p > 0 ? p : 1) * sizeof(float));
+  e.total = off;
+  return e;
+}
+}  // namespace stdadk
+
+extern "C" size_t stdadk_eval_workspace_bytes(const stdadk_basis_desc *b, const stdadk_mlp_desc *d, int64_t B,
+                                              int32_t flags) {
+  const size_t step = stdadk_step_workspace_bytes(b, d, B, flags & ~STDADK_FLAG_PREBINNED);
+  if (step == 0) return 0;
+  return eval_plan(step, B > 0 ? B : 1, d->out_dim, b->p).total;
+}
+
+extern "C" int stdadk_eval_indexed_f32(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
+                                       const stdadk_mlp_tensors *P, const float *coords_all, const float *t_all,
+                                       const float *X_all, const float *y_all, const int64_t *idx, int64_t B,
+                                       const stdadk_loss_desc *loss, int32_t metric_col, double batch_weight,
+                                       double *acc, float *y_pred, void *workspace, size_t workspace_bytes,
+                                       int32_t flags, stdadk_stream_t stream) {
+  STDADK_REQUIRE(B >= 0, STDADK_E_ARG, "eval_indexed: negative B");
+  if (B == 0) return 0;
+  STDADK_REQUIRE(!(flags & STDADK_FLAG_PREBINNED), STDADK_E_ARG, "eval_indexed: STDADK_FLAG_PREBINNED is not accepted");
+  STDADK_REQUIRE(workspace_bytes >= 256, STDADK_E_WORKSPACE, "eval_indexed: workspace %zu bytes", workspace_bytes);
+  Ctx c;
+  bool window;
+  // the step plan is validated against whatever the workspace holds; the evaluation's own buffers are checked below
+  int rc = step_common(c, b, d, B, workspace, workspace_bytes, flags, &window);
+  if (rc) return rc;
+  const int Q = d->out_dim;
+  const EvalPlan ep = eval_plan(c.pl.total_floats * sizeof(float), B, Q, b->p);
+  STDADK_REQUIRE(workspace_bytes >= ep.total, STDADK_E_WORKSPACE,
+                 "eval_indexed: workspace %zu < %zu bytes (stdadk_eval_workspace_bytes)", workspace_bytes, ep.total);
+  STDADK_REQUIRE(P && coords_all && t_all && y_all && idx && acc, STDADK_E_ARG, "eval_indexed: NULL pointer");
+  STDADK_REQUIRE(b->p == 0 || X_all, STDADK_E_ARG, "eval_indexed: X_all is NULL with p=%d", b->p);
+  STDADK_REQUIRE((reinterpret_cast<uintptr_t>(acc) & 7) == 0, STDADK_E_ALIGN, "eval_indexed: acc not 8-byte aligned");
+  STDADK_REQUIRE(Q <= STDADK_MAX_Q, STDADK_E_ARG, "eval_indexed: Q=%d above %d", Q, STDADK_MAX_Q);
+  STDADK_REQUIRE(metric_col >= 0 && metric_col < Q, STDADK_E_ARG, "eval_indexed: metric_col=%d outside 0..%d",
+                 metric_col, Q - 1);
+  rc = make_loss(loss, Q, &c.loss);
+  if (rc) return rc;
+  const LossDev L = c.loss;
+  c.P = P; c.G = nullptr; c.st = (hipStream_t)stream;
+  c.dp = 0.f; c.seed = 0; c.step_dev = nullptr; c.save = false;      // eval mode: no dropout, nothing kept for a backward
+  char *base = (char *)workspace;
+  double *part = (double *)(base + ep.part);
+  if (window) {
+    // the indexed training step's binning: rows idx[b] read in place, targets carried into sorted order
+    c.idx = idx;
+    rc = step_forward(c, b, true, coords_all, t_all, X_all, y_all, y_pred, stream);
+    if (rc) return rc;
+    return launch_eval_metrics(L, c.ws + c.pl.ypred, c.ws + c.pl.y_s, B, Q, metric_col, batch_weight, part, acc, c.st);
+  }
+  float *cg = (float *)(base + ep.coords), *tg = (float *)(base + ep.t), *yg = (float *)(base + ep.y);
+  float *Xg = b->p > 0 ? (float *)(base + ep.X) : nullptr;
+  rc = stdadk_gather_batch_f32(coords_all, t_all, y_all, b->p > 0 ? X_all : nullptr, idx, B, L.y_cols, b->p, cg, tg, yg,
+                               Xg, stream);
+  if (rc) return rc;
+  float *yp = y_pred ? y_pred : c.ws + c.pl.ypred;
+  rc = step_forward(c, b, false, cg, tg, Xg, nullptr, yp, stream);
+  if (rc) return rc;
+  return launch_eval_metrics(L, yp, yg, B, Q, metric_col, batch_weight, part, acc, c.st);
 }

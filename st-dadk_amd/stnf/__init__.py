@@ -6,3 +6,14 @@ runs in libstdadk.so (hand-written HIP).  Put `st-dadk_amd/` on PYTHONPATH and t
 `scripts/train_st_interp.py` imports this package instead of its own.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # the epoch driver and the evaluator, imported on first use (they pull in torch and the native library)
+    if name in ("train_model", "evaluate_model"):
+        from . import training
+        return getattr(training, name)
+    if name == "Evaluator":
+        from .evaluation import Evaluator
+        return Evaluator
+    raise AttributeError(f"module 'stnf' has no attribute '{name}'")

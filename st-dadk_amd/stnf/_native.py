@@ -48,7 +48,7 @@ class BasisDesc(C.Structure):
                 ("t_bw", C.c_void_p)]
 
 
-ABI_VERSION = 8            # STDADK_ABI_VERSION of include/stdadk.h this binding was written against
+ABI_VERSION = 9            # STDADK_ABI_VERSION of include/stdadk.h this binding was written against
 MAX_Q = 8
 LOSS_MSE, LOSS_PINBALL = 0, 1
 
@@ -181,6 +181,11 @@ _SIGNATURES = {
                                                    C.c_float, C.POINTER(LossDesc), C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_int32,
                                                    C.c_void_p, C.c_void_p]),
+    "stdadk_eval_workspace_bytes": (C.c_size_t, [C.POINTER(BasisDesc), C.POINTER(MlpDesc), C.c_int64, C.c_int32]),
+    "stdadk_eval_indexed_f32": (C.c_int, [C.POINTER(BasisDesc), C.POINTER(MlpDesc), C.POINTER(MlpTensors),
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.POINTER(LossDesc), C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
     "stdadk_bin_batch_f32": (C.c_int, [C.POINTER(BasisDesc), C.POINTER(MlpDesc), C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                        C.c_size_t, C.c_int32, C.c_void_p]),
@@ -620,6 +625,33 @@ def bin_batch(basis, desc, coords_all, t_all, X_all, y_all, idx, workspace, flag
                                     y_all.shape[1] if y_all is not None else 0, workspace.data_ptr(),
                                     workspace.numel() * workspace.element_size(), flags, _stream())
     _check(rc, "stdadk_bin_batch_f32")
+
+
+# slots of the float64 accumulator stdadk_eval_indexed_f32 adds into (include/stdadk.h)
+EVAL_OBJECTIVE, EVAL_SSE, EVAL_SAE, EVAL_ROWS, EVAL_BATCHES, EVAL_CHECK, EVAL_SLOTS = 0, 1, 2, 3, 4, 5, 16
+
+
+def eval_workspace_bytes(basis, desc, B, flags):
+    n = lib().stdadk_eval_workspace_bytes(C.byref(basis), C.byref(desc), B, flags)
+    if n == 0:
+        raise RuntimeError("stdadk_eval_workspace_bytes: invalid descriptors")
+    return n
+
+
+def eval_indexed(basis, desc, params, coords_all, t_all, X_all, y_all, idx, loss_desc, metric_col, batch_weight, acc,
+                 y_pred, workspace, flags):
+    """Forward-only pass on rows `idx` (contiguous int64 device tensor) of the resident arrays; the batch's metric
+    sums are ADDED into `acc` (EVAL_SLOTS float64 on the device); `y_pred` (B,Q) or None."""
+    if idx.dtype != torch.int64 or not _on_device(idx) or not idx.is_contiguous():
+        raise RuntimeError("eval_indexed: idx must be a contiguous int64 tensor on the device")
+    if acc.dtype != torch.float64 or not _on_device(acc) or not acc.is_contiguous() or acc.numel() < EVAL_SLOTS:
+        raise RuntimeError(f"eval_indexed: acc must be {EVAL_SLOTS} contiguous float64 on the device")
+    rc = lib().stdadk_eval_indexed_f32(
+        C.byref(basis), C.byref(desc), C.byref(params), _dev(coords_all, "coords"), _dev(t_all, "t"),
+        _dev(X_all, "X"), _dev(y_all, "y"), idx.data_ptr(), idx.numel(),
+        C.byref(loss_desc) if loss_desc is not None else None, int(metric_col), float(batch_weight), acc.data_ptr(),
+        _dev(y_pred, "y_pred"), workspace.data_ptr(), workspace.numel() * workspace.element_size(), flags, _stream())
+    _check(rc, "stdadk_eval_indexed_f32")
 
 
 def make_knot_train(centers_init, gradient_damping=False, damping_threshold=0.3, damping_strength=1.0,

@@ -321,6 +321,7 @@ class TrainStep:
         self.ws = torch.empty(N.step_workspace_bytes(self.state.basis, self.state.desc, B, self.state.flags) // 4,
                               device=self.dev)
         self.loss_sum = torch.zeros(1, device=self.dev)       # running sum of squared errors
+        self._loss_snap = None          # run_epoch(loss="batches"): copy of the accumulator before the last batch
         self.sumsq = torch.zeros(N.SUMSQ_PARTS, device=self.dev)
         self.lr_dev = torch.full((1,), self.lr, device=self.dev)
         self.step_dev = torch.zeros(1, device=self.dev, dtype=torch.int32)
@@ -734,7 +735,7 @@ class TrainStep:
             enqueue()
         self._stepped(B)
 
-    def run_epoch(self, dataset, batch_size, generator=None, shuffle=True, check_every=0):
+    def run_epoch(self, dataset, batch_size, generator=None, shuffle=True, check_every=0, on_step=None, loss="rows"):
         """One pass over a `stnf.dataio.device_dataset.DeviceDataset` in shuffled mini-batches (the
         epoch loop of scripts/train_st_interp.py:608-724 with the set resident in HBM): every step
         announces the next batch so that its preparation overlaps the running step.  Returns the mean
@@ -745,6 +746,13 @@ class TrainStep:
         step without a host sync; `check_every=k` reads it every k steps (one 4-byte read = one sync each) and stops
         the epoch there (`stopped_at` = index of the last batch stepped), `check_every=0` runs the epoch through and
         leaves the step in `first_nonfinite_step()`.
+
+        `on_step(i, batches)` (optional) is called before batch i of the epoch's index slices `batches` is enqueued: the
+        place for a per-step learning rate (`set_lr` during warm-up).  `loss="batches"` returns the reference's
+        `train_loss` instead, the mean of the BATCH means (scripts/train_st_interp.py:721,735; it differs from the
+        per-row mean when the last batch is ragged): the accumulator is copied on the device before the last batch
+        (4 bytes, no launch of the library, no sync) and both partial sums come back in the epoch's one read.  Single
+        process only; an epoch left early through `check_every` has a non-finite loss either way.
 
         Data-parallel: `dataset` is this rank's shard.  The shard sizes are all-gathered once per call (8 bytes per
         rank: every rank enters it, whatever it has cached) and `stnf.distributed.epoch_schedule` gives every rank the
@@ -760,8 +768,20 @@ class TrainStep:
             batches = dataset.epoch_batches(batch_size, generator=generator, shuffle=shuffle)
             rows = [None] * len(batches)
         self.stopped_at = None
+        if loss not in ("rows", "batches"):
+            raise ValueError(f"loss='{loss}'; use 'rows' or 'batches'")
+        if loss == "batches" and self.distributed:
+            raise RuntimeError("loss='batches' is per process; data-parallel epochs report the per-row mean")
+        sizes = [b.numel() for b in batches]
+        by_batch = loss == "batches" and len(set(sizes[:-1])) <= 1
         for i, idx in enumerate(batches):
             nxt = batches[i + 1] if i + 1 < len(batches) else None
+            if on_step is not None:
+                on_step(i, batches)
+            if by_batch and nxt is None:
+                if self._loss_snap is None:
+                    self._loss_snap = torch.zeros_like(self.loss_sum)
+                self._loss_snap.copy_(self.loss_sum)        # the accumulator before the last (ragged) batch
             self.step_indexed(dataset.coords, dataset.t, dataset.y, idx, X_all=dataset.X, global_rows=rows[i],
                               next_idx=nxt)
             if check_every and self.nonfinite is not None and (i + 1) % check_every == 0 and nxt is not None:
@@ -772,7 +792,19 @@ class TrainStep:
                 if int(bad.item()) > 0:
                     self.stopped_at = i
                     break
-        return self.mean_loss()
+        if not by_batch or self.stopped_at is not None:
+            return self.mean_loss()
+        return self._batch_mean_loss(sizes)
+
+    def _batch_mean_loss(self, sizes):
+        """Mean of the batch means of an epoch whose batches but the last have one size, from the accumulator and its
+        copy taken before the last batch (ONE host sync); resets the accumulator like mean_loss()."""
+        before_last, total = torch.stack([self._loss_snap[0], self.loss_sum[0]]).tolist()
+        self.loss_sum.zero_()
+        self.rows_seen = 0
+        Q = self.model.output_dim
+        head = before_last / (sizes[0] * Q) if len(sizes) > 1 else 0.0
+        return (head + (total - before_last) / (sizes[-1] * Q)) / len(sizes)
 
     def _step_pipelined(self, coords_all, t_all, y_all, Xa, idx, next_idx, B, global_rows, key):
         """Step on a batch that was (or is now) binned into one of two workspaces, and batch

@@ -1,0 +1,190 @@
+"""On-device validation: `Evaluator` runs the reference's evaluation passes (scripts/train_st_interp.py:737-806,
+884-961) over a `DeviceDataset` through stdadk_eval_indexed_f32 -- an indexed, forward-only pass per batch whose
+metric sums stay in a float64 accumulator on the device.  One host sync per call (one read of the accumulator).
+
+EMA weights (`params="ema"`, with the `TrainStep` that owns the shadow):
+  * fixed knots, no delta head, replicated optimiser -- the north-star path and every BASELINE configuration: the
+    parameter table points INTO `engine.ema` (same flat layout as the live buffer, W0 stored transposed), so nothing is
+    copied and nothing is swapped.  In bf16 mode the pass keeps the bf16 matrix cores: operand copies of the EMA
+    values are rounded into buffers of the evaluator's own by one stdadk_bf16_shadow_refresh launch per call;
+  * learnable knots, the delta head, the sharded optimiser: the pass is bracketed by `engine.swap_in_ema()`.
+Either way the live parameters, Adam moments, the shadow and the step counter are the same bits afterwards."""
+import torch
+import torch.distributed as dist
+
+from . import _native as N
+from . import losses
+
+
+class Evaluator:
+    """evaluate(dataset, batch_size, params="live"|"ema", engine=None) -> dict with the reference's keys
+    `mse, mae, rmse` (of the median level `Q // 2` for several outputs), `check_loss` (quantile), `mean_check_loss`,
+    `check_loss`, `crps` (multi-quantile), plus `loss`: the mean over batches of the batch objective, the
+    reference's `val_loss` (with the delta head and `non_crossing_lambda > 0` the parameter-level P_nc(delta) is part
+    of every batch's objective, as scripts/train_st_interp.py:770-777 has it)."""
+
+    def __init__(self, model, loss="mse", quantile_levels=None, non_crossing_weight=0.0, non_crossing_power=1,
+                 non_crossing_lambda=0.0, max_batch=65536, force_dense=False, process_group=None):
+        if loss not in ("mse", "pinball"):
+            raise ValueError(f"unknown loss '{loss}'; use 'mse' or 'pinball'")
+        self.model = model
+        self.loss_kind = loss
+        self.quantile_levels = [float(q) for q in quantile_levels] if quantile_levels is not None else None
+        if loss == "pinball" and (self.quantile_levels is None or len(self.quantile_levels) != model.output_dim):
+            raise ValueError(f"pinball loss needs output_dim={model.output_dim} quantile levels")
+        self.nc_weight = 0.0 if model._has_delta else float(non_crossing_weight)
+        self.nc_power = int(non_crossing_power)
+        self.nc_lambda = float(non_crossing_lambda) if model._has_delta else 0.0
+        self.max_batch = int(max_batch)
+        self.force_dense = bool(force_dense)
+        self.pg = process_group
+        self.dev = next(model.parameters()).device
+        if self.dev.type != "cuda" and not N.dry_run():
+            raise RuntimeError("Evaluator needs the model on a HIP device; there is no CPU path")
+        self.acc = torch.zeros(N.EVAL_SLOTS, dtype=torch.float64, device=self.dev)
+        self.sums = None               # the accumulator of the last call as host floats
+        self._desc = None
+        self._loss_descs = {}
+        self._ws = {}
+        self._ema = None               # (key, parameter table over engine.ema, bf16 refresh table or None)
+
+    # ------------------------------------------------------------------------------------
+    def _loss_desc(self, y_cols):
+        Q = self.model.output_dim
+        if y_cols not in (1, Q):
+            raise RuntimeError(f"targets have {y_cols} columns; expected 1 or output_dim={Q}")
+        if self.loss_kind == "mse" and y_cols == Q:
+            return None
+        if y_cols not in self._loss_descs:
+            self._loss_descs[y_cols] = N.make_loss(self.loss_kind, Q, y_cols, self.quantile_levels, self.nc_weight,
+                                                   self.nc_power)
+        return self._loss_descs[y_cols]
+
+    def _workspace(self, basis, desc, B, flags):
+        B = max(int(B), self.max_batch)
+        key = int(flags)
+        ws = self._ws.get(key)
+        need = N.eval_workspace_bytes(basis, desc, B, flags)
+        if ws is None or ws.numel() * 4 < need:
+            ws = self._ws[key] = torch.empty((need + 3) // 4, device=self.dev)
+        return ws
+
+    @staticmethod
+    def ema_in_place(engine):
+        """True when the EMA pass reads `engine.ema` through views (no swap): fixed knots, no delta head,
+        replicated optimiser."""
+        return not engine.learnable and not engine.model._has_delta and not engine.shard
+
+    def _ema_params(self, eng):
+        """Parameter table over views of `eng.ema` (the flat layout of `eng.flat`: first weight stored (in,out))."""
+        m = self.model
+        key = (eng.ema.data_ptr(), eng.flat.data_ptr(), eng.dtype)
+        if self._ema is not None and self._ema[0] == key:
+            return self._ema[1], self._ema[2]
+        by_name = {n: (o, k) for n, o, k in eng.offsets}
+        names = {id(p): n for n, p in m.named_parameters()}
+        first_w = m._body[0].weight
+        tensors = []
+        for p in m._body_params():
+            o, k = by_name[names[id(p)]]
+            v = eng.ema[o:o + k]
+            tensors.append(v.view(p.shape[1], p.shape[0]) if p is first_w else v.view(p.shape))
+        pairs, table = None, None
+        if eng._shadow_regions:
+            # bf16 mode: operand copies of the EMA values in buffers of our own, re-rounded at the start of every pass
+            lins = m._linears()
+            pairs, regions = [None] * len(lins), []
+            for l in range(1, len(m.hidden_dims)):
+                h, hp = lins[l].weight.shape
+                wb = torch.empty(h, hp, device=self.dev, dtype=torch.bfloat16)
+                wt = torch.empty(hp, h, device=self.dev, dtype=torch.bfloat16)
+                pairs[l] = (wb, wt)
+                regions.append((by_name[names[id(lins[l].weight)]][0], h, hp, wb, wt))
+            table = N.make_bf16_shadow(regions)
+        params = m._pack(tensors, bf16=pairs)
+        params._views = (tensors, pairs)          # the descriptors hold raw addresses: keep the tensors alive
+        self._ema = (key, params, table)
+        return params, table
+
+    # ------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def evaluate(self, dataset, batch_size, params="live", engine=None):
+        if params not in ("live", "ema"):
+            raise ValueError(f"params='{params}'; use 'live' or 'ema'")
+        m = self.model
+        swapped = False
+        if params == "ema":
+            if engine is None or engine.ema is None:
+                raise RuntimeError("params='ema' needs the TrainStep that owns the shadow (built with ema_decay)")
+            if engine.model is not m:
+                raise RuntimeError("the engine trains another model")
+            if not self.ema_in_place(engine):
+                engine.swap_in_ema()
+                swapped = True
+        try:
+            return self._evaluate(dataset, int(batch_size), engine, ema_views=(params == "ema" and not swapped))
+        finally:
+            if swapped:
+                engine.swap_in_ema()
+
+    def _evaluate(self, dataset, batch_size, engine, ema_views):
+        m = self.model
+        if self._desc is None:
+            self._desc = m._native_desc(False)
+        desc = self._desc
+        if engine is not None:
+            engine._check_bf16_current()
+            st = engine.state
+            basis, flags, ptab = st.basis, st.flags, st.params
+            if self.force_dense:
+                flags |= N.FLAG_DENSE
+            if st.head is not None:
+                N.delta_head(st.delta, st.head[0], st.head[1])     # output layer of the delta values as they are now
+            if ema_views:
+                ptab, table = self._ema_params(engine)
+                if table is not None:
+                    N.bf16_shadow_refresh(engine.ema, table)
+        else:
+            st = m._step_state(self.dev, force_dense=self.force_dense, training=False)
+            basis, flags, ptab = st.basis, st.flags, st.params
+        Q = m.output_dim
+        metric_col = Q // 2
+        y_all = dataset.y
+        ldesc = self._loss_desc(y_all.shape[1])
+        X_all = dataset.X if m.p > 0 else None
+        t_all = dataset.t.view(-1)
+        batches = dataset.epoch_batches(batch_size, shuffle=False) if len(dataset) else ()
+        ws = self._workspace(basis, desc, max((b.numel() for b in batches), default=1), flags)
+        acc = self.acc
+        acc.zero_()
+        for idx in batches:
+            B = idx.numel()
+            N.eval_indexed(basis, desc, ptab, dataset.coords, t_all, X_all, y_all,
+                           idx if idx.is_contiguous() else idx.contiguous(), ldesc, metric_col, 1.0 / (B * Q), acc,
+                           None, ws, flags)
+        if self.nc_lambda > 0.0 and len(batches):
+            # parameter-level penalty of the delta head: the same value in every batch's objective
+            p_nc = losses.compute_p_nc_delta_penalty(list(m.delta_params))
+            acc[N.EVAL_OBJECTIVE] += (self.nc_lambda * len(batches)) * p_nc.double()
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.pg) > 1:
+            dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=self.pg)
+        self.sums = acc.tolist()                                   # the call's ONE host sync
+        return self.metrics(self.sums)
+
+    def metrics(self, sums):
+        """The reference's metric dict from the accumulator's sums."""
+        Q = self.model.output_dim
+        rows, nb = max(sums[N.EVAL_ROWS], 1.0), max(sums[N.EVAL_BATCHES], 1.0)
+        mse = sums[N.EVAL_SSE] / rows
+        out = {"mse": mse, "mae": sums[N.EVAL_SAE] / rows, "rmse": mse ** 0.5,
+               "loss": sums[N.EVAL_OBJECTIVE] / nb, "rows": int(sums[N.EVAL_ROWS])}
+        if self.loss_kind == "pinball":
+            checks = [sums[N.EVAL_CHECK + q] / rows for q in range(Q)]
+            if Q == 1:
+                out["check_loss"] = checks[0]
+            else:
+                # compute_crps_multi_quantile with its default weights: 2 x sum_k (1/K) x check loss at level k
+                out["crps"] = 2.0 * sum(c / Q for c in checks)
+                out["mean_check_loss"] = sum(checks) / Q
+                out["check_loss"] = out["mean_check_loss"]
+        return out

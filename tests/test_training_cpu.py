@@ -1,0 +1,286 @@
+"""CPU tests of stnf.training / stnf.evaluation / stdadk_eval_indexed_f32 (no GPU): with STDADK_DRY_RUN=1 the library
+validates and plans but launches nothing, so the epoch driver's control flow, its learning-rate sequence and the
+library calls of a validated epoch can be checked on host tensors.  stnf._native reads the variable at import, so this
+file is its own driver: run as a script in a child process it prints one JSON record, which the tests read."""
+import ctypes as C
+import json
+import math
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LR, EPOCHS, BATCH, ROWS, VAL_ROWS = 2e-2, 8, 64, 200, 150
+
+
+def _record(tmp):
+    for p in (ROOT, os.path.join(ROOT, "st-dadk_amd"), os.path.join(ROOT, "tests")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    assert os.environ.get("STDADK_DRY_RUN") == "1"
+    import torch
+    from stnf import _native as N
+    from stnf import training as T
+    from stnf.dataio.device_dataset import DeviceDataset
+    from stnf.engine import TrainStep
+    from stnf.evaluation import Evaluator
+    from stnf.models import STInterpMLP
+
+    def model(**kw):
+        torch.manual_seed(0)
+        return STInterpMLP(p=0, k_spatial_centers=[25, 81], k_temporal_centers=[10, 15], hidden_dims=[64, 64],
+                           dropout=0.0, layernorm=True, **kw)
+
+    def data(n, seed):
+        g = torch.Generator().manual_seed(seed)
+        return DeviceDataset(torch.rand(n, 2, generator=g), torch.rand(n, 1, generator=g), torch.randn(n, 1, generator=g))
+
+    class Stub:
+        """Scripted validation losses; records what it was asked."""
+        def __init__(self, losses):
+            self.losses, self.calls = list(losses), []
+
+        def evaluate(self, dataset, batch_size, params="live", engine=None):
+            self.calls.append((len(dataset), batch_size, params))
+            v = self.losses[len(self.calls) - 1]
+            return {"loss": v, "rmse": abs(v) ** 0.5 if v == v else v, "mse": v, "mae": v}
+
+    def watch(eng, log):
+        for name in ("set_lr", "set_basis_lr"):
+            fn = getattr(eng, name)
+            setattr(eng, name, (lambda f, n: lambda v: (log.append([n, eng.step_count, float(v)]), f(v))[1])(fn, name))
+
+    rec = {}
+    # --- 1. schedule + control flow: fixed knots, warm-up 1 epoch, cosine, scripted validation
+    cfg = {"lr": LR, "epochs": EPOCHS, "batch_size": BATCH, "warmup_epochs": 1, "scheduler": "cosine", "patience": 3,
+           "grad_clip": 10.0, "verbose": False}
+    losses = [0.9, 0.5, float("nan"), 0.7, 0.4, 0.45, 0.41, 0.6]
+    m = model()
+    n_batches = math.ceil(ROWS / BATCH)
+    eng = T.make_engine(m, cfg, BATCH, n_batches)
+    log = []
+    watch(eng, log)
+    stub = Stub(losses)
+    out_dir = os.path.join(tmp, "run1")
+    _, hist, _ = T.train_model(m, data(ROWS, 1), data(VAL_ROWS, 2), cfg, output_dir=out_dir, shuffle=False, engine=eng,
+                               evaluator=stub)
+    rec["fixed"] = {"hist": hist, "rates": log, "stub_calls": stub.calls, "files": sorted(os.listdir(out_dir)),
+                    "steps": eng.step_count, "ema_decay": eng.ema_decay, "wd": eng.wd,
+                    "csv": open(os.path.join(out_dir, "training_history.csv")).read().splitlines(),
+                    "keys": sorted(torch.load(os.path.join(out_dir, "model_best.pt")).keys()),
+                    "model_keys": sorted(m.state_dict().keys())}
+    # --- early stop + every validation NaN: no best, final EMA loaded, no model_best.pt
+    cfg2 = dict(cfg, patience=2, warmup_epochs=0)
+    m = model()
+    eng = T.make_engine(m, cfg2, BATCH, n_batches)
+    stub = Stub([float("nan")] * EPOCHS)
+    out_dir = os.path.join(tmp, "run2")
+    _, hist, _ = T.train_model(m, data(ROWS, 1), data(VAL_ROWS, 2), cfg2, output_dir=out_dir, shuffle=False, engine=eng,
+                               evaluator=stub)
+    rec["nan"] = {"epochs": len(hist["val_loss"]), "files": sorted(os.listdir(out_dir)),
+                  "best": eng.best_ema is None}
+    # --- the reference's schedules (tests/golden/sched_*.npz): the rate of every group at every step
+    from golden import training_cases as tc
+    rec["sched"] = {}
+    for name, case in tc.SCHED_CASES.items():
+        c = dict(case["config"], verbose=False)
+        m = model(spatial_learnable=True) if case["learnable"] else model()
+        nb = math.ceil(tc.SCHED_ROWS / tc.SCHED_BATCH)
+        eng = T.make_engine(m, c, tc.SCHED_BATCH, nb)
+        cur = {"set_lr": None, "set_basis_lr": None}
+        per_step = []
+        for nm in cur:
+            fn = getattr(eng, nm)
+            setattr(eng, nm, (lambda f, n: lambda v: (cur.__setitem__(n, float(v)), f(v))[1])(fn, nm))
+        step = eng.step_indexed
+
+        def stepping(*a, _step=step, _cur=cur, _out=per_step, _learn=case["learnable"], **kw):
+            _out.append([_cur["set_lr"]] + ([_cur["set_basis_lr"]] if _learn else []))
+            return _step(*a, **kw)
+        eng.step_indexed = stepping
+        _, hist, _ = T.train_model(m, data(tc.SCHED_ROWS, 1), data(tc.SCHED_VAL_ROWS, 2), c, shuffle=False, engine=eng,
+                                   evaluator=Stub([1.0 / (i + 1) for i in range(c["epochs"])]))
+        rec["sched"][name] = {"rates": per_step, "lr": hist["lr"]}
+
+    # --- 2. call trace of one validated epoch
+    real = N.lib()
+    calls = []
+
+    class Proxy:
+        def __getattr__(self, name):
+            fn = getattr(real, name)
+            if name in ("stdadk_last_error", "stdadk_abi_version"):
+                return fn
+
+            def call(*args):
+                calls.append((name, args))
+                return fn(*args)
+            return call
+    N.lib = lambda: Proxy()
+
+    def scalars(name, args):
+        types = N._SIGNATURES[name][1]
+        out = [name]
+        for t, a in zip(types, args):
+            if t in (C.c_int64, C.c_int32, C.c_size_t):
+                out.append(int(a))
+            elif t in (C.c_float, C.c_double):
+                out.append(float(a))
+        return out
+
+    def is_eval(name):
+        return name.startswith("stdadk_eval_")
+
+    def trace_plain():
+        m = model()
+        cfgt = {"lr": LR, "batch_size": BATCH, "grad_clip": 10.0}
+        eng = T.make_engine(m, cfgt, BATCH, n_batches)
+        del calls[:]
+        eng.run_epoch(data(ROWS, 1), BATCH, shuffle=False)
+        return [scalars(n, a) for n, a in calls]
+
+    def trace_driver(warmup):
+        """One epoch as train_model runs it (on_step rates, loss="batches", validation under EMA)."""
+        m = model()
+        cfgt = {"lr": LR, "batch_size": BATCH, "grad_clip": 10.0, "epochs": 1, "warmup_epochs": warmup,
+                "scheduler": "cosine", "val_batch_size": BATCH, "verbose": False}
+        eng = T.make_engine(m, cfgt, BATCH, n_batches)
+        lo, hi = eng.ema.data_ptr(), eng.ema.data_ptr() + eng.ema.numel() * 4
+        copies = []
+        clone, copy_ = torch.Tensor.clone, torch.Tensor.copy_
+        big = eng.flat.numel()
+
+        def counting_clone(t, *a, **kw):
+            if t.numel() >= big:
+                copies.append("clone")
+            return clone(t, *a, **kw)
+
+        def counting_copy(t, src, *a, **kw):
+            if t.numel() >= big:
+                copies.append("copy_")
+            return copy_(t, src, *a, **kw)
+        del calls[:]
+        torch.Tensor.clone, torch.Tensor.copy_ = counting_clone, counting_copy
+        try:
+            T.train_model(m, data(ROWS, 1), data(VAL_ROWS, 2), cfgt, shuffle=False, engine=eng)
+        finally:
+            torch.Tensor.clone, torch.Tensor.copy_ = clone, copy_
+        inside = []
+        for n, a in calls:
+            if n == "stdadk_eval_indexed_f32":
+                tab = a[2]._obj
+                ptrs = [p for arr in (tab.W, tab.b, tab.ln_g, tab.ln_b) for p in arr if p]
+                inside.append(all(lo <= p < hi for p in ptrs) and len(ptrs) > 0)
+        return {"train": [scalars(n, a) for n, a in calls if not is_eval(n)],
+                "eval": [scalars(n, a) for n, a in calls if is_eval(n)], "inside_ema": inside,
+                # one epoch, it is the best: ONE copy of the shadow into the best state, one load of it at the end
+                "flat_copies": copies, "ema_in_place": Evaluator.ema_in_place(eng)}
+    rec["trace_plain"] = trace_plain()
+    rec["trace_driver"] = {str(w): trace_driver(w) for w in (0, 1)}
+
+    # --- 3. argument errors of the new entry
+    m = model()
+    eng = TrainStep(m, max_batch=BATCH, ema_decay=0.99, seed=1)
+    ev = Evaluator(m, max_batch=BATCH)
+    va = data(VAL_ROWS, 2)
+    st = eng.state
+    desc = m._native_desc(False)
+    ws = torch.empty(N.eval_workspace_bytes(st.basis, desc, BATCH, st.flags) // 4)
+    acc = torch.zeros(N.EVAL_SLOTS, dtype=torch.float64)
+    idx = torch.arange(BATCH)
+
+    def attempt(**kw):
+        a = dict(basis=st.basis, desc=desc, params=st.params, coords_all=va.coords, t_all=va.t.view(-1), X_all=None,
+                 y_all=va.y, idx=idx, loss_desc=None, metric_col=0, batch_weight=1.0 / BATCH, acc=acc, y_pred=None,
+                 workspace=ws, flags=st.flags)
+        a.update(kw)
+        try:
+            N.eval_indexed(**a)
+            return "ok"
+        except RuntimeError as e:
+            return str(e)
+    rec["errors"] = {"ok": attempt(), "null_coords": attempt(coords_all=None), "null_y": attempt(y_all=None),
+                     "big_B": attempt(idx=torch.arange(4 * BATCH)), "metric_col": attempt(metric_col=1),
+                     "metric_neg": attempt(metric_col=-1), "small_ws": attempt(workspace=ws[:ws.numel() // 2])}
+    null_acc = real.stdadk_eval_indexed_f32(C.byref(st.basis), C.byref(desc), C.byref(st.params), va.coords.data_ptr(),
+                                            va.t.data_ptr(), None, va.y.data_ptr(), idx.data_ptr(), BATCH, None, 0,
+                                            1.0 / BATCH, None, None, ws.data_ptr(), ws.numel() * 4, st.flags, None)
+    rec["errors"]["null_acc"] = [null_acc, real.stdadk_last_error().decode()]
+    print("RECORD " + json.dumps(rec))
+
+
+@pytest.fixture(scope="module")
+def rec(tmp_path_factory):
+    tmp = str(tmp_path_factory.mktemp("training"))
+    env = dict(os.environ, STDADK_DRY_RUN="1")
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), tmp], env=env, capture_output=True, text=True,
+                         timeout=600)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    line = [l for l in out.stdout.splitlines() if l.startswith("RECORD ")][-1]
+    return json.loads(line[len("RECORD "):])
+
+
+@pytest.mark.parametrize("name", ["sched_fixed", "sched_learn", "sched_learn_now"])
+def test_learning_rates_equal_the_reference(rec, name):
+    """Every group's rate at every optimiser step and the history's lr column against what the reference's own
+    train_model used (recorded by tests/golden/make_training_golden.py): warm-up, unfreezing with its ramp, and the
+    cosine recursion acting on the manually written knot rates.  Host arithmetic: equal to 1e-12."""
+    import numpy as np
+    g = np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))
+    got = np.asarray(rec["sched"][name]["rates"], np.float64)
+    assert got.shape == g["rates"].shape, (got.shape, g["rates"].shape)
+    assert np.all(np.abs(got - g["rates"]) <= 1e-12 * np.abs(g["rates"])), np.argwhere(got != g["rates"])[:5]
+    lr = np.asarray(rec["sched"][name]["lr"], np.float64)
+    assert lr.shape == g["lr"].shape and np.all(np.abs(lr - g["lr"]) <= 1e-12 * np.abs(g["lr"]))
+
+
+def test_driver_settings(rec):
+    r = rec["fixed"]
+    nb = math.ceil(ROWS / BATCH)
+    assert r["ema_decay"] == pytest.approx(1.0 - 1.0 / (10.0 * nb), rel=1e-15)
+    assert r["wd"] == 1e-5                      # the code default of the reference driver, not the YAML's
+
+
+def test_best_patience_early_stop_and_files(rec):
+    r = rec["fixed"]
+    # scripted validation losses 0.9 0.5 nan 0.7 0.4 0.45 0.41 0.6, patience 3: best at epochs 1, 2, 5; the NaN never
+    # becomes best; epochs 6, 7, 8 do not improve -> early stop after the 8th
+    assert len(r["hist"]["val_loss"]) == 8
+    assert [c[2] for c in r["stub_calls"]] == ["ema"] * 8
+    assert all(c[0] == VAL_ROWS and c[1] == min(max(16 * BATCH, 32768), VAL_ROWS) for c in r["stub_calls"])
+    assert r["files"] == ["model_best.pt", "training_history.csv"]
+    assert r["csv"][0] == "epoch,train_loss,val_loss,val_rmse,lr" and len(r["csv"]) == 9
+    assert r["keys"] == r["model_keys"]
+    n = rec["nan"]
+    assert n["epochs"] == 2 and n["files"] == ["training_history.csv"] and n["best"]
+
+
+@pytest.mark.parametrize("warmup", ["0", "1"])
+def test_call_trace_of_a_validated_epoch(rec, warmup):
+    """One epoch as train_model runs it -- per-step rates, batch-mean loss, validation under EMA, best state -- makes
+    the library calls of a plain run_epoch, then one stdadk_eval_indexed_f32 per validation batch on views of the
+    shadow; the flat buffer is copied twice in all (shadow -> best state, best state -> model), never swapped."""
+    t = rec["trace_driver"][warmup]
+    assert t["train"] == rec["trace_plain"], "the driver's epoch differs from a plain run_epoch in its library calls"
+    evals = [c for c in t["eval"] if c[0] == "stdadk_eval_indexed_f32"]
+    sizes = [BATCH] * (VAL_ROWS // BATCH) + ([VAL_ROWS % BATCH] if VAL_ROWS % BATCH else [])
+    assert [c[1] for c in evals] == sizes                                  # one call per batch, last one ragged
+    assert [c[3] for c in evals] == pytest.approx([1.0 / b for b in sizes], rel=1e-15)      # 1 / (B Q), Q = 1
+    assert [c[0] for c in t["eval"]] == ["stdadk_eval_workspace_bytes"] + ["stdadk_eval_indexed_f32"] * len(sizes)
+    assert t["ema_in_place"] and all(t["inside_ema"]) and len(t["inside_ema"]) == len(sizes)
+    assert t["flat_copies"] == ["copy_", "copy_"], t["flat_copies"]
+
+
+def test_argument_errors(rec):
+    e = rec["errors"]
+    assert e["ok"] == "ok"
+    assert "NULL pointer" in e["null_coords"] and "NULL pointer" in e["null_y"]
+    assert "workspace" in e["big_B"] and "workspace" in e["small_ws"]
+    assert "metric_col" in e["metric_col"] and "metric_col" in e["metric_neg"]
+    assert e["null_acc"][0] == -1 and "NULL pointer" in e["null_acc"][1]
+
+
+if __name__ == "__main__":
+    _record(sys.argv[1])

@@ -1,6 +1,7 @@
 """End-to-end soak: KAUST-shaped synthetic field (S sites x T times, z = smooth field + N(0, 0.1^2) noise, 10 % held
-out), C2 model, the reference's optimiser settings with a cosine learning-rate schedule, `run_epoch` over a
-device-resident dataset for many epochs.  Prints train loss / held-out RMSE per few epochs and the rate.
+out), C2 model, the reference's optimiser settings with a cosine learning-rate schedule: `stnf.training.train_model`
+(run_epoch + validation under the EMA weights every epoch) over a device-resident dataset.  Prints the driver's line per
+epoch, the best held-out RMSE and the rate; then the shipped multi-quantile shape on plain run_epoch.
 usage (MI355X box): python tools/soak_training.py [epochs]"""
 import math, os, sys, time
 import numpy as np
@@ -8,9 +9,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "st-dadk_amd"))
 from stnf.models import STInterpMLP
-from stnf.engine import TrainStep, Predictor
+from stnf.engine import TrainStep
+from stnf.training import train_model, evaluate_model
 from stnf.dataio.device_dataset import DeviceDataset
-from stnf.utils import compute_metrics, set_seed
+from stnf.utils import set_seed
 
 epochs = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 set_seed(0)
@@ -28,29 +30,19 @@ clean = DeviceDataset.from_mask(field.astype(np.float32), coords, ~mask)
 d = torch.device("cuda:0")
 m = STInterpMLP(p=0, k_spatial_centers=[1024, 4096, 5184], k_temporal_centers=[10, 15, 45], hidden_dims=[256, 256, 128],
                 dropout=0.1, layernorm=True).to(d)
-m.train()
 B = 4096
 nb = math.ceil(len(ds) / B)
-eng = TrainStep(m, lr=2e-2, weight_decay=5e-4, grad_clip=10.0, ema_decay=1.0 - 1.0 / (10.0 * nb), max_batch=B)
+config = {"lr": 2e-2, "weight_decay": 5e-4, "grad_clip": 10.0, "batch_size": B, "epochs": epochs, "scheduler": "cosine",
+          "patience": epochs + 1}
 g = torch.Generator(device=d).manual_seed(0)
 t0 = time.perf_counter()
-for ep in range(epochs):
-    eng.set_lr(2e-2 * 0.5 * (1 + math.cos(math.pi * ep / epochs)))         # CosineAnnealingLR, as the driver
-    tr = eng.run_epoch(ds, B, generator=g)
-    if ep % 10 == 9 or ep == epochs - 1:
-        eng.swap_in_ema()
-        m.eval()
-        pred = Predictor(m).predict(dv.coords, dv.t)
-        m.train()
-        eng.swap_in_ema()
-        rmse_noisy = float(((pred - dv.y) ** 2).mean().sqrt())
-        rmse_clean = float(((pred - clean.y) ** 2).mean().sqrt())
-        assert math.isfinite(tr) and math.isfinite(rmse_noisy)
-        print(f"epoch {ep + 1:3d}  train MSE {tr:.5f}  held-out RMSE vs noisy {rmse_noisy:.4f} (noise floor 0.1000)  "
-              f"vs the noise-free field {rmse_clean:.4f}", flush=True)
+m, hist, _ = train_model(m, ds, dv, config, generator=g)          # validation under EMA after every epoch
 torch.cuda.synchronize()
 el = time.perf_counter() - t0
-print(f"{epochs} epochs x {nb} steps of {B} in {el:.2f} s incl. evaluation = {epochs * len(ds) / el / 1e6:.1f} M obs/s end to end")
+rmse_clean = evaluate_model(m, clean, config)["rmse"]               # the returned model holds the best EMA state
+assert all(math.isfinite(v) for v in hist["train_loss"] + hist["val_rmse"])
+print(f"best held-out RMSE vs noisy {min(hist['val_rmse']):.4f} (noise floor 0.1000)  vs the noise-free field {rmse_clean:.4f}")
+print(f"{epochs} epochs x {nb} steps of {B} in {el:.2f} s incl. validation every epoch = {epochs * len(ds) / el / 1e6:.1f} M obs/s end to end")
 
 
 # ---- the shipped configuration's shape: 227 GMM-initialised learnable knots, 5 quantiles, non-crossing penalty
