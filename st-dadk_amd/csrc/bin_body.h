@@ -154,4 +154,121 @@ __device__ __forceinline__ void bin_small_body(const BinSmallArgs &a, const int 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The same binning for a carrier whose workgroups are BIN_DW_T = 256 threads with a static LDS block: the merged
+// weight-gradient launch of a step (dw_all.hip), which runs three times as long as the binning needs and leaves HBM
+// mostly idle -- beside the optimiser's HBM stream every link of the binning's chain of dependent loads queues behind
+// that stream (adamw_bin_kernel: 25 us against 18.5 us for the optimiser alone).  Up to BIN_DW_B rows; same integers
+// and floats in the same places as bin_small_body.  What makes it fit 32 KiB: batch positions < 4 096 are 16-bit
+// entries of the two permutations; ONE array of the cells serves as counts, then cursors, and after the scatter a
+// cell's cursor is the next cell's start; the row numbers are not staged (in this launch the extra dependent load is
+// not behind an HBM stream).
+// ---------------------------------------------------------------------------------------------------------
+// BIN_DW_WG workgroups share the ordering and the emission (each builds the whole sort): 8 to 32 measure the same
+// step time within run-to-run noise (0.1054-0.1058 ms), 64 cost 1 us (STDADK_BIN_WG)
+constexpr int BIN_DW_T = 256, BIN_DW_B = 4096, BIN_DW_WG = 16;
+constexpr int BIN_DW_LDS_INTS = SMALL_G * SMALL_G + BIN_DW_B / 2 + BIN_DW_B / 2 + 8;     // 32 KiB + 32 B
+__host__ __device__ constexpr bool bin_dw_holds(int B, int G) { return B >= 1 && B <= BIN_DW_B && G <= SMALL_G; }
+
+// workgroup `block` of `nblocks` (256 threads); smem: BIN_DW_LDS_INTS ints
+__device__ __forceinline__ void bin_dw_body(const BinSmallArgs &a, const int block, const int nblocks, int *smem) {
+  typedef unsigned short u16;
+  int *hist = smem;                                                   // [SMALL_G^2] counts, cursors, then cell ends
+  u16 *ptmp = reinterpret_cast<u16 *>(hist + SMALL_G * SMALL_G);      // [BIN_DW_B] unordered permutation
+  u16 *pfin = ptmp + BIN_DW_B;                                        // [BIN_DW_B] ordered permutation
+  int *part = reinterpret_cast<int *>(pfin + BIN_DW_B);               // [8] wave totals of the scan
+  const int64_t *__restrict__ idx = a.idx;
+  const float *__restrict__ coords = a.coords, *__restrict__ t = a.t, *__restrict__ y = a.y, *__restrict__ X = a.X;
+  const int Q = a.Q, p = a.p, B = a.B, G = a.G;
+  int *__restrict__ keys = a.keys, *__restrict__ cell_start = a.cell_start, *__restrict__ perm = a.perm;
+  float *__restrict__ xs = a.xs, *__restrict__ ys = a.ys, *__restrict__ ts = a.ts, *__restrict__ y_s = a.y_s,
+        *__restrict__ X_s = a.X_s;
+  const int tid = threadIdx.x;
+  const int ncell = G * G;
+  constexpr int PER_T = BIN_DW_B / BIN_DW_T;   // observations per thread
+  // this workgroup's slice [lo, hi) of the batch positions (keys) and of the sorted positions (everything else)
+  const int per_wg = ((B + nblocks - 1) / nblocks + 63) & ~63;
+  const int lo = min(block * per_wg, B), hi = min(lo + per_wg, B);
+  for (int c = tid; c < ncell; c += BIN_DW_T) hist[c] = 0;
+  __syncthreads();
+  int kk[PER_T];
+#pragma unroll
+  for (int i = 0; i < PER_T; ++i) {
+    const int bc = min(tid + BIN_DW_T * i, B - 1);
+    const int64_t r = idx ? idx[bc] : bc;
+    kk[i] = bin_cell_of(coords[2 * r], coords[2 * r + 1], G);       // unconditional, clamped
+  }
+#pragma unroll
+  for (int i = 0; i < PER_T; ++i) {
+    const int b = tid + BIN_DW_T * i;
+    if (b < B) {
+      if (b >= lo && b < hi) keys[b] = kk[i];
+      atomicAdd(&hist[kk[i]], 1);
+    }
+  }
+  __syncthreads();
+  // exclusive scan: thread tid owns cells [tid*per, tid*per+per); wave-level shuffles, one barrier
+  const int per = (ncell + BIN_DW_T - 1) / BIN_DW_T;
+  const int i0 = min(tid * per, ncell), i1 = min(i0 + per, ncell);
+  int s = 0;
+  for (int i = i0; i < i1; ++i) s += hist[i];
+  const int lane = tid & 63, wv = tid >> 6;
+  int incl = s;                                  // inclusive scan inside the wave
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  if (lane == 63) part[wv] = incl;               // wave totals
+  __syncthreads();
+  int run = incl - s;
+  for (int w = 0; w < wv; ++w) run += part[w];
+  for (int i = i0; i < i1; ++i) {
+    const int cnt = hist[i];
+    if (block == 0) cell_start[i] = run;
+    hist[i] = run;            // cursor for the scatter
+    run += cnt;
+  }
+  if (tid == BIN_DW_T - 1 && block == 0) cell_start[ncell] = (part[0] + part[1]) + (part[2] + part[3]);
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < PER_T; ++i) {
+    const int b = tid + BIN_DW_T * i;
+    if (b < B) ptmp[atomicAdd(&hist[kk[i]], 1)] = (u16)b;
+  }
+  __syncthreads();
+  // hist[c] is now the END of cell c = the start of cell c + 1.  Order every cell that reaches into [lo, hi) by
+  // original index (rank by counting): LDS only
+  for (int c = tid; c < ncell; c += BIN_DW_T) {
+    const int s0 = c > 0 ? hist[c - 1] : 0, s1 = hist[c];
+    if (s1 <= lo || s0 >= hi) continue;
+    for (int i = s0; i < s1; ++i) {
+      const int b = ptmp[i];
+      int rank = 0;
+      for (int j = s0; j < s1; ++j) rank += ptmp[j] < b;
+      pfin[s0 + rank] = (u16)b;
+    }
+  }
+  __syncthreads();
+  // emit the sorted arrays: one position per thread and pass, independent loads
+#pragma unroll 1
+  for (int base = lo; base < hi; base += BIN_DW_T) {      // workgroup-uniform
+    const int pos = base + tid;
+    const int b = pfin[min(pos, hi - 1)];
+    const int64_t r = idx ? idx[b] : b;
+    const float cx = coords[2 * r], cy = coords[2 * r + 1];
+    const float tv = t ? t[r] : 0.f;
+    if (pos < hi) {
+      perm[pos] = b;
+      xs[pos] = cx;
+      ys[pos] = cy;
+      if (t) ts[pos] = tv;
+      if (y_s)
+        for (int q = 0; q < Q; ++q) y_s[(int64_t)pos * Q + q] = y[r * Q + q];
+      if (X_s)
+        for (int q = 0; q < p; ++q) X_s[(int64_t)pos * p + q] = X[r * p + q];
+    }
+  }
+}
+
 }  // namespace stdadk

@@ -6,25 +6,45 @@
 // running them one after the other, and one launch + drain is saved.
 #include <stdlib.h>
 
+#include "bin_body.h"
 #include "gemm_body.h"
 #include "l1_bwd_body.h"
 
 namespace stdadk {
 
 static_assert(GT == BW_T, "the GEMM tiles and the knot groups must share the workgroup shape");
+static_assert(GT == BIN_DW_T, "the binning workgroups of the NEXT batch share it too");
+// the launch's static LDS block: the staged GEMM tiles, or the binning image (8 KiB more; the kernels stay at the three
+// workgroups per CU that their registers allow -- 53 KiB of LDS each would still do)
+constexpr int DW_ALL_LDS_FLOATS = GROUP_LDS_FLOATS > BIN_DW_LDS_INTS ? GROUP_LDS_FLOATS : BIN_DW_LDS_INTS;
 
 // NK (fixed knots only): 2 neighbouring knots per wave, see l1_window_bwd_multi_body; 1: one knot per wave
 // fin.cnt != NULL (FinArgs, gemm_f32.h): the launch also does what the reductions launch behind it did -- block
-// order [GEMM tiles | tall reduce jobs | padding | knot groups]
+// order [binning | GEMM tiles | tall reduce jobs | padding | knot groups]
+// n_bin > 0: the launch also bins the NEXT batch of the training loop (bin_body.h: bin_dw_body) with n_bin independent
+// workgroups that nobody in this launch waits for.  They take the LOWEST block ids: each is one latency chain of
+// dependent loads (~10 us) with hardly any bandwidth, so it has to start with the launch to end inside it -- behind
+// the GEMM tiles (bin_front == 0, measurement aid STDADK_BIN_POS=mid) the binning workgroups get their CU slots only
+// when the first tiles retire and the launch grows by what the optimiser launch saved (27.3 -> 33.1 us; in front
+// see DESIGN.md section 6).  The tiles, the tall jobs and the knot groups keep their order and their squared-norm slots.
 template <int CPL, int BASIS, bool KNOTS, int NK>
 __global__ __launch_bounds__(GT) void dw_all_kernel(GemmGroup grp, int n_gemm_blocks, L1BwdArgs a, FinArgs fin,
-                                                    ReduceGroup tall) {
-  __shared__ __attribute__((aligned(16))) float lds[GROUP_LDS_FLOATS];
+                                                    ReduceGroup tall, BinSmallArgs bin, int n_bin, int bin_front) {
+  __shared__ __attribute__((aligned(16))) float lds[DW_ALL_LDS_FLOATS];
+  int blk = (int)blockIdx.x;
+  // (the binning in front is padded to a multiple of 8 blocks: (block & 7), the XCD, stays what the tiles and the knot
+  //  groups were laid out for)
+  const int lead = bin_front ? (n_bin + 7) & ~7 : 0;          // blockIdx.x = blk + lead
+  if (lead) {
+    if (blk < n_bin) { bin_dw_body(bin, blk, n_bin, reinterpret_cast<int *>(lds)); return; }
+    if (blk < lead) return;
+    blk -= lead;
+  }
   // GEMM tiles take the low block ids (dispatched first): measured 33.5 us vs 42.5 us the other way round
-  if ((int)blockIdx.x < n_gemm_blocks) { gemm_tn_grouped_block(grp, (int)blockIdx.x, lds, &fin); return; }
+  if (blk < n_gemm_blocks) { gemm_tn_grouped_block(grp, blk, lds, &fin); return; }
   const int n_front = n_gemm_blocks + fin.n_tall;
-  if ((int)blockIdx.x < n_front) {
-    const int tb = (int)blockIdx.x - n_gemm_blocks;
+  if (blk < n_front) {
+    const int tb = blk - n_gemm_blocks;
     if (tb == 0 && threadIdx.x == 0 && fin.step_inc) fin.step_inc[0] += 1;
     const float sq = reduce_job_block(tall, tb, lds);
     if (fin.slots) {
@@ -33,20 +53,22 @@ __global__ __launch_bounds__(GT) void dw_all_kernel(GemmGroup grp, int n_gemm_bl
     }
     return;
   }
+  const int n_mid = bin_front ? 0 : n_bin;
+  if (blk < n_front + n_mid) { bin_dw_body(bin, blk - n_front, n_bin, reinterpret_cast<int *>(lds)); return; }
   // XCD-striped knot groups start at a multiple of 8, so that (group block & 7) is the XCD of the workgroup
-  const int first = a.xcd_slots > 0 ? (n_front + 7) & ~7 : n_front;
-  if ((int)blockIdx.x < first) return;
+  const int first = a.xcd_slots > 0 ? (n_front + n_mid + 7) & ~7 : n_front + n_mid;
+  if (blk < first) return;
   float sq;
-  if constexpr (NK > 1) sq = l1_window_bwd_multi_body<CPL, BASIS, NK>(a, (int)blockIdx.x - first);
-  else sq = l1_window_bwd_body<CPL, BASIS, KNOTS>(a, (int)blockIdx.x - first);
+  if constexpr (NK > 1) sq = l1_window_bwd_multi_body<CPL, BASIS, NK>(a, blk - first);
+  else sq = l1_window_bwd_body<CPL, BASIS, KNOTS>(a, blk - first);
   if (fin.slots) {                 // workgroup-uniform; every wave of the workgroup arrives (no wave exits early)
     const float t = block4_sum(sq, lds);
-    if (threadIdx.x == 0) fin.slots[fin.n_tiles + fin.n_tall + ((int)blockIdx.x - first)] = t;
+    if (threadIdx.x == 0) fin.slots[fin.n_tiles + fin.n_tall + (blk - first)] = t;
   }
 }
 
 // kernel arguments travel in the 4 KiB kernarg segment
-static_assert(sizeof(GemmGroup) + sizeof(L1BwdArgs) + sizeof(FinArgs) + sizeof(ReduceGroup) + 16 <= 4096,
+static_assert(sizeof(GemmGroup) + sizeof(L1BwdArgs) + sizeof(FinArgs) + sizeof(ReduceGroup) + sizeof(BinSmallArgs) + 32 <= 4096,
               "dw_all: kernel arguments exceed the kernarg segment");
 
 int dw_all_knot_blocks(const L1BwdArgs &a_in) {
@@ -56,8 +78,10 @@ int dw_all_knot_blocks(const L1BwdArgs &a_in) {
   return slots > 0 ? 8 * slots : (int)ceil_div(knot_group_count(a.g, nk), BW_T / 64);
 }
 
+bool dw_all_bins(int B, int G) { return bin_dw_holds(B, G); }
+
 int launch_dw_all(GemmGroup &grp, const L1BwdArgs &a_in, int basis, hipStream_t st, const FinArgs *fin_in,
-                  ReduceGroup *tall_in, int *n_slots) {
+                  ReduceGroup *tall_in, int *n_slots, const BinSmallArgs *bin_in) {
   L1BwdArgs a = a_in;
   STDADK_REQUIRE(a.G <= 256, STDADK_E_ARG, "dw_all: G too large");
   STDADK_REQUIRE((int64_t)a.B * a.H < (1ll << 32), STDADK_E_ARG, "dw_all: B*H exceeds 32-bit offsets");
@@ -89,16 +113,30 @@ int launch_dw_all(GemmGroup &grp, const L1BwdArgs &a_in, int basis, hipStream_t 
     fin.slots = fin_in->slots;
     if (n_slots) *n_slots = (int)n_knot;
   }
-  const unsigned front = (unsigned)ng + (unsigned)fin.n_tall;
-  const unsigned grid = (a.xcd_slots > 0 ? ((front + 7u) & ~7u) : front) + n_knot;
+  BinSmallArgs bin{};
+  int n_bin = 0, bin_front = 0;
+  if (bin_in) {
+    STDADK_REQUIRE(bin_dw_holds(bin_in->B, bin_in->G), STDADK_E_ARG,
+                   "dw_all: a next batch of %d rows on a grid of %d cells a side does not fit the launch's binning", bin_in->B,
+                   bin_in->G);
+    bin = *bin_in;
+    // (a few hundred rows are not worth splitting: one workgroup)
+    n_bin = bin.B >= 1024 ? BIN_DW_WG : 1;
+    { const char *e = getenv("STDADK_BIN_WG"); if (e && atoi(e) > 0 && atoi(e) <= 256 && bin.B >= 1024) n_bin = atoi(e); }   // measurement aid
+    { const char *e = getenv("STDADK_BIN_POS"); bin_front = (e && e[0] == 'm') ? 0 : 1; }                                     // measurement aid
+  }
+  // the blocks in front of the knot groups; the knot groups themselves start at a multiple of 8 wherever the binning is
+  const unsigned lead = bin_front ? ((unsigned)n_bin + 7u) & ~7u : 0u;
+  const unsigned front = (unsigned)ng + (unsigned)fin.n_tall + (bin_front ? 0u : (unsigned)n_bin);
+  const unsigned grid = lead + (a.xcd_slots > 0 ? ((front + 7u) & ~7u) : front) + n_knot;
 #define GO(CPL_, BS_)                                                                                      \
   do {                                                                                                     \
     if (a.kpart) STDADK_LAUNCH_NAMED("dw_all_kernel<knots>", (dw_all_kernel<CPL_, BS_, true, 1>),          \
-                                     dim3(grid), dim3(GT), 0, st, grp, ng, a, fin, tall);                  \
+                                     dim3(grid), dim3(GT), 0, st, grp, ng, a, fin, tall, bin, n_bin, bin_front); \
     else if (nk == 2) STDADK_LAUNCH_NAMED("dw_all_kernel", (dw_all_kernel<CPL_, BS_, false, 2>), dim3(grid), \
-                                          dim3(GT), 0, st, grp, ng, a, fin, tall);                         \
+                                          dim3(GT), 0, st, grp, ng, a, fin, tall, bin, n_bin, bin_front);  \
     else STDADK_LAUNCH_NAMED("dw_all_kernel", (dw_all_kernel<CPL_, BS_, false, 1>), dim3(grid),            \
-                             dim3(GT), 0, st, grp, ng, a, fin, tall);                                      \
+                             dim3(GT), 0, st, grp, ng, a, fin, tall, bin, n_bin, bin_front);               \
   } while (0)
   if (a.H == 256) { if (basis == STDADK_BASIS_WENDLAND) GO(4, 0); else GO(4, 2); }
   else if (a.H == 128) { if (basis == STDADK_BASIS_WENDLAND) GO(2, 0); else GO(2, 2); }

@@ -530,6 +530,9 @@ struct Ctx {
                                 // 1: which leaves the squared-norm slots of its knot rows, reductions launch behind it
   GemmGroup gg_pend;
   ReduceGroup rg_pend;
+  // one-call step that announces its NEXT batch: the merged dW launch bins it when it is what the step runs
+  const BinSmallArgs *bin_next = nullptr;
+  bool bin_next_done = false;
   bool l1_pend_valid = false;   // window path, B <= 4096: the layer-0 launch is parked as well
   L1FwdArgs l1_pend;
   int l1_basis = 0;
@@ -1238,9 +1241,15 @@ static int window_dw0(Ctx &c, hipStream_t st, GemmGroup *with_products = nullptr
     }
     STDADK_REQUIRE(need <= slot_cap, STDADK_E_WORKSPACE, "dw_all: %d squared-norm slots, the plan holds %d", need,
                    slot_cap);
-    return launch_dw_all(*with_products, a, b->basis, st, fin, tall, n_slots);
+    const int rc = launch_dw_all(*with_products, a, b->basis, st, fin, tall, n_slots, c.bin_next);
+    if (rc == 0 && c.bin_next) c.bin_next_done = true;
+    return rc;
   }
-  if (with_products) return launch_dw_all(*with_products, a, b->basis, st);
+  if (with_products) {
+    const int rc = launch_dw_all(*with_products, a, b->basis, st, nullptr, nullptr, nullptr, c.bin_next);
+    if (rc == 0 && c.bin_next) c.bin_next_done = true;
+    return rc;
+  }
   return l1_window_backward(a, b->basis, st);
 }
 
@@ -1592,14 +1601,20 @@ static int train_fwd_bwd_impl(const stdadk_basis_desc *b, const stdadk_mlp_desc 
                               uint64_t drop_seed, const int32_t *step_dev, int32_t flags,
                               stdadk_stream_t stream, stdadk_stream_t aux_stream,
                               float *gradsq_parts = nullptr, int32_t *step_inc = nullptr,
-                              const float **gradsq_out = nullptr, int *gradsq_n = nullptr) {
+                              const float **gradsq_out = nullptr, int *gradsq_n = nullptr,
+                              const BinSmallArgs *bin_next = nullptr, bool *bin_next_done = nullptr) {
+  if (bin_next_done) *bin_next_done = false;
   if (B == 0) return 0;
   Ctx c;
   c.gradsq = gradsq_parts; c.step_inc = step_inc;
+  c.bin_next = bin_next;
   struct Done {
-    Ctx &c; const float **out; int *n;
-    ~Done() { if (out) { *out = c.gradsq_done ? c.gradsq_out : nullptr; *n = c.gradsq_done ? c.gradsq_n : 0; } }
-  } done_guard{c, gradsq_out, gradsq_n};
+    Ctx &c; const float **out; int *n; bool *bin;
+    ~Done() {
+      if (out) { *out = c.gradsq_done ? c.gradsq_out : nullptr; *n = c.gradsq_done ? c.gradsq_n : 0; }
+      if (bin) *bin = c.bin_next_done;
+    }
+  } done_guard{c, gradsq_out, gradsq_n, bin_next_done};
   bool window;
   int rc = step_common(c, b, d, B, workspace, workspace_bytes, flags, &window);
   if (rc) return rc;
@@ -1676,6 +1691,22 @@ static int train_step_impl(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
     STDADK_REQUIRE(!bin_next || (next_y_cols >= 0 && next_y_cols <= d->out_dim && (next_y_cols == 0 || y)),
                    STDADK_E_ARG, "train_step: next_y_cols=%d must be in 0..Q with y given", next_y_cols);
   }
+  // its carrier: the merged weight-gradient launch of this step (dw_all.hip), which has the time and the idle HBM for
+  // the binning's chain of dependent loads, whenever that launch is what the step runs and can hold the batch;
+  // otherwise, or with STDADK_BIN_IN=adam (diagnostic), the optimiser launch (optim.hip: adamw_bin_kernel).  The
+  // weight-gradient launch still reads this step's workspace, so there the next batch must go to another one.
+  BinSmallArgs ba{};
+  bool bin_in_dw = false;
+  if (bin_next) {
+    const BinBuffers bb = plan_bins(cn.ws, cn.pl);
+    ba = bin_small_args(coords, t, next_y_cols > 0 ? y : nullptr, next_y_cols, X, b->p, (int)next_B, cn.pl.G, bb, next_idx);
+    const char *ws0 = (const char *)workspace, *ws1 = (const char *)next_workspace;
+    const bool apart = ws1 + next_workspace_bytes <= ws0 || ws0 + workspace_bytes <= ws1;
+    const char *e = getenv("STDADK_BIN_IN");
+    const bool in_adam = e && e[0] == 'a';
+    bin_in_dw = !in_adam && apart && dw_all_bins((int)next_B, cn.pl.G);
+  }
+  bool binned_in_dw = false;
   const bool clip = o->max_norm > 0.f;
   const bool sparse = sparsity && sparsity->kind != STDADK_SPARSITY_NONE;
   const float *sq_parts = nullptr;   // where the step's own launches left the squared-norm partials, if they did
@@ -1684,7 +1715,10 @@ static int train_step_impl(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
   const bool fuse_sq = clip && !sparse;
   int rc = train_fwd_bwd_impl(b, d, P, G, coords, t, X, y, idx, B, grad_scale, loss, loss_sum, nullptr, workspace,
                               workspace_bytes, drop_seed, o->step_dev, flags, stream, nullptr,
-                              fuse_sq ? o->sumsq_parts : nullptr, fuse_sq ? o->step_dev : nullptr, &sq_parts, &sq_n);
+                              fuse_sq ? o->sumsq_parts : nullptr, fuse_sq ? o->step_dev : nullptr, &sq_parts, &sq_n,
+                              bin_in_dw ? &ba : nullptr, &binned_in_dw);
+  // (a failure behind the weight-gradient launch: the next batch may be binned, but the caller is not told so and
+  //  bins it again)
   if (rc) return rc;
   if (sparse) {
     const bool w0_t = (flags & STDADK_FLAG_W0_T) != 0;
@@ -1705,12 +1739,9 @@ static int train_step_impl(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
     rc = stdadk_step_advance(o->step_dev, stream);
     if (rc) return rc;
   }
-  if (bin_next) {
+  if (bin_next && !binned_in_dw) {
     // the NEXT batch's binning inside this step's optimiser launch (optim.hip: adamw_bin_kernel), when it is the
     // one-launch binning of small batches; the caller then steps on `next_workspace` with STDADK_FLAG_PREBINNED
-    const BinBuffers bb = plan_bins(cn.ws, cn.pl);
-    const BinSmallArgs ba = bin_small_args(coords, t, next_y_cols > 0 ? y : nullptr, next_y_cols, X, b->p, (int)next_B,
-                                           cn.pl.G, bb, next_idx);
     rc = adamw_ema_with_binning(o->p, o->g, o->m, o->v, o->ema, o->n, o->lr, o->lr_dev, o->beta1, o->beta2, o->eps,
                                 o->weight_decay, o->step_dev, o->max_norm, clip ? parts : nullptr, n_parts,
                                 o->ema_decay, o->shadow, o->nonfinite_step ? loss_sum : nullptr, o->nonfinite_step,
@@ -1718,10 +1749,12 @@ static int train_step_impl(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
     if (rc == 0) *next_binned = 1;
     return rc;
   }
-  return stdadk_adamw_ema_f32(o->p, o->g, o->m, o->v, o->ema, o->n, o->lr, o->lr_dev, o->beta1, o->beta2, o->eps,
-                              o->weight_decay, 1, o->step_dev, o->max_norm, clip ? parts : nullptr, n_parts,
-                              1.0f, o->ema_decay, o->shadow, o->nonfinite_step ? loss_sum : nullptr, o->nonfinite_step,
-                              stream);
+  rc = stdadk_adamw_ema_f32(o->p, o->g, o->m, o->v, o->ema, o->n, o->lr, o->lr_dev, o->beta1, o->beta2, o->eps,
+                            o->weight_decay, 1, o->step_dev, o->max_norm, clip ? parts : nullptr, n_parts,
+                            1.0f, o->ema_decay, o->shadow, o->nonfinite_step ? loss_sum : nullptr, o->nonfinite_step,
+                            stream);
+  if (rc == 0 && binned_in_dw) *next_binned = 1;
+  return rc;
 }
 
 extern "C" int stdadk_train_step_f32(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,

@@ -128,8 +128,11 @@ namespace stdadk {
 // the grouped dW products of the other layers and this per-knot gather as ONE launch (dw_all.hip)
 // fin (optional, fin->cnt != NULL): the launch also finishes the products (FinArgs: last-arriving K slice sums its
 // tile), runs the tall reduce jobs of `tall` and leaves squared-norm slots; *n_slots = how many slots it writes
+// bin (optional): the launch also bins the NEXT batch of the training loop (bin_body.h: bin_dw_body), which must
+// satisfy dw_all_bins(bin->B, bin->G) and write to another workspace than the one this launch reads
 int launch_dw_all(GemmGroup &grp, const L1BwdArgs &a, int basis, hipStream_t st, const FinArgs *fin = nullptr,
-                  ReduceGroup *tall = nullptr, int *n_slots = nullptr);
+                  ReduceGroup *tall = nullptr, int *n_slots = nullptr, const BinSmallArgs *bin = nullptr);
+bool dw_all_bins(int B, int G);                  // a batch the binning workgroups of the launch can hold
 int dw_all_knot_blocks(const L1BwdArgs &a);      // knot workgroups of the launch (for sizing the slots)
 
 // out[perm[i]*Q + q] = in[i*Q + q]

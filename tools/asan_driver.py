@@ -65,6 +65,18 @@ for ks, B in (([25, 81, 121], 300), ([1024], 4096), ([1024, 4096, 5184], 4096), 
               ([1024, 4096, 16384, 28224], 16384)):
     steps(model(ks), B)
 steps(model([1024, 4096, 5184]), 4096, dict(dtype="bf16"))
+# the step that announces its next batch, with the binning in the weight-gradient launch (default) and in the optimiser
+# launch (STDADK_BIN_IN=adam, read on every call): next batches on both sides of what the carriers hold
+eng = TrainStep(model([1024, 4096, 5184]).train(), max_batch=6000, ema_decay=0.99)
+_, c, t, y = data(6000)
+for carrier in ("dw", "adam"):
+    os.environ["STDADK_BIN_IN"] = carrier
+    for nB in (1, 63, 1500, 4096, 6000):
+        took = eng._enqueue(None, c, t.view(-1), y, 4096, 4096, idx=torch.arange(4095, -1, -1), ws=eng.ws,
+                            nxt=(torch.arange(nB), torch.empty_like(eng.ws)))
+        assert took == (nB <= 4096), (carrier, nB, took)
+        calls += 1
+del os.environ["STDADK_BIN_IN"]
 steps(model([1024, 4096, 5184]), 20000, dict(dtype="bf16"))
 steps(model([1024, 4096, 5184]), 4096, dict(force_dense=True))
 steps(model([25, 81, 121], layernorm=False, dropout=0.0), 777)
