@@ -107,6 +107,9 @@ int tail_krot();
 // rows per workgroup the launches will use for a batch of B rows (`cap32`: bf16 operands together with the dense
 // layer 0 inside the launch keep three activation images in LDS, which fit for at most 32 rows)
 int tail_rows(int64_t B, bool cap32 = false);
+// STDADK_FLAG_BF16 (`bf16` != 0): layers first .. n - 1 must carry their 16-byte aligned bf16 weight copies, Wbf for
+// the forward (`fwd`) and WTbf for the backward; 0 or an error code (set_error)
+int tail_check_bf16(int bf16, int n, const TailLayer *L, bool fwd, int first);
 int tail_forward(const TailFwdArgs &a, hipStream_t st);
 int tail_backward(const TailBwdArgs &a, hipStream_t st, bool cap32 = false);
 // training: forward (with the loss) and backward of every row tile in one launch

@@ -11,23 +11,21 @@
 
 namespace stdadk {
 
-// NW: waves per workgroup (tail_body.h): 16 = one 1024-thread workgroup per CU, the only shape the library
-// instantiates; 8 = 512 threads, at most 128 registers and (32-row tiles) 76 KiB of LDS, so that two workgroups share
-// a CU (see TAIL_DISPATCH below).
+// One 1024-thread workgroup per CU (tail_body.h).
 // D0: the launch starts from the raw observations (TailDense0 in tail.h); BF: bf16 operands (STDADK_FLAG_BF16)
-#define TAIL_BOUNDS(NW) __launch_bounds__(64 * NW, NW == 8 ? 4 : 1)
+#define TAIL_BOUNDS __launch_bounds__(TAIL_THREADS, 1)
 
-template <int NW, int MT, bool D0, bool BF>
-__global__ TAIL_BOUNDS(NW) void tail_fwd_kernel(TailFwdArgs a) {
+template <int MT, bool D0, bool BF>
+__global__ TAIL_BOUNDS void tail_fwd_kernel(TailFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ float red[NW];
-  Tail<NW>::template tail_fwd_body<MT, D0, BF>(a, smem, red, blockIdx.x);
+  __shared__ float red[TAIL_WAVES];
+  tail_fwd_body<MT, D0, BF>(a, smem, red, blockIdx.x);
 }
 
-template <int NW, int MT, bool BF>
-__global__ TAIL_BOUNDS(NW) void tail_bwd_kernel(TailBwdArgs a) {
+template <int MT, bool BF>
+__global__ TAIL_BOUNDS void tail_bwd_kernel(TailBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  Tail<NW>::template tail_bwd_body<MT, BF>(a, smem, blockIdx.x);
+  tail_bwd_body<MT, BF>(a, smem, blockIdx.x);
 }
 
 // Training step: the forward chain, the loss and the backward chain of a row tile are all row-local, so
@@ -35,13 +33,13 @@ __global__ TAIL_BOUNDS(NW) void tail_bwd_kernel(TailBwdArgs a) {
 // what the forward just wrote in L2).  The forward's global stores (xhat, act, rstd, dY) are complete
 // and visible to the whole workgroup after the __syncthreads() (vmcnt(0) + barrier); none of those lines
 // was read by this CU earlier in the launch, so no stale copy can sit in its L1.
-template <int NW, int MT, bool D0, bool BF>
-__global__ TAIL_BOUNDS(NW) void tail_fwd_bwd_kernel(TailFwdArgs f, TailBwdArgs b) {
+template <int MT, bool D0, bool BF>
+__global__ TAIL_BOUNDS void tail_fwd_bwd_kernel(TailFwdArgs f, TailBwdArgs b) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ float red[NW];
-  Tail<NW>::template tail_fwd_body<MT, D0, BF>(f, smem, red, blockIdx.x);
+  __shared__ float red[TAIL_WAVES];
+  tail_fwd_body<MT, D0, BF>(f, smem, red, blockIdx.x);
   __syncthreads();
-  Tail<NW>::template tail_bwd_body<MT, BF>(b, smem, blockIdx.x);
+  tail_bwd_body<MT, BF>(b, smem, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -53,18 +51,8 @@ bool tail_supported(const stdadk_mlp_desc *d, int first_layer) {
   return true;
 }
 
-// bf16 operands: one fp32 tile + the bf16 image (with the dense layer 0: the fp32 pair + the image)
-static size_t fwd_lds(int R, bool d0, bool bf) {
-  if (!bf) return (size_t)(2 * R * ACT_LD) * sizeof(float);
-  return (size_t)((d0 ? 2 : 1) * R * ACT_LD) * sizeof(float) + (size_t)R * ABF_LD * sizeof(u16);
-}
-template <int NW>
-static size_t bwd_lds(int R, bool bf) {
-  using T = Tail<NW>;
-  if (bf) return (R == 64 ? T::template tail_bwd_lds_floats<4, true>() : (R == 32 ? T::template tail_bwd_lds_floats<2, true>() : T::template tail_bwd_lds_floats<1, true>())) * sizeof(float);
-  return (R == 64 ? T::template tail_bwd_lds_floats<4, false>() : (R == 32 ? T::template tail_bwd_lds_floats<2, false>() : T::template tail_bwd_lds_floats<1, false>())) * sizeof(float);
-}
-static_assert(Tail<16>::tail_bwd_lds_floats<4, true>() * sizeof(float) <= 160 * 1024, "bf16 backward tile does not fit the LDS");
+static_assert(tail_bwd_lds(64, true) <= 160 * 1024, "bf16 backward tile does not fit the LDS");
+
 int tail_rows(int64_t B, bool cap32) {
   // two or four 16-row tiles per workgroup (shared weight fragments) once that still gives every CU
   // a workgroup; one tile per workgroup for small batches
@@ -75,7 +63,7 @@ int tail_rows(int64_t B, bool cap32) {
   return ceil_div(B, 32) >= 256 ? 32 : 16;
 }
 
-static int check_bf(int bf16, int n, const TailLayer *L, bool fwd, int first) {
+int tail_check_bf16(int bf16, int n, const TailLayer *L, bool fwd, int first) {
   if (!bf16) return 0;
   for (int i = first; i < n; ++i)
     STDADK_REQUIRE((fwd ? L[i].Wbf : L[i].WTbf) != nullptr && (reinterpret_cast<uintptr_t>(fwd ? L[i].Wbf : L[i].WTbf) & 15) == 0,
@@ -101,38 +89,32 @@ static int check_d0(const TailFwdArgs &a) {
   return 0;
 }
 
-template <int NW, int MT, bool D0, bool BF>
+template <int MT, bool D0, bool BF>
 static int launch_fwd(const TailFwdArgs &a, hipStream_t st) {
-  constexpr int R = 16 * MT, TT = 64 * NW;
+  constexpr int R = 16 * MT;
   static bool attr_done = false;
   if (!attr_done) {   // once per process, never inside a stream capture (the first step runs eagerly)
-    hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void *>(tail_fwd_kernel<NW, MT, D0, BF>), (int)fwd_lds(R, D0, BF));
+    hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void *>(tail_fwd_kernel<MT, D0, BF>), (int)tail_fwd_lds(R, D0, BF));
     if (e != hipSuccess) { set_error("tail_forward: LDS attribute: %s", hipGetErrorString(e)); return (int)e; }
     attr_done = true;
   }
   STDADK_LAUNCH_NAMED(D0 ? (BF ? "tail_fwd_kernel<dense0,bf16>" : "tail_fwd_kernel<dense0>") : (BF ? "tail_fwd_kernel<bf16>" : "tail_fwd_kernel"),
-                      (tail_fwd_kernel<NW, MT, D0, BF>), dim3((unsigned)ceil_div(a.B, R)), dim3(TT), fwd_lds(R, D0, BF), st, a);
+                      (tail_fwd_kernel<MT, D0, BF>), dim3((unsigned)ceil_div(a.B, R)), dim3(TAIL_THREADS), tail_fwd_lds(R, D0, BF), st, a);
   STDADK_CHECK_LAUNCH("tail_forward");
   return 0;
 }
 
 // dispatch on (rows, dense layer 0, bf16 operands); the bf16 + dense-0 combination is built for <= 32 rows.
-// All launches use Tail<16> (1024 threads, one workgroup per CU): Tail<8> -- 512 threads, 32-row tiles, TWO
-// workgroups per CU (confirmed by tools/diag/occupancy_tail8.hip), meant to overlap one tile's row-local phases with
-// the other's GEMM phases -- measured 0-4 % SLOWER at 16 384 and 65 536 rows, fp32 and bf16 (round 2), and again in
-// round 3 with the second workgroup of a CU started 3 .. 40 us late so that the two cannot run in lockstep: 451 us
-// (no delay) / 452 / 457 / 457 / 461 / 470 us against 448 us for one 1024-thread workgroup at 65 536 rows
-// (profiles/r03_tail_stagger_negative.txt).  The fp32 matrix instructions run at the fp32 VECTOR rate: a GEMM phase
-// and a row-local phase compete for the same issue, so there is nothing to overlap -- what pays is fewer vector
-// instructions in the row-local phases.  Tail<8> is not instantiated in the library.
-#define TAIL_DISPATCH(FN, r, d0, bf, ...)                                                                    \
-  ((bf) ? ((d0) ? ((r) == 32 ? FN<16, 2, true, true>(__VA_ARGS__) : FN<16, 1, true, true>(__VA_ARGS__))      \
-                : ((r) == 64 ? FN<16, 4, false, true>(__VA_ARGS__)                                           \
-                             : ((r) == 32 ? FN<16, 2, false, true>(__VA_ARGS__) : FN<16, 1, false, true>(__VA_ARGS__)))) \
-        : ((d0) ? ((r) == 64 ? FN<16, 4, true, false>(__VA_ARGS__)                                           \
-                             : ((r) == 32 ? FN<16, 2, true, false>(__VA_ARGS__) : FN<16, 1, true, false>(__VA_ARGS__))) \
-                : ((r) == 64 ? FN<16, 4, false, false>(__VA_ARGS__)                                          \
-                             : ((r) == 32 ? FN<16, 2, false, false>(__VA_ARGS__) : FN<16, 1, false, false>(__VA_ARGS__)))))
+// A 512-thread shape with two workgroups per CU measured 0-4 % slower, also with the second workgroup started late:
+// DESIGN.md section 8, profiles/r02_tail_two_workgroups_per_cu.txt, profiles/r03_tail_stagger_negative.txt.
+#define TAIL_DISPATCH(FN, r, d0, bf, ...)                                                                \
+  ((bf) ? ((d0) ? ((r) == 32 ? FN<2, true, true>(__VA_ARGS__) : FN<1, true, true>(__VA_ARGS__))          \
+                : ((r) == 64 ? FN<4, false, true>(__VA_ARGS__)                                           \
+                             : ((r) == 32 ? FN<2, false, true>(__VA_ARGS__) : FN<1, false, true>(__VA_ARGS__)))) \
+        : ((d0) ? ((r) == 64 ? FN<4, true, false>(__VA_ARGS__)                                           \
+                             : ((r) == 32 ? FN<2, true, false>(__VA_ARGS__) : FN<1, true, false>(__VA_ARGS__))) \
+                : ((r) == 64 ? FN<4, false, false>(__VA_ARGS__)                                          \
+                             : ((r) == 32 ? FN<2, false, false>(__VA_ARGS__) : FN<1, false, false>(__VA_ARGS__)))))
 
 int tail_krot() {
   static const int on = [] { const char *e = getenv("STDADK_KROT"); return (e && e[0] == '1') ? 1 : 0; }();
@@ -145,38 +127,38 @@ int tail_forward(const TailFwdArgs &a_in, hipStream_t st) {
   const bool d0 = a.d0.on != 0, bf = a.bf16 != 0;
   const int r = tail_rows(a.B, bf && d0);
   if (int rc = check_d0(a)) return rc;
-  if (int rc = check_bf(a.bf16, a.n_layers, a.L, true, 0)) return rc;
+  if (int rc = tail_check_bf16(a.bf16, a.n_layers, a.L, true, 0)) return rc;
   return TAIL_DISPATCH(launch_fwd, r, d0, bf, a, st);
 }
 
-template <int NW, int MT, bool BF>
+template <int MT, bool BF>
 static int launch_bwd(const TailBwdArgs &a, hipStream_t st) {
-  constexpr int R = 16 * MT, TT = 64 * NW;
+  constexpr int R = 16 * MT;
   static bool attr_done = false;
   if (!attr_done) {
-    hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void *>(tail_bwd_kernel<NW, MT, BF>), (int)bwd_lds<NW>(R, BF));
+    hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void *>(tail_bwd_kernel<MT, BF>), (int)tail_bwd_lds(R, BF));
     if (e != hipSuccess) { set_error("tail_backward: LDS attribute: %s", hipGetErrorString(e)); return (int)e; }
     attr_done = true;
   }
-  STDADK_LAUNCH_NAMED(BF ? "tail_bwd_kernel<bf16>" : "tail_bwd_kernel", (tail_bwd_kernel<NW, MT, BF>),
-                      dim3((unsigned)ceil_div(a.B, R)), dim3(TT), bwd_lds<NW>(R, BF), st, a);
+  STDADK_LAUNCH_NAMED(BF ? "tail_bwd_kernel<bf16>" : "tail_bwd_kernel", (tail_bwd_kernel<MT, BF>),
+                      dim3((unsigned)ceil_div(a.B, R)), dim3(TAIL_THREADS), tail_bwd_lds(R, BF), st, a);
   STDADK_CHECK_LAUNCH("tail_backward");
   return 0;
 }
 
-template <int NW, int MT, bool D0, bool BF>
+template <int MT, bool D0, bool BF>
 static int launch_fwd_bwd(const TailFwdArgs &f, const TailBwdArgs &b, hipStream_t st) {
-  constexpr int R = 16 * MT, TT = 64 * NW;
-  const size_t lds = fwd_lds(R, D0, BF) > bwd_lds<NW>(R, BF) ? fwd_lds(R, D0, BF) : bwd_lds<NW>(R, BF);
+  constexpr int R = 16 * MT;
+  const size_t lds = tail_fwd_lds(R, D0, BF) > tail_bwd_lds(R, BF) ? tail_fwd_lds(R, D0, BF) : tail_bwd_lds(R, BF);
   static bool attr_done = false;
   if (!attr_done) {
-    hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void *>(tail_fwd_bwd_kernel<NW, MT, D0, BF>), (int)lds);
+    hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void *>(tail_fwd_bwd_kernel<MT, D0, BF>), (int)lds);
     if (e != hipSuccess) { set_error("tail_forward_backward: LDS attribute: %s", hipGetErrorString(e)); return (int)e; }
     attr_done = true;
   }
   STDADK_LAUNCH_NAMED(D0 ? (BF ? "tail_fwd_bwd_kernel<dense0,bf16>" : "tail_fwd_bwd_kernel<dense0>")
                          : (BF ? "tail_fwd_bwd_kernel<bf16>" : "tail_fwd_bwd_kernel"),
-                      (tail_fwd_bwd_kernel<NW, MT, D0, BF>), dim3((unsigned)ceil_div(f.B, R)), dim3(TT), lds, st, f, b);
+                      (tail_fwd_bwd_kernel<MT, D0, BF>), dim3((unsigned)ceil_div(f.B, R)), dim3(TAIL_THREADS), lds, st, f, b);
   STDADK_CHECK_LAUNCH("tail_forward_backward");
   return 0;
 }
@@ -189,8 +171,8 @@ int tail_forward_backward(const TailFwdArgs &f_in, const TailBwdArgs &b_in, hipS
   STDADK_REQUIRE((f.bf16 != 0) == (b.bf16 != 0), STDADK_E_ARG, "tail: forward and backward disagree on bf16 operands");
   const int r = tail_rows(f.B, bf && d0);
   if (int rc = check_d0(f)) return rc;
-  if (int rc = check_bf(f.bf16, f.n_layers, f.L, true, 0)) return rc;
-  if (int rc = check_bf(b.bf16, b.n_layers, b.L, false, 1)) return rc;
+  if (int rc = tail_check_bf16(f.bf16, f.n_layers, f.L, true, 0)) return rc;
+  if (int rc = tail_check_bf16(b.bf16, b.n_layers, b.L, false, 1)) return rc;
   return TAIL_DISPATCH(launch_fwd_bwd, r, d0, bf, f, b, st);
 }
 
@@ -200,9 +182,9 @@ int tail_backward(const TailBwdArgs &a_in, hipStream_t st, bool cap32) {
   TailBwdArgs a = a_in;
   a.krot = tail_krot();
   const int r = tail_rows(a.B, cap32);
-  if (int rc = check_bf(a.bf16, a.n_layers, a.L, false, 1)) return rc;
-  if (a.bf16) return r == 64 ? launch_bwd<16, 4, true>(a, st) : (r == 32 ? launch_bwd<16, 2, true>(a, st) : launch_bwd<16, 1, true>(a, st));
-  return r == 64 ? launch_bwd<16, 4, false>(a, st) : (r == 32 ? launch_bwd<16, 2, false>(a, st) : launch_bwd<16, 1, false>(a, st));
+  if (int rc = tail_check_bf16(a.bf16, a.n_layers, a.L, false, 1)) return rc;
+  if (a.bf16) return r == 64 ? launch_bwd<4, true>(a, st) : (r == 32 ? launch_bwd<2, true>(a, st) : launch_bwd<1, true>(a, st));
+  return r == 64 ? launch_bwd<4, false>(a, st) : (r == 32 ? launch_bwd<2, false>(a, st) : launch_bwd<1, false>(a, st));
 }
 
 }  // namespace stdadk

@@ -1,14 +1,10 @@
 // Bodies of the fused MLP-tail kernels (see tail.h / tail.hip), shared by their own kernels and by the
 // fused training-step kernel (fused_step.hip).  `tile` = index of the row tile (R rows) a workgroup carries.
 //
-// Everything that depends on the workgroup shape lives in Tail<NW> (NW waves of 64 lanes):
-//   Tail<16>: 1024 threads, ONE workgroup per CU, one 16-column N tile per wave; 16 / 32 / 64-row tiles.  The shape of
-//             every launch of the library and of the fused step kernel (fused_step.hip) -- at 16 rows per CU the
-//             phases are latency-bound and more waves = more loads in flight.
-//   Tail<8>:  512 threads, up to two N tiles per wave, 32-row tiles whose LDS (<= 76 KiB) and registers (<= 128) let
-//             TWO workgroups share a CU, so that one's row-local phases (LayerNorm, stores, barriers) could run beside
-//             the other's GEMM phases.  Built, parity-tested and measured in round 2: no faster at any batch size
-//             (DESIGN.md section 8), so the library does not instantiate it; tools/diag/occupancy_tail8.hip does.
+// One workgroup shape: 16 waves (1024 threads), ONE workgroup per CU, wave w owning the 16-column N tile w of every
+// GEMM; 16 / 32 / 64-row tiles.  At 16 rows per CU the phases are latency-bound and more waves = more loads in flight.
+// A 512-thread variant (two workgroups per CU, two N tiles per wave) measured 0-4 % slower: DESIGN.md section 8 and
+// profiles/r02_tail_two_workgroups_per_cu.txt; its code is in the history before the commit that removed it.
 #pragma once
 #include "tail.h"
 #include "basis.h"
@@ -18,6 +14,9 @@ namespace stdadk {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int ACT_LD = TAIL_MAX_W + 4;        // activation row stride in LDS (floats)
+constexpr int TAIL_WAVES = 16;                // waves per workgroup: one per 16-column N tile of the widest layer
+constexpr int TAIL_THREADS = 64 * TAIL_WAVES; // threads per workgroup (1024)
+static_assert(16 * TAIL_WAVES == TAIL_MAX_W, "one N tile per wave");
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding
 // GLOBAL store (vmcnt(0)); nothing in these kernels reads global data written by another wave.
@@ -29,8 +28,7 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-template <int NI>
-struct BFrag { float4 v[2 * NI]; };     // [2*i + j]: chunk fragment of this lane, N tile i, 16-deep half j
+struct BFrag { float4 v[2]; };          // [j]: chunk fragment of this lane (the wave's N tile), 16-deep half j
 
 // ---------------------------------------------------------------------------------------------
 // bf16 operands (STDADK_FLAG_BF16): v_mfma_f32_16x16x32_bf16, fp32 accumulate
@@ -54,8 +52,7 @@ __device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
 }
 __device__ __forceinline__ u16 to_bf16(float a) { return (u16)(pack_bf16(a, 0.f) & 0xffffu); }
 
-template <int NI>
-struct BFragH { uint4 v[2 * NI]; };     // [2*i + half]: this lane's 16 k of weight row n_i in chunk c
+struct BFragH { uint4 v[2]; };          // [half]: this lane's 16 k of weight row n in chunk c
 
 #ifdef STDADK_DIAG   // diagnostic build only: in-kernel wall-clock stamps of the phases
 #define STAMP(i) do { if (a.stamps && tid == 0) a.stamps[tile * 16 + (i)] = wall_clock64(); } while (0)
@@ -68,49 +65,35 @@ struct BFragH { uint4 v[2 * NI]; };     // [2*i + half]: this lane's 16 k of wei
 #define WSTAMP(i) do { } while (0)
 #endif
 
-template <int NW_>
-struct Tail {
-static constexpr int NW = NW_;                       // waves per workgroup
-static constexpr int TT = 64 * NW;                   // threads per workgroup
-static constexpr int MAX_NI = TAIL_MAX_W / 16 / NW;  // N tiles per wave: tile i of a wave is column tile wave + NW*i
-static_assert(MAX_NI == 1 || MAX_NI == 2, "Tail<NW>: 8 or 16 waves");
-
-// N tiles per wave a GEMM of width N runs with (scalar).  A tile index beyond the layer's N/16 tiles (widths that
-// are not a multiple of 16*NW) is clamped for the loads and its accumulator is never stored.
-static __device__ __forceinline__ int tiles_of(int N) { return ((N >> 4) + NW - 1) / NW; }
-
 // Loads are UNCONDITIONAL from clamped (always valid) addresses and never masked in registers: a
 // conditional load gets its own branch + vmcnt(0), and a select on the loaded value drags the wait
-// in front of the MFMAs of the previous chunk.  The number of N tiles of this wave (NI) is a
-// template parameter and the K-half test is scalar, so the MFMA stream has no exec-masked branches.
-// KN = false: W is [N][K] (K contiguous): one dwordx4 per tile and 16-deep half.
+// in front of the MFMAs of the previous chunk.  The K-half test is scalar, so the MFMA stream has no
+// exec-masked branches.
+// KN = false: W is [N][K] (K contiguous): one dwordx4 per 16-deep half.
 // KN = true:  W is [K][N] row-major (N contiguous): nn.Linear's own (out,in) weight read as the B operand of
 //             dA = dZ . W -- four dword loads (64-byte pieces per 16 lanes) instead of one dwordx4, and no
 //             transposed copy of the weights is needed.  Component e of v[..] is k = 32c + 16j + 4q + e in both
 //             forms, the same k order as the A fragments.
-template <int NI, bool KN>
-static __device__ __forceinline__ void load_bfrag(BFrag<MAX_NI> &f, const float *__restrict__ W, int N, int K, int c,
-                                                  int wave, int c16, int q) {
+template <bool KN>
+__device__ __forceinline__ void load_bfrag(BFrag &f, const float *__restrict__ W, int N, int K, int c, int wave,
+                                           int c16, int q) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int k = 32 * c + 16 * j + 4 * q;
     const int kc = k < K ? k : 0;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int n = min(16 * (wave + NW * i), N - 16) + c16;
-      if constexpr (KN) {
-        const float *b = W + (size_t)kc * N + n;
-        f.v[2 * i + j] = make_float4(b[0], b[N], b[2 * (size_t)N], b[3 * (size_t)N]);
-      } else {
-        f.v[2 * i + j] = *reinterpret_cast<const float4 *>(W + (size_t)n * K + kc);
-      }
+    const int n = min(16 * wave, N - 16) + c16;
+    if constexpr (KN) {
+      const float *b = W + (size_t)kc * N + n;
+      f.v[j] = make_float4(b[0], b[N], b[2 * (size_t)N], b[3 * (size_t)N]);
+    } else {
+      f.v[j] = *reinterpret_cast<const float4 *>(W + (size_t)n * K + kc);
     }
   }
 }
 
-template <int NI, int MT>
-static __device__ __forceinline__ void mma_chunk(f32x4 (*acc)[MAX_NI], const BFrag<MAX_NI> &f, const float *__restrict__ A,
-                                                 int K, int c, int c16, int q) {
+template <int MT>
+__device__ __forceinline__ void mma_chunk(f32x4 *acc, const BFrag &f, const float *__restrict__ A, int K, int c,
+                                          int c16, int q) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     if (32 * c + 16 * j < K) {          // scalar: K is a multiple of 16, a 16-deep half is all in or out
@@ -122,14 +105,11 @@ static __device__ __forceinline__ void mma_chunk(f32x4 (*acc)[MAX_NI], const BFr
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
+        const float4 bv = f.v[j];
+        const float bf[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-          const float4 bv = f.v[2 * i + j];
-          const float bf[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt) {    // every weight fragment feeds all row tiles
-            acc[mt][i] = mfma16(af[mt][e], bf[e], acc[mt][i]);
-          }
+        for (int mt = 0; mt < MT; ++mt) {    // every weight fragment feeds all row tiles
+          acc[mt] = mfma16(af[mt][e], bf[e], acc[mt]);
         }
       }
     }
@@ -141,12 +121,12 @@ static __device__ __forceinline__ void mma_chunk(f32x4 (*acc)[MAX_NI], const BFr
 // chunk `rot mod nchunk` and wraps around, so that at any instant the CUs of an XCD are spread over the chunks, i.e.
 // over different lines / channels; only the order of a tile's fp32 partial sums changes.  Measured (round 3, VERDICT
 // r2 item 3): no gain -- off by default (rot = 0 is the natural order), kept as a switch for that measurement.
-static __device__ __forceinline__ int chunk_start(int rot, int nchunk) { return rot % nchunk; }
+__device__ __forceinline__ int chunk_start(int rot, int nchunk) { return rot % nchunk; }
 
 // mma_chunk for a chunk that lies entirely below K (no scalar test per 16-deep half: straight-line code)
-template <int NI, int MT>
-static __device__ __forceinline__ void mma_chunk_full(f32x4 (*acc)[MAX_NI], const BFrag<MAX_NI> &f, const float *__restrict__ A,
-                                                      int c, int c16, int q) {
+template <int MT>
+__device__ __forceinline__ void mma_chunk_full(f32x4 *acc, const BFrag &f, const float *__restrict__ A, int c, int c16,
+                                               int q) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     float af[MT][4];
@@ -157,13 +137,10 @@ static __device__ __forceinline__ void mma_chunk_full(f32x4 (*acc)[MAX_NI], cons
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
+      const float4 bv = f.v[j];
+      const float bf[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        const float4 bv = f.v[2 * i + j];
-        const float bf[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt][i] = mfma16(af[mt][e], bf[e], acc[mt][i]);
-      }
+      for (int mt = 0; mt < MT; ++mt) acc[mt] = mfma16(af[mt][e], bf[e], acc[mt]);
     }
   }
 }
@@ -172,32 +149,29 @@ static __device__ __forceinline__ void mma_chunk_full(f32x4 (*acc)[MAX_NI], cons
 // LayerNorm / input phase that precedes the GEMM) so that its L2 round trip is hidden behind that phase.
 // `rot`: this workgroup's rotation of the K-chunk order (chunk_start above), 0 = natural order.
 template <bool KN = false>
-static __device__ __forceinline__ void preload_w(BFrag<MAX_NI> &f, const float *__restrict__ W, int N, int K,
-                                                 int wave, int c16, int q, int rot = 0) {
-  // always all MAX_NI tiles (a tile the layer does not have is a clamped, unused load): one write pattern for the
-  // fragment whatever the layer's width keeps it in registers
-  if (wave < (N >> 4)) load_bfrag<MAX_NI, KN>(f, W, N, K, chunk_start(rot, (K + 31) >> 5), wave, c16, q);
+__device__ __forceinline__ void preload_w(BFrag &f, const float *__restrict__ W, int N, int K, int wave, int c16,
+                                          int q, int rot = 0) {
+  if (wave < (N >> 4)) load_bfrag<KN>(f, W, N, K, chunk_start(rot, (K + 31) >> 5), wave, c16, q);
 }
 
-// GEMM of a phase: acc[mt][i] (rows 16 mt.., N tile wave + NW*i) += A[R x K] (LDS, row stride ACT_LD) * W.
+// GEMM of a phase: acc[mt] (rows 16 mt.., N tile `wave`) += A[R x K] (LDS, row stride ACT_LD) * W.
 // M = 16..64 rows is the GEMV-like regime: every wave streams ITS OWN slice of W straight into VGPRs (no
 // LDS staging, no workgroup barrier in the K loop), two 32-deep chunks in flight; chunk 0 is already in
 // registers (preload_w).
-template <int MT, int NI, bool KN>
-static __device__ __forceinline__ void gemm16_loop(f32x4 (*acc)[MAX_NI], const float *__restrict__ A,
-                                                   const float *__restrict__ W, int N, int K, int wave, int c16,
-                                                   int q, BFrag<MAX_NI> &f0, int rot) {
+template <int MT, bool KN>
+__device__ __forceinline__ void gemm16_loop(f32x4 *acc, const float *__restrict__ A, const float *__restrict__ W,
+                                            int N, int K, int wave, int c16, int q, BFrag &f0, int rot) {
   const int nchunk = (K + 31) >> 5;
-  BFrag<MAX_NI> f1;
+  BFrag f1;
   int c = chunk_start(rot, nchunk);             // f0 holds this chunk (preload_w)
   for (int i = 0; i < nchunk; i += 2) {
     const int c1 = c + 1 == nchunk ? 0 : c + 1;
-    if (i + 1 < nchunk) load_bfrag<NI, KN>(f1, W, N, K, c1, wave, c16, q);
-    mma_chunk<NI, MT>(acc, f0, A, K, c, c16, q);
+    if (i + 1 < nchunk) load_bfrag<KN>(f1, W, N, K, c1, wave, c16, q);
+    mma_chunk<MT>(acc, f0, A, K, c, c16, q);
     if (i + 1 < nchunk) {
       const int c2 = c1 + 1 == nchunk ? 0 : c1 + 1;
-      if (i + 2 < nchunk) load_bfrag<NI, KN>(f0, W, N, K, c2, wave, c16, q);
-      mma_chunk<NI, MT>(acc, f1, A, K, c1, c16, q);
+      if (i + 2 < nchunk) load_bfrag<KN>(f0, W, N, K, c2, wave, c16, q);
+      mma_chunk<MT>(acc, f1, A, K, c1, c16, q);
       c = c2;
     }
   }
@@ -210,116 +184,102 @@ static __device__ __forceinline__ void gemm16_loop(f32x4 (*acc)[MAX_NI], const f
 // every chunk's MFMAs waited for the NEXT chunk's fragments: no weight chunk was ever in flight under the MFMAs, and
 // the phase ran at ~60-70 % of the matrix pipe with four waves per SIMD covering for each other (round-3 per-wave
 // stamps, tools/diag/wave_stamps.py).  Unrolled, every wait is an exact count.
-template <int MT, int NI, bool KN, int NCH>
-static __device__ __forceinline__ void gemm16_unrolled(f32x4 (*acc)[MAX_NI], const float *__restrict__ A,
-                                                       const float *__restrict__ W, int N, int K, int wave, int c16,
-                                                       int q, const BFrag<MAX_NI> &f0) {
+template <int MT, bool KN, int NCH>
+__device__ __forceinline__ void gemm16_unrolled(f32x4 *acc, const float *__restrict__ A, const float *__restrict__ W,
+                                                int N, int K, int wave, int c16, int q, const BFrag &f0) {
   // (also measured: the A fragments of the next 16-deep step read from LDS ahead of the current step's MFMAs, two
   //  register sets -- 56.8 vs 57.3 us for the 16-row fused kernel, 403 vs 388 us at 64 rows; and that order pinned
   //  with sched_group_barrier -- 59.8 / 407 us: the compiler's own placement of the LDS reads stays)
-  BFrag<MAX_NI> f[3];
+  BFrag f[3];
   f[0] = f0;
-  if (NCH > 1) load_bfrag<NI, KN>(f[1], W, N, K, 1, wave, c16, q);
-  if (NCH > 2) load_bfrag<NI, KN>(f[2], W, N, K, 2, wave, c16, q);
+  if (NCH > 1) load_bfrag<KN>(f[1], W, N, K, 1, wave, c16, q);
+  if (NCH > 2) load_bfrag<KN>(f[2], W, N, K, 2, wave, c16, q);
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
-    mma_chunk_full<NI, MT>(acc, f[c % 3], A, c, c16, q);
-    if (c + 3 < NCH) load_bfrag<NI, KN>(f[c % 3], W, N, K, c + 3, wave, c16, q);
+    mma_chunk_full<MT>(acc, f[c % 3], A, c, c16, q);
+    if (c + 3 < NCH) load_bfrag<KN>(f[c % 3], W, N, K, c + 3, wave, c16, q);
   }
 }
 
 template <int MT, bool KN = false>
-static __device__ __forceinline__ void gemm16_pre(f32x4 (*acc)[MAX_NI], const float *__restrict__ A,
-                                                  const float *__restrict__ W, int N, int K, int wave, int c16,
-                                                  int q, BFrag<MAX_NI> &f0, int rot = 0) {
+__device__ __forceinline__ void gemm16_pre(f32x4 *acc, const float *__restrict__ A, const float *__restrict__ W, int N,
+                                           int K, int wave, int c16, int q, BFrag &f0, int rot = 0) {
   if (wave >= (N >> 4)) return;                 // scalar: this wave has no N tile in a narrow layer
 
-  if (MAX_NI > 1 && tiles_of(N) > 1) gemm16_loop<MT, MAX_NI, KN>(acc, A, W, N, K, wave, c16, q, f0, rot);
-  else if (MAX_NI == 1 && rot == 0 && K == 256) gemm16_unrolled<MT, 1, KN, 8>(acc, A, W, N, K, wave, c16, q, f0);
-  else if (MAX_NI == 1 && rot == 0 && K == 128) gemm16_unrolled<MT, 1, KN, 4>(acc, A, W, N, K, wave, c16, q, f0);
-  else gemm16_loop<MT, 1, KN>(acc, A, W, N, K, wave, c16, q, f0, rot);
+  if (rot == 0 && K == 256) gemm16_unrolled<MT, KN, 8>(acc, A, W, N, K, wave, c16, q, f0);
+  else if (rot == 0 && K == 128) gemm16_unrolled<MT, KN, 4>(acc, A, W, N, K, wave, c16, q, f0);
+  else gemm16_loop<MT, KN>(acc, A, W, N, K, wave, c16, q, f0, rot);
 }
 
 // ---- bf16 operands
 // unconditional loads from clamped addresses like load_bfrag; a piece beyond K meets zeros in the A image
-template <int NI>
-static __device__ __forceinline__ void load_bfrag_h(BFragH<MAX_NI> &f, const u16 *__restrict__ Wn, int N, int K, int c,
-                                                    int wave, int c16, int q) {
+__device__ __forceinline__ void load_bfrag_h(BFragH &f, const u16 *__restrict__ Wn, int N, int K, int c, int wave,
+                                             int c16, int q) {
   const int k = 64 * c + 16 * q;
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int n = min(16 * (wave + NW * i), N - 16) + c16;
-    const uint4 *src = reinterpret_cast<const uint4 *>(Wn + (size_t)n * K + (k < K ? k : 0));
-    f.v[2 * i] = src[0]; f.v[2 * i + 1] = src[1];
-  }
+  const int n = min(16 * wave, N - 16) + c16;
+  const uint4 *src = reinterpret_cast<const uint4 *>(Wn + (size_t)n * K + (k < K ? k : 0));
+  f.v[0] = src[0]; f.v[1] = src[1];
 }
 
-template <int NI, int MT>
-static __device__ __forceinline__ void mma_chunk_h(f32x4 (*acc)[MAX_NI], const BFragH<MAX_NI> &f, const u16 *__restrict__ A,
-                                                   int c, int c16, int q) {
+template <int MT>
+__device__ __forceinline__ void mma_chunk_h(f32x4 *acc, const BFragH &f, const u16 *__restrict__ A, int c, int c16,
+                                            int q) {
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
     const uint4 *ap = reinterpret_cast<const uint4 *>(A + (16 * mt + c16) * ABF_LD + 64 * c + 16 * q);
     const uint4 a0 = ap[0], a1 = ap[1];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      acc[mt][i] = mfma16h(a0, f.v[2 * i], acc[mt][i]);
-      acc[mt][i] = mfma16h(a1, f.v[2 * i + 1], acc[mt][i]);
-    }
+    acc[mt] = mfma16h(a0, f.v[0], acc[mt]);
+    acc[mt] = mfma16h(a1, f.v[1], acc[mt]);
   }
 }
 
-static __device__ __forceinline__ void preload_wh(BFragH<MAX_NI> &f, const u16 *__restrict__ Wn, int N, int K, int wave,
-                                                  int c16, int q, int rot = 0) {
-  if (wave < (N >> 4)) load_bfrag_h<MAX_NI>(f, Wn, N, K, chunk_start(rot, (K + 63) >> 6), wave, c16, q);
+__device__ __forceinline__ void preload_wh(BFragH &f, const u16 *__restrict__ Wn, int N, int K, int wave, int c16,
+                                           int q, int rot = 0) {
+  if (wave < (N >> 4)) load_bfrag_h(f, Wn, N, K, chunk_start(rot, (K + 63) >> 6), wave, c16, q);
 }
 
-// acc[mt][i] += A[R x K] (bf16 image in LDS, columns K .. 64 ceil(K/64) zero) * W^T, W = [N][K] bf16 in global
+// acc[mt] += A[R x K] (bf16 image in LDS, columns K .. 64 ceil(K/64) zero) * W^T, W = [N][K] bf16 in global
 // memory, chunk 0 already in registers (preload_wh), two chunks in flight
-template <int MT, int NI>
-static __device__ __forceinline__ void gemm16_loop_h(f32x4 (*acc)[MAX_NI], const u16 *__restrict__ A,
-                                                     const u16 *__restrict__ Wn, int N, int K, int wave, int c16, int q,
-                                                     BFragH<MAX_NI> &f0, int rot) {
+template <int MT>
+__device__ __forceinline__ void gemm16_loop_h(f32x4 *acc, const u16 *__restrict__ A, const u16 *__restrict__ Wn, int N,
+                                              int K, int wave, int c16, int q, BFragH &f0, int rot) {
   const int nchunk = (K + 63) >> 6;
-  BFragH<MAX_NI> f1;
+  BFragH f1;
   int c = chunk_start(rot, nchunk);
   for (int i = 0; i < nchunk; i += 2) {
     const int c1 = c + 1 == nchunk ? 0 : c + 1;
-    if (i + 1 < nchunk) load_bfrag_h<NI>(f1, Wn, N, K, c1, wave, c16, q);
-    mma_chunk_h<NI, MT>(acc, f0, A, c, c16, q);
+    if (i + 1 < nchunk) load_bfrag_h(f1, Wn, N, K, c1, wave, c16, q);
+    mma_chunk_h<MT>(acc, f0, A, c, c16, q);
     if (i + 1 < nchunk) {
       const int c2 = c1 + 1 == nchunk ? 0 : c1 + 1;
-      if (i + 2 < nchunk) load_bfrag_h<NI>(f0, Wn, N, K, c2, wave, c16, q);
-      mma_chunk_h<NI, MT>(acc, f1, A, c1, c16, q);
+      if (i + 2 < nchunk) load_bfrag_h(f0, Wn, N, K, c2, wave, c16, q);
+      mma_chunk_h<MT>(acc, f1, A, c1, c16, q);
       c = c2;
     }
   }
 }
 // the unrolled ring of gemm16_unrolled for the bf16 operands: K = 64 NCH exactly (256 -> 4 chunks, 128 -> 2)
-template <int MT, int NI, int NCH>
-static __device__ __forceinline__ void gemm16_unrolled_h(f32x4 (*acc)[MAX_NI], const u16 *__restrict__ A,
-                                                         const u16 *__restrict__ Wn, int N, int K, int wave, int c16,
-                                                         int q, const BFragH<MAX_NI> &f0) {
-  BFragH<MAX_NI> f[3];
+template <int MT, int NCH>
+__device__ __forceinline__ void gemm16_unrolled_h(f32x4 *acc, const u16 *__restrict__ A, const u16 *__restrict__ Wn,
+                                                  int N, int K, int wave, int c16, int q, const BFragH &f0) {
+  BFragH f[3];
   f[0] = f0;
-  if (NCH > 1) load_bfrag_h<NI>(f[1], Wn, N, K, 1, wave, c16, q);
-  if (NCH > 2) load_bfrag_h<NI>(f[2], Wn, N, K, 2, wave, c16, q);
+  if (NCH > 1) load_bfrag_h(f[1], Wn, N, K, 1, wave, c16, q);
+  if (NCH > 2) load_bfrag_h(f[2], Wn, N, K, 2, wave, c16, q);
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
-    mma_chunk_h<NI, MT>(acc, f[c % 3], A, c, c16, q);
-    if (c + 3 < NCH) load_bfrag_h<NI>(f[c % 3], Wn, N, K, c + 3, wave, c16, q);
+    mma_chunk_h<MT>(acc, f[c % 3], A, c, c16, q);
+    if (c + 3 < NCH) load_bfrag_h(f[c % 3], Wn, N, K, c + 3, wave, c16, q);
   }
 }
 
 template <int MT>
-static __device__ __forceinline__ void gemm16_pre_h(f32x4 (*acc)[MAX_NI], const u16 *__restrict__ A,
-                                                    const u16 *__restrict__ Wn, int N, int K, int wave, int c16, int q,
-                                                    BFragH<MAX_NI> &f0, int rot = 0) {
+__device__ __forceinline__ void gemm16_pre_h(f32x4 *acc, const u16 *__restrict__ A, const u16 *__restrict__ Wn, int N,
+                                             int K, int wave, int c16, int q, BFragH &f0, int rot = 0) {
   if (wave >= (N >> 4)) return;
-  if (MAX_NI > 1 && tiles_of(N) > 1) gemm16_loop_h<MT, MAX_NI>(acc, A, Wn, N, K, wave, c16, q, f0, rot);
-  else if (MAX_NI == 1 && rot == 0 && K == 256) gemm16_unrolled_h<MT, 1, 4>(acc, A, Wn, N, K, wave, c16, q, f0);
-  else if (MAX_NI == 1 && rot == 0 && K == 128) gemm16_unrolled_h<MT, 1, 2>(acc, A, Wn, N, K, wave, c16, q, f0);
-  else gemm16_loop_h<MT, 1>(acc, A, Wn, N, K, wave, c16, q, f0, rot);
+  if (rot == 0 && K == 256) gemm16_unrolled_h<MT, 4>(acc, A, Wn, N, K, wave, c16, q, f0);
+  else if (rot == 0 && K == 128) gemm16_unrolled_h<MT, 2>(acc, A, Wn, N, K, wave, c16, q, f0);
+  else gemm16_loop_h<MT>(acc, A, Wn, N, K, wave, c16, q, f0, rot);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -329,11 +289,11 @@ static __device__ __forceinline__ void gemm16_pre_h(f32x4 (*acc)[MAX_NI], const 
 // D; and into the feature buffer (row stride ldf = D rounded up to 32, padding zero) for the backward.
 // Same arithmetic as rbf_build_kernel (phi_eval / psi_eval of basis.h).
 template <int MT>
-static __device__ __forceinline__ void d0_fill_features(const TailDense0 &z, float *act0, float *act1, int row0, int B) {
+__device__ __forceinline__ void d0_fill_features(const TailDense0 &z, float *act0, float *act1, int row0, int B) {
   constexpr int R = 16 * MT;
   const int D = z.p + z.Ks + z.Kt;
   const int Dp = (D + 31) & ~31;
-  for (int idx = threadIdx.x; idx < R * Dp; idx += TT) {
+  for (int idx = threadIdx.x; idx < R * Dp; idx += TAIL_THREADS) {
     const int row = idx / Dp, col = idx - row * Dp;
     const int grow = min(row0 + row, B - 1);
     float v = 0.f;
@@ -359,7 +319,7 @@ static __device__ __forceinline__ void d0_fill_features(const TailDense0 &z, flo
 }
 
 // B fragment of chunk c from W0^T [D][N] with every row index clamped below D (the A columns there are zero)
-static __device__ __forceinline__ void d0_load_bfrag(BFrag<MAX_NI> &f, const float *__restrict__ W0T, int N, int D, int c, int wave,
+__device__ __forceinline__ void d0_load_bfrag(BFrag &f, const float *__restrict__ W0T, int N, int D, int c, int wave,
                                               int c16, int q) {
   const int n = 16 * wave + c16;
 #pragma unroll
@@ -373,21 +333,19 @@ static __device__ __forceinline__ void d0_load_bfrag(BFrag<MAX_NI> &f, const flo
 
 // acc += features (LDS, two 256-column halves) . W0^T, 32-deep chunks, two in flight like gemm16_pre
 template <int MT>
-static __device__ __forceinline__ void d0_gemm(f32x4 (*acc)[MAX_NI], const float *act0, const float *act1,
-                                               const float *__restrict__ W0T, int N, int D, int wave, int c16, int q,
-                                               BFrag<MAX_NI> &f0) {
-  static_assert(MAX_NI == 1, "the dense layer 0 inside the tail launch is built for 16 waves");
+__device__ __forceinline__ void d0_gemm(f32x4 *acc, const float *act0, const float *act1, const float *__restrict__ W0T,
+                                        int N, int D, int wave, int c16, int q, BFrag &f0) {
   if (wave >= (N >> 4)) return;
   const int Kp = (D + 15) & ~15;                 // mma_chunk works in 16-deep halves
   const int nchunk = (D + 31) >> 5;
   constexpr int HC = TAIL_MAX_W / 32;            // chunks per LDS half
-  BFrag<MAX_NI> f1;
+  BFrag f1;
   for (int c = 0; c < nchunk; c += 2) {
     if (c + 1 < nchunk) d0_load_bfrag(f1, W0T, N, D, c + 1, wave, c16, q);
-    mma_chunk<1, MT>(acc, f0, c < HC ? act0 : act1 - TAIL_MAX_W, Kp, c, c16, q);
+    mma_chunk<MT>(acc, f0, c < HC ? act0 : act1 - TAIL_MAX_W, Kp, c, c16, q);
     if (c + 1 < nchunk) {
       if (c + 2 < nchunk) d0_load_bfrag(f0, W0T, N, D, c + 2, wave, c16, q);
-      mma_chunk<1, MT>(acc, f1, c + 1 < HC ? act0 : act1 - TAIL_MAX_W, Kp, c + 1, c16, q);
+      mma_chunk<MT>(acc, f1, c + 1 < HC ? act0 : act1 - TAIL_MAX_W, Kp, c + 1, c16, q);
     }
   }
 }
@@ -411,8 +369,8 @@ struct LnFwdCtx {
 };
 
 template <int RPW, int CC, bool FULL, bool BF>
-static __device__ __forceinline__ void ln_fwd_rows(const LnFwdCtx &c, float *nxt, u16 *abf, int wave, int lane, int row0,
-                                                   const float (&gv)[4], const float (&bev)[4]) {
+__device__ __forceinline__ void ln_fwd_rows(const LnFwdCtx &c, float *nxt, u16 *abf, int wave, int lane, int row0,
+                                            const float (&gv)[4], const float (&bev)[4]) {
   const int h = c.h;
   bool okc[CC];
 #pragma unroll
@@ -502,9 +460,9 @@ struct LnBwdCtx {
 // untouched).  Staged over the rows like the forward phase: the masked gradient and the two row sums of every row,
 // then the rows' reductions (independent chains), then dZ and its stores.
 template <int RPW, int CC, bool FULL, bool BF>
-static __device__ __forceinline__ void ln_bwd_rows(const LnBwdCtx &c, float *cur, u16 *abf, int wave, int lane, int row0,
-                                                   const float (&gv)[4], const float (&bev)[4], const float (&xv)[RPW][4],
-                                                   const float (&rsv)[RPW], float (&pg)[4], float (&pb)[4], float (&pz)[4]) {
+__device__ __forceinline__ void ln_bwd_rows(const LnBwdCtx &c, float *cur, u16 *abf, int wave, int lane, int row0,
+                                            const float (&gv)[4], const float (&bev)[4], const float (&xv)[RPW][4],
+                                            const float (&rsv)[RPW], float (&pg)[4], float (&pb)[4], float (&pz)[4]) {
   const int h = c.h;
   bool okc[CC];
 #pragma unroll
@@ -589,8 +547,8 @@ static __device__ __forceinline__ void ln_bwd_rows(const LnBwdCtx &c, float *cur
 // current activations in the place of the second fp32 tile -- with D0 the fp32 pair stays (the features of layer 0
 // use both halves) and the image follows them.
 template <int MT, bool D0 = false, bool BF = false>
-static __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float *smem, float *red, const int tile) {
-  constexpr int R = 16 * MT, RPW = (R + NW - 1) / NW;
+__device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float *smem, float *red, const int tile) {
+  constexpr int R = 16 * MT, RPW = (R + TAIL_WAVES - 1) / TAIL_WAVES;
   float *act0 = smem, *act1 = (BF && !D0) ? smem : smem + R * ACT_LD;
   u16 *abf = reinterpret_cast<u16 *>(smem + (D0 ? 2 : 1) * R * ACT_LD);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -600,9 +558,8 @@ static __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float
   // workgroups b, b + 8, ... share an XCD: consecutive ones of them start their K walks one chunk apart
   const int rot = a.krot ? (int)(blockIdx.x >> 3) : 0;
   STAMP(0);
-  static_assert(!D0 || MAX_NI == 1, "the dense layer 0 inside the tail launch is built for 16 waves");
-  BFrag<MAX_NI> wpre;
-  BFragH<MAX_NI> wpre_h;
+  BFrag wpre;
+  BFragH wpre_h;
   if constexpr (D0) {
     if (a.d0.on == 1) {
       if (wave < (a.d0.L0.h >> 4)) d0_load_bfrag(wpre, a.d0.W0T, a.d0.L0.h, a.d0.L0.hp, 0, wave, c16, q);
@@ -618,17 +575,17 @@ static __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float
     // input tile: unconditional loads from clamped rows (rows >= B duplicate the last row; nothing
     // computed for them is ever stored), 4 per thread in flight
     const int v4 = a.h_in >> 2;            // <= 64 float4 per row => R*v4 <= 64*R
-    constexpr int NLD = 64 * R / TT;
+    constexpr int NLD = 64 * R / TAIL_THREADS;
     float4 tv[NLD];
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-      const int idx = min(tid + TT * i, R * v4 - 1);
+      const int idx = min(tid + TAIL_THREADS * i, R * v4 - 1);
       const int row = idx / v4, c4 = idx - row * v4;
       tv[i] = *reinterpret_cast<const float4 *>(a.a_in + (size_t)min(row0 + row, a.B - 1) * a.h_in + 4 * c4);
     }
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-      const int idx = tid + TT * i;
+      const int idx = tid + TAIL_THREADS * i;
       if (idx < R * v4) {
         const int row = idx / v4, c4 = idx - row * v4;
         *reinterpret_cast<float4 *>(act0 + row * ACT_LD + 4 * c4) = tv[i];
@@ -639,7 +596,7 @@ static __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float
     if constexpr (BF) {
       // the image's columns h_in .. 255 are zero: a 64-deep chunk may reach past K
       const int z4 = (TAIL_MAX_W - a.h_in) >> 2;
-      for (int idx = tid; idx < R * z4; idx += TT) {
+      for (int idx = tid; idx < R * z4; idx += TAIL_THREADS) {
         const int row = idx / z4, c4 = idx - row * z4;
         *reinterpret_cast<uint2 *>(abf + row * ABF_LD + a.h_in + 4 * c4) = make_uint2(0u, 0u);
       }
@@ -674,19 +631,15 @@ static __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float
     }
     // this wave's bias columns: requested before the GEMM like the LayerNorm parameters (it used to be a dependent
     // L2 round trip between the last MFMA and the stores of z: ~1 us per layer at the tail of every wave)
-    float bias_v[MAX_NI];
+    const float bias_v = L.b[min(16 * wave, h - 16) + c16];
+    f32x4 acc[MT];
 #pragma unroll
-    for (int i = 0; i < MAX_NI; ++i) bias_v[i] = L.b[min(16 * (wave + NW * i), h - 16) + c16];
-    f32x4 acc[MT][MAX_NI];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int i = 0; i < MAX_NI; ++i) acc[mt][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int mt = 0; mt < MT; ++mt) acc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const bool parts = D0 && li < 0 && a.d0.on == 2;    // scalar
     if (parts) {
       // site x time grid: the pre-activation of layer 0 is the sum of a per-site and a per-time row
       const int h4 = h >> 2;
-      for (int idx = tid; idx < R * h4; idx += TT) {
+      for (int idx = tid; idx < R * h4; idx += TAIL_THREADS) {
         const int row = idx / h4, c4 = idx - row * h4;
         const int grow = min(row0 + row, a.B - 1);
         const int ti = grow / a.d0.S, si = grow - ti * a.d0.S;
@@ -713,17 +666,12 @@ static __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float
     }
     STAMP(2 + 4 * (li < 0 ? 0 : li));
     // z = acc + bias into the other activation buffer
+    if (wave < NT && !parts) {
+      const int col = 16 * wave + c16;
 #pragma unroll
-    for (int i = 0; i < MAX_NI; ++i) {
-      const int t = wave + NW * i;
-      if (t < NT && !parts) {
-        const int col = 16 * t + c16;
-        const float bv = bias_v[i];
+      for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) nxt[(16 * mt + 4 * q + r) * ACT_LD + col] = acc[mt][i][r] + bv;
-      }
+        for (int r = 0; r < 4; ++r) nxt[(16 * mt + 4 * q + r) * ACT_LD + col] = acc[mt][r] + bias_v;
     }
     if (li == 0) WSTAMP(2);
     lds_barrier();
@@ -791,7 +739,7 @@ static __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float
     if (tid == 0) {
       float t = 0.f;
 #pragma unroll
-      for (int w = 0; w < NW; ++w) t += red[w];
+      for (int w = 0; w < TAIL_WAVES; ++w) t += red[w];
       atomicAdd(a.loss_sum, t);
     }
   }
@@ -800,20 +748,25 @@ static __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float
 // ---------------------------------------------------------------------------------------------
 // backward (data path): dA / dZ of every hidden layer + column partials for dgamma, dbeta, db
 // ---------------------------------------------------------------------------------------------
-// LDS floats of the backward body (the launch code sizes the dynamic segment with it)
-template <int MT, bool BF>
-static constexpr size_t tail_bwd_lds_floats() {
-  constexpr size_t R = 16 * MT;
-  if (BF) return R * ACT_LD + (R * ABF_LD + 1) / 2 + 3 * NW * 256 + R * TAIL_MAXQ;
-  return 2 * R * ACT_LD + (R * ACT_LD >= (size_t)3 * NW * 256 ? 0 : 3 * NW * 256) + R * TAIL_MAXQ;
+// LDS of the bodies for R-row tiles: floats of the backward body (the layout at the top of tail_bwd_body), and the
+// bytes the launch code sizes the dynamic segment with.  Forward with bf16 operands: one fp32 tile + the bf16 image
+// (with the dense layer 0: the fp32 pair + the image).
+constexpr size_t tail_bwd_lds_floats(size_t R, bool bf) {
+  if (bf) return R * ACT_LD + (R * ABF_LD + 1) / 2 + 3 * TAIL_WAVES * 256 + R * TAIL_MAXQ;
+  return 2 * R * ACT_LD + (R * ACT_LD >= (size_t)3 * TAIL_WAVES * 256 ? 0 : 3 * TAIL_WAVES * 256) + R * TAIL_MAXQ;
+}
+constexpr size_t tail_bwd_lds(size_t R, bool bf) { return tail_bwd_lds_floats(R, bf) * sizeof(float); }
+constexpr size_t tail_fwd_lds(size_t R, bool d0, bool bf) {
+  if (!bf) return 2 * R * ACT_LD * sizeof(float);
+  return (d0 ? 2 : 1) * R * ACT_LD * sizeof(float) + R * ABF_LD * sizeof(u16);
 }
 
 // Head of the backward: dY of the tile's rows into LDS (sdy [R][Q]), dA_last = dY Wo into d0, and the partials of
-// dWo / dbo over the tile's rows into part_head[tile][Q*hl (dWo) | Q (dbo)].  `scr`: LDS scratch [TT/256][Q][256]
-// (32 / 64 rows), free until the first LayerNorm phase.  Q1: one output column.
+// dWo / dbo over the tile's rows into part_head[tile][Q*hl (dWo) | Q (dbo)].  `scr`: LDS scratch
+// [TAIL_THREADS / 256][Q][256] (32 / 64 rows), free until the first LayerNorm phase.  Q1: one output column.
 template <int MT, bool BF, bool Q1>
-static __device__ __forceinline__ void bwd_head(const TailBwdArgs &a, float *d0, float *scr, float *sdy, int row0, int tile,
-                                                int hl) {
+__device__ __forceinline__ void bwd_head(const TailBwdArgs &a, float *d0, float *scr, float *sdy, int row0, int tile,
+                                         int hl) {
   constexpr int R = 16 * MT;
   constexpr int QM = Q1 ? 1 : TAIL_MAXQ;
   const int tid = threadIdx.x;
@@ -825,7 +778,7 @@ static __device__ __forceinline__ void bwd_head(const TailBwdArgs &a, float *d0,
     sdy[tid] = (tid < R * Q && row0 + row < a.B) ? a.dY[(size_t)(row0 + row) * Q + qq] : 0.f;
   }
   // this thread's column of Wo (requested before the barrier), then its column of dA for every NG-th row
-  constexpr int NG = TT / 256;
+  constexpr int NG = TAIL_THREADS / 256;
   const int g = tid >> 8, col = tid & 255;
   const int colc = min(col, hl - 1);
   float wo[QM];
@@ -895,7 +848,7 @@ static __device__ __forceinline__ void bwd_head(const TailBwdArgs &a, float *d0,
         ph[tid] = t;
       }
     } else {
-      for (int i = tid; i < Q * hl; i += TT) {
+      for (int i = tid; i < Q * hl; i += TAIL_THREADS) {
         const int qq = i / hl, c2 = i - qq * hl;
         float t = 0.f;
 #pragma unroll
@@ -915,15 +868,15 @@ static __device__ __forceinline__ void bwd_head(const TailBwdArgs &a, float *d0,
 // BF: dA = dZ W with bf16 operands (the transposed weight copies WTbf as the K-contiguous operand): ONE fp32
 // gradient tile (LayerNorm backward in place, the GEMM's output lands in it again) + the bf16 image of dZ.
 template <int MT, bool BF = false>
-static __device__ __forceinline__ void tail_bwd_body(const TailBwdArgs &a, float *smem, const int tile) {
-  constexpr int R = 16 * MT, RPW = (R + NW - 1) / NW;
+__device__ __forceinline__ void tail_bwd_body(const TailBwdArgs &a, float *smem, const int tile) {
+  constexpr int R = 16 * MT, RPW = (R + TAIL_WAVES - 1) / TAIL_WAVES;
   float *d0 = smem, *d1 = BF ? smem : smem + R * ACT_LD;
   u16 *abf = reinterpret_cast<u16 *>(smem + R * ACT_LD);
-  // column-partial scratch [3][NW][256]: with 64 rows the spare activation buffer is large enough and
+  // column-partial scratch [3][TAIL_WAVES][256]: with 64 rows the spare activation buffer is large enough and
   // free during the LayerNorm phase, so it is aliased there instead of taking another 48 KiB
-  constexpr bool RED_ALIAS = !BF && (size_t)R * ACT_LD >= (size_t)3 * NW * 256;
+  constexpr bool RED_ALIAS = !BF && (size_t)R * ACT_LD >= (size_t)3 * TAIL_WAVES * 256;
   float *red_own = BF ? smem + R * ACT_LD + (R * ABF_LD + 1) / 2 : smem + 2 * R * ACT_LD;
-  float *sdy = red_own + (RED_ALIAS ? 0 : 3 * NW * 256);   // [R][TAIL_MAXQ]
+  float *sdy = red_own + (RED_ALIAS ? 0 : 3 * TAIL_WAVES * 256);   // [R][TAIL_MAXQ]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int q = lane >> 4, c16 = lane & 15;
@@ -972,9 +925,9 @@ static __device__ __forceinline__ void tail_bwd_body(const TailBwdArgs &a, float
   for (int li = a.n_layers - 1; li >= 0; --li) {
     const TailLayer &L = a.L[li];
     const int h = L.h;
-    BFrag<MAX_NI> wpre;
-    BFragH<MAX_NI> wpre_h;
-    if (li > 0) {                                                       // for the dA GEMM at the end of this pass
+    BFrag wpre;
+    BFragH wpre_h;
+    if (li > 0) {                                                      // for the dA GEMM at the end of this pass
       if constexpr (BF) preload_wh(wpre_h, L.WTbf, L.hp, h, wave, c16, q, rot);
       else preload_w<true>(wpre, L.W, L.hp, h, wave, c16, q, rot);
     }
@@ -993,9 +946,9 @@ static __device__ __forceinline__ void tail_bwd_body(const TailBwdArgs &a, float
     float *red = RED_ALIAS ? nxt : red_own;
 #pragma unroll
     for (int cc = 0; cc < 4; ++cc) {
-      red[(0 * NW + wave) * 256 + lane + 64 * cc] = pg[cc];
-      red[(1 * NW + wave) * 256 + lane + 64 * cc] = pb[cc];
-      red[(2 * NW + wave) * 256 + lane + 64 * cc] = pz[cc];
+      red[(0 * TAIL_WAVES + wave) * 256 + lane + 64 * cc] = pg[cc];
+      red[(1 * TAIL_WAVES + wave) * 256 + lane + 64 * cc] = pb[cc];
+      red[(2 * TAIL_WAVES + wave) * 256 + lane + 64 * cc] = pz[cc];
     }
     lds_barrier();
     if (tid < h) {
@@ -1004,7 +957,7 @@ static __device__ __forceinline__ void tail_bwd_body(const TailBwdArgs &a, float
       for (int k = 0; k < 3; ++k) {
         float t = 0.f;
 #pragma unroll
-        for (int w = 0; w < NW; ++w) t += red[(k * NW + w) * 256 + tid];
+        for (int w = 0; w < TAIL_WAVES; ++w) t += red[(k * TAIL_WAVES + w) * 256 + tid];
         pbase[k * h + tid] = t;
       }
     }
@@ -1013,32 +966,24 @@ static __device__ __forceinline__ void tail_bwd_body(const TailBwdArgs &a, float
     // ---- (b) dA_prev[16 x hp] = dZ[16 x h] W[h x hp], with W^T ([hp][h], K contiguous) as the B operand
     const int hp = L.hp;
     const int NT = hp >> 4;
-    f32x4 acc[MT][MAX_NI];
+    f32x4 acc[MT];
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int i = 0; i < MAX_NI; ++i) acc[mt][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int mt = 0; mt < MT; ++mt) acc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     ln_inputs(a.L[li - 1]);        // consumed after the GEMM, in the next pass
     lds_barrier();                 // every wave's dZ rows are in `cur`
     if constexpr (BF) gemm16_pre_h<MT>(acc, abf, L.WTbf, hp, h, wave, c16, q, wpre_h, rot);
     else gemm16_pre<MT, true>(acc, cur, L.W, hp, h, wave, c16, q, wpre, rot);
     STAMP(3 + 3 * (a.n_layers - 1 - li));      // dA GEMM of this pass
+    if (wave < NT) {
 #pragma unroll
-    for (int i = 0; i < MAX_NI; ++i) {
-      const int t = wave + NW * i;
-      if (t < NT) {
+      for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) nxt[(16 * mt + 4 * q + r) * ACT_LD + 16 * t + c16] = acc[mt][i][r];
-      }
+        for (int r = 0; r < 4; ++r) nxt[(16 * mt + 4 * q + r) * ACT_LD + 16 * wave + c16] = acc[mt][r];
     }
     lds_barrier();
     STAMP(4 + 3 * (a.n_layers - 1 - li));      // dA tile stored + barrier
     float *tmp = cur; cur = nxt; nxt = tmp;
   }
 }
-
-};  // struct Tail<NW>
 
 }  // namespace stdadk
