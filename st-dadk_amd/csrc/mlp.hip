@@ -1174,12 +1174,17 @@ extern "C" int32_t stdadk_step_uses_window(const stdadk_basis_desc *b, const std
   return want_window(b, d, flags) ? 1 : 0;
 }
 
+// the workspace plan of a step on `B` rows (the scattered-knot buffers exist on the window path only)
+static void plan_step(const stdadk_basis_desc *b, const stdadk_mlp_desc *d, int64_t B, int32_t flags, Plan *p) {
+  make_plan(d, B, p, want_window(b, d, flags) ? PLAN_STEP_WINDOW : PLAN_STEP_DENSE, b->p, (int)b->Kt, learn_ks(b, flags),
+            is_scattered(b, flags) ? b->Ks : 0, b->n_levels, b->Ks);
+}
+
 extern "C" size_t stdadk_step_workspace_bytes(const stdadk_basis_desc *b, const stdadk_mlp_desc *d, int64_t B,
                                               int32_t flags) {
   if (check_desc(d) != 0 || check_basis(b, d) != 0 || B < 0 || B >= (1ll << 31)) return 0;
   Plan p;
-  make_plan(d, B > 0 ? B : 1, &p, want_window(b, d, flags) ? PLAN_STEP_WINDOW : PLAN_STEP_DENSE, b->p, (int)b->Kt,
-            learn_ks(b, flags), is_scattered(b, flags) ? b->Ks : 0, b->n_levels, b->Ks);
+  plan_step(b, d, B > 0 ? B : 1, flags, &p);
   return p.total_floats * sizeof(float);
 }
 
@@ -1195,8 +1200,7 @@ static int step_common(Ctx &c, const stdadk_basis_desc *b, const stdadk_mlp_desc
   rc = check_levels(b, flags);
   if (rc) return rc;
   c.scattered = *window && is_scattered(b, flags);
-  make_plan(d, B, &c.pl, *window ? PLAN_STEP_WINDOW : PLAN_STEP_DENSE, b->p, (int)b->Kt, learn_ks(b, flags),
-            c.scattered ? b->Ks : 0, b->n_levels, b->Ks);
+  plan_step(b, d, B, flags, &c.pl);
   c.log_bw = (flags & STDADK_FLAG_LOG_BW) != 0;
   c.bf16 = (flags & STDADK_FLAG_BF16) != 0;
   STDADK_REQUIRE(!c.bf16 || (tail_enabled() && d->n_hidden >= 1 && tail_supported(d, 1)), STDADK_E_ARG,
@@ -1739,21 +1743,14 @@ static int train_step_impl(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
     rc = stdadk_step_advance(o->step_dev, stream);
     if (rc) return rc;
   }
-  if (bin_next && !binned_in_dw) {
-    // the NEXT batch's binning inside this step's optimiser launch (optim.hip: adamw_bin_kernel), when it is the
-    // one-launch binning of small batches; the caller then steps on `next_workspace` with STDADK_FLAG_PREBINNED
-    rc = adamw_ema_with_binning(o->p, o->g, o->m, o->v, o->ema, o->n, o->lr, o->lr_dev, o->beta1, o->beta2, o->eps,
-                                o->weight_decay, o->step_dev, o->max_norm, clip ? parts : nullptr, n_parts,
-                                o->ema_decay, o->shadow, o->nonfinite_step ? loss_sum : nullptr, o->nonfinite_step,
-                                stream, ba);
-    if (rc == 0) *next_binned = 1;
-    return rc;
-  }
-  rc = stdadk_adamw_ema_f32(o->p, o->g, o->m, o->v, o->ema, o->n, o->lr, o->lr_dev, o->beta1, o->beta2, o->eps,
-                            o->weight_decay, 1, o->step_dev, o->max_norm, clip ? parts : nullptr, n_parts,
-                            1.0f, o->ema_decay, o->shadow, o->nonfinite_step ? loss_sum : nullptr, o->nonfinite_step,
-                            stream);
-  if (rc == 0 && binned_in_dw) *next_binned = 1;
+  // with `bin`: the NEXT batch's binning inside this step's optimiser launch (optim.hip: adamw_bin_kernel), when it is
+  // the one-launch binning of small batches; the caller then steps on `next_workspace` with STDADK_FLAG_PREBINNED
+  const BinSmallArgs *bin = bin_next && !binned_in_dw ? &ba : nullptr;
+  stdadk_adam_group gr;
+  AdamHyper h;
+  optim_group(o, clip ? parts : nullptr, n_parts, loss_sum, &gr, &h);
+  rc = adamw_launch("adamw", 1, &gr, nullptr, h, bin, stream);
+  if (rc == 0 && (bin || binned_in_dw)) *next_binned = 1;
   return rc;
 }
 

@@ -298,35 +298,46 @@ extern "C" int stdadk_sumsq_f32(const float *g, int64_t n, float *parts, int32_t
   return 0;
 }
 
-static int adamw_impl(float *p, const float *g, float *m, float *v, float *ema, int64_t n,
-                      float lr, const float *lr_dev, float beta1, float beta2, float eps,
-                      float weight_decay, int32_t step, const int32_t *step_dev, float max_norm,
-                      const float *sumsq_parts, int32_t n_parts, float grad_mul,
-                      float ema_decay, const stdadk_bf16_shadow *shadow,
-                      const float *loss_watch, int32_t *nonfinite_step, stdadk_stream_t stream,
-                      const stdadk::BinSmallArgs *bin) {
-  STDADK_REQUIRE(n >= 0, STDADK_E_ARG, "adamw: negative n");
-  STDADK_REQUIRE((loss_watch != nullptr) == (nonfinite_step != nullptr), STDADK_E_ARG,
-                 "adamw: loss_watch and nonfinite_step go together (both or neither)");
-  if (n == 0) return 0;
-  STDADK_REQUIRE(p && g && m && v, STDADK_E_ARG, "adamw: NULL pointer");
-  STDADK_REQUIRE(step_dev || step >= 1, STDADK_E_ARG, "adamw: step must be >= 1");
-  STDADK_REQUIRE(max_norm <= 0.f || (sumsq_parts && n_parts > 0), STDADK_E_ARG, "adamw: max_norm > 0 needs sumsq parts");
-  AdamArgs a;
-  a.p = p; a.g = g; a.m = m; a.v = v; a.ema = ema; a.n = n; a.lr = lr; a.lr_dev = lr_dev;
-  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay; a.step = step; a.step_dev = step_dev;
-  a.max_norm = max_norm; a.sumsq = sumsq_parts; a.n_parts = n_parts; a.grad_mul = grad_mul; a.ema_decay = ema_decay;
-  a.watch = loss_watch; a.bad_step = nonfinite_step;
-  if (int rc = fill_shadow(a.sh, shadow, p, n)) return rc;
-  STDADK_REQUIRE(a.sh.n == 0 || ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                                  reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(ema)) & 15) == 0,
-                 STDADK_E_ALIGN, "adamw: bf16 shadows need 16-byte aligned buffers");
+// The one place that validates a parameter group against the hyper-parameters and fills the kernel's arguments.
+// `guard`: this group's launch keeps the non-finite guard; `may_be_empty`: n == 0 is accepted and leaves a.n == 0.
+static int fill_adam(AdamArgs &a, const char *what, const stdadk_adam_group *gr, const AdamHyper &h, bool guard,
+                     bool may_be_empty) {
+  STDADK_REQUIRE((h.loss_watch != nullptr) == (h.nonfinite_step != nullptr), STDADK_E_ARG,
+                 "%s: loss_watch and nonfinite_step go together (both or neither)", what);
+  a.n = 0;
+  if (may_be_empty && gr && gr->n == 0) return 0;
+  STDADK_REQUIRE(gr && gr->n > 0 && gr->p && gr->g && gr->m && gr->v, STDADK_E_ARG, "%s: NULL pointer%s", what,
+                 may_be_empty ? "" : " or empty group");
+  STDADK_REQUIRE(h.step_dev || h.step >= 1, STDADK_E_ARG, "%s: step must be >= 1", what);
+  STDADK_REQUIRE(gr->max_norm <= 0.f || (gr->sumsq_parts && gr->n_parts > 0), STDADK_E_ARG,
+                 "%s: max_norm > 0 needs sumsq parts", what);
+  a.p = gr->p; a.g = gr->g; a.m = gr->m; a.v = gr->v; a.ema = gr->ema; a.n = gr->n; a.lr = gr->lr; a.lr_dev = gr->lr_dev;
+  a.beta1 = h.beta1; a.beta2 = h.beta2; a.eps = h.eps; a.wd = h.weight_decay; a.step = h.step; a.step_dev = h.step_dev;
+  a.max_norm = gr->max_norm; a.sumsq = gr->sumsq_parts; a.n_parts = gr->n_parts; a.grad_mul = h.grad_mul;
+  a.ema_decay = h.ema_decay;
+  a.watch = guard ? h.loss_watch : nullptr; a.bad_step = guard ? h.nonfinite_step : nullptr;
+  if (int rc = fill_shadow(a.sh, gr->shadow, gr->p, gr->n)) return rc;
+  STDADK_REQUIRE(a.sh.n == 0 || ((reinterpret_cast<uintptr_t>(gr->g) | reinterpret_cast<uintptr_t>(gr->m) |
+                                  reinterpret_cast<uintptr_t>(gr->v) | reinterpret_cast<uintptr_t>(gr->ema)) & 15) == 0,
+                 STDADK_E_ALIGN, "%s: bf16 shadows need 16-byte aligned buffers", what);
+  return 0;
+}
+
+// The one place that launches them: `ng` (1 or 2) filled groups; `bin` (one group only): the next batch to bin with them.
+static int launch_adam(const AdamArgs *a, int ng, const BinSmallArgs *bin, hipStream_t st) {
   // grid: at most 6 workgroups per CU = ONE resident round of the chip (72 VGPRs: 7 fit), each thread walking
   // its float4 groups with a grid stride -- a second, partly filled round of one-group threads cost 3 us of the
   // 20 (MI355X, 2.76 M parameters, tools/sweep_knobs.sh: 2 695 blocks 20.6 us, 1 536 blocks 17.6 us = 5.6 TB/s)
-  int64_t blocks = ceil_div(n, 256 * 4);
-  if (blocks > 1536) blocks = 1536;
-  { const char *e = getenv("STDADK_ADAMW_BLOCKS"); if (e && atoi(e) > 0) blocks = atoi(e); }   // measurement aid
+  int64_t nb[2] = {0, 0};
+  for (int i = 0; i < ng; ++i) nb[i] = std::min<int64_t>(ceil_div(a[i].n, 256 * 4), 1536);
+  if (ng == 2) {
+    STDADK_REQUIRE(!bin, STDADK_E_ARG, "adamw2: the two-group launch bins no batch");
+    STDADK_LAUNCH(adamw_ema2_kernel, dim3((unsigned)(nb[0] + nb[1])), dim3(256), 0, st, a[0], a[1], (int)nb[0]);
+    STDADK_CHECK_LAUNCH("adamw_ema2");
+    return 0;
+  }
+  int64_t blocks = nb[0];
+  { const char *e = getenv("STDADK_ADAMW_BLOCKS"); if (e && atoi(e) > 0) blocks = atoi(e); }   // measurement aid (one group)
   if (bin) {
     // one resident round of 1024-thread workgroups (the dynamic LDS of the binning allows one per CU): the binning
     // workgroups first, the optimiser on the other CUs
@@ -342,14 +353,24 @@ static int adamw_impl(float *p, const float *g, float *m, float *v, float *ema, 
       if (e != hipSuccess) { set_error("adamw_bin: LDS attribute: %s", hipGetErrorString(e)); return (int)e; }
       attr = true;
     }
-    STDADK_LAUNCH_NAMED("adamw_bin_kernel", adamw_bin_kernel, dim3((unsigned)(ab + n_bin)), dim3(1024), lds,
-                        (hipStream_t)stream, a, *bin, n_bin);
+    STDADK_LAUNCH_NAMED("adamw_bin_kernel", adamw_bin_kernel, dim3((unsigned)(ab + n_bin)), dim3(1024), lds, st, a[0],
+                        *bin, n_bin);
     STDADK_CHECK_LAUNCH("adamw_bin");
     return 0;
   }
-  STDADK_LAUNCH(adamw_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  STDADK_LAUNCH(adamw_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a[0]);
   STDADK_CHECK_LAUNCH("adamw_ema");
   return 0;
+}
+
+int stdadk::adamw_launch(const char *what, int ng, const stdadk_adam_group *g0, const stdadk_adam_group *g1,
+                         const AdamHyper &h, const BinSmallArgs *bin, stdadk_stream_t stream) {
+  const stdadk_adam_group *gr[2] = {g0, g1};
+  AdamArgs a[2];
+  for (int i = 0; i < ng; ++i)
+    if (int rc = fill_adam(a[i], what, gr[i], h, i == 0, ng == 1)) return rc;
+  if (a[0].n == 0) return 0;                      // (one empty group)
+  return launch_adam(a, ng, bin, (hipStream_t)stream);
 }
 
 extern "C" int stdadk_adamw_ema_f32(float *p, const float *g, float *m, float *v, float *ema, int64_t n,
@@ -358,36 +379,10 @@ extern "C" int stdadk_adamw_ema_f32(float *p, const float *g, float *m, float *v
                                     const float *sumsq_parts, int32_t n_parts, float grad_mul,
                                     float ema_decay, const stdadk_bf16_shadow *shadow,
                                     const float *loss_watch, int32_t *nonfinite_step, stdadk_stream_t stream) {
-  return adamw_impl(p, g, m, v, ema, n, lr, lr_dev, beta1, beta2, eps, weight_decay, step, step_dev, max_norm,
-                    sumsq_parts, n_parts, grad_mul, ema_decay, shadow, loss_watch, nonfinite_step, stream, nullptr);
-}
-
-namespace stdadk {
-int adamw_ema_with_binning(float *p, const float *g, float *m, float *v, float *ema, int64_t n, float lr,
-                           const float *lr_dev, float beta1, float beta2, float eps, float weight_decay,
-                           const int32_t *step_dev, float max_norm, const float *sumsq_parts, int32_t n_parts,
-                           float ema_decay, const stdadk_bf16_shadow *shadow, const float *loss_watch,
-                           int32_t *nonfinite_step, stdadk_stream_t stream, const BinSmallArgs &bin) {
-  return adamw_impl(p, g, m, v, ema, n, lr, lr_dev, beta1, beta2, eps, weight_decay, 1, step_dev, max_norm, sumsq_parts,
-                    n_parts, 1.0f, ema_decay, shadow, loss_watch, nonfinite_step, stream, &bin);
-}
-}  // namespace stdadk
-
-static int fill_group(AdamArgs &a, const stdadk_adam_group *gr, float beta1, float beta2, float eps, float wd,
-                      int32_t step, const int32_t *step_dev, float grad_mul, float ema_decay) {
-  STDADK_REQUIRE(gr && gr->n > 0 && gr->p && gr->g && gr->m && gr->v, STDADK_E_ARG, "adamw2: NULL pointer or empty group");
-  STDADK_REQUIRE(gr->max_norm <= 0.f || (gr->sumsq_parts && gr->n_parts > 0), STDADK_E_ARG,
-                 "adamw2: max_norm > 0 needs sumsq parts");
-  a.p = gr->p; a.g = gr->g; a.m = gr->m; a.v = gr->v; a.ema = gr->ema; a.n = gr->n; a.lr = gr->lr; a.lr_dev = gr->lr_dev;
-  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = wd; a.step = step; a.step_dev = step_dev;
-  a.max_norm = gr->max_norm; a.sumsq = gr->sumsq_parts; a.n_parts = gr->n_parts; a.grad_mul = grad_mul;
-  a.ema_decay = ema_decay;
-  a.watch = nullptr; a.bad_step = nullptr;
-  if (int rc = fill_shadow(a.sh, gr->shadow, gr->p, gr->n)) return rc;
-  STDADK_REQUIRE(a.sh.n == 0 || ((reinterpret_cast<uintptr_t>(gr->g) | reinterpret_cast<uintptr_t>(gr->m) |
-                                  reinterpret_cast<uintptr_t>(gr->v) | reinterpret_cast<uintptr_t>(gr->ema)) & 15) == 0,
-                 STDADK_E_ALIGN, "adamw2: bf16 shadows need 16-byte aligned buffers");
-  return 0;
+  STDADK_REQUIRE(n >= 0, STDADK_E_ARG, "adamw: negative n");
+  const stdadk_adam_group gr = {p, g, m, v, ema, n, lr, lr_dev, max_norm, sumsq_parts, n_parts, shadow};
+  const AdamHyper h = {beta1, beta2, eps, weight_decay, step, step_dev, grad_mul, ema_decay, loss_watch, nonfinite_step};
+  return adamw_launch("adamw", 1, &gr, nullptr, h, nullptr, stream);
 }
 
 extern "C" int stdadk_bf16_shadow_refresh(const float *p, const stdadk_bf16_shadow *shadow, stdadk_stream_t stream) {
@@ -406,19 +401,6 @@ extern "C" int stdadk_adamw_ema2_f32(const stdadk_adam_group *g0, const stdadk_a
                                      float beta2, float eps, float weight_decay, int32_t step,
                                      const int32_t *step_dev, float grad_mul, float ema_decay,
                                      const float *loss_watch, int32_t *nonfinite_step, stdadk_stream_t stream) {
-  STDADK_REQUIRE(step_dev || step >= 1, STDADK_E_ARG, "adamw2: step must be >= 1");
-  STDADK_REQUIRE((loss_watch != nullptr) == (nonfinite_step != nullptr), STDADK_E_ARG,
-                 "adamw2: loss_watch and nonfinite_step go together (both or neither)");
-  AdamArgs a0, a1;
-  int rc = fill_group(a0, g0, beta1, beta2, eps, weight_decay, step, step_dev, grad_mul, ema_decay);
-  if (rc) return rc;
-  rc = fill_group(a1, g1, beta1, beta2, eps, weight_decay, step, step_dev, grad_mul, ema_decay);
-  if (rc) return rc;
-  a0.watch = loss_watch; a0.bad_step = nonfinite_step;        // group 0's first block keeps the guard
-  int64_t nb0 = ceil_div(a0.n, 256 * 4), nb1 = ceil_div(a1.n, 256 * 4);
-  if (nb0 > 1536) nb0 = 1536;        // one resident round of the chip (see stdadk_adamw_ema_f32)
-  if (nb1 > 1536) nb1 = 1536;
-  STDADK_LAUNCH(adamw_ema2_kernel, dim3((unsigned)(nb0 + nb1)), dim3(256), 0, (hipStream_t)stream, a0, a1, (int)nb0);
-  STDADK_CHECK_LAUNCH("adamw_ema2");
-  return 0;
+  const AdamHyper h = {beta1, beta2, eps, weight_decay, step, step_dev, grad_mul, ema_decay, loss_watch, nonfinite_step};
+  return adamw_launch("adamw2", 2, g0, g1, h, nullptr, stream);
 }

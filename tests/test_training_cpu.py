@@ -208,6 +208,49 @@ def _record(tmp):
                                             va.t.data_ptr(), None, va.y.data_ptr(), idx.data_ptr(), BATCH, None, 0,
                                             1.0 / BATCH, None, None, ws.data_ptr(), ws.numel() * 4, st.flags, None)
     rec["errors"]["null_acc"] = [null_acc, real.stdadk_last_error().decode()]
+
+    # --- 4. refusals of the optimiser entry points: code and text
+    def refused(fn, *a, **kw):
+        try:
+            fn(*a, **kw)
+            return "ok"
+        except RuntimeError as e:
+            return str(e)
+    n = 64
+    p_, g_, m_, v_, e_ = (torch.zeros(n + 4) for _ in range(5))
+    bufs = (p_[:n], g_[:n], m_[:n], v_[:n], e_[:n])
+    parts, word, watch = torch.zeros(N.SUMSQ_PARTS), torch.zeros(1, dtype=torch.int32), torch.zeros(1)
+    half = torch.zeros(32, dtype=torch.bfloat16)
+    shadow = N.make_bf16_shadow([(0, 4, 8, half, None)])
+    hyper = ((0.9, 0.999), 1e-8, 0.0, 1)
+    group = N.make_adam_group(*bufs, 1e-3)
+    rec["optim_errors"] = {
+        "ok": refused(N.adamw_ema, *bufs, 1e-3, *hyper, max_norm=1.0, sumsq_parts=parts, shadow=shadow,
+                      loss_watch=watch, nonfinite_step=word),
+        "ok2": refused(N.adamw_ema2, group, group, *hyper, loss_watch=watch, nonfinite_step=word),
+        "empty_ok": refused(N.adamw_ema, *(b[:0] for b in bufs), 1e-3, *hyper),
+        "clip": refused(N.adamw_ema, *bufs, 1e-3, *hyper, max_norm=1.0),
+        "clip2": refused(N.adamw_ema2, group, N.make_adam_group(*bufs, 1e-3, max_norm=1.0), *hyper),
+        "watch": refused(N.adamw_ema, *bufs, 1e-3, *hyper, loss_watch=watch),
+        "watch2": refused(N.adamw_ema2, group, group, *hyper, nonfinite_step=word),
+        "shadow": refused(N.adamw_ema, p_[:n], g_[1:n + 1], m_[:n], v_[:n], e_[:n], 1e-3, *hyper, shadow=shadow),
+        "shadow2": refused(N.adamw_ema2, group, N.make_adam_group(p_[:n], g_[:n], m_[1:n + 1], v_[:n], e_[:n], 1e-3,
+                                                                 shadow=shadow), *hyper),
+        "empty2": refused(N.adamw_ema2, group, N.make_adam_group(*(b[:0] for b in bufs), 1e-3), *hyper),
+        "step0": refused(N.adamw_ema, *bufs, 1e-3, (0.9, 0.999), 1e-8, 0.0, 0),
+    }
+    eng = TrainStep(model(), max_batch=BATCH, ema_decay=0.99, seed=1)
+    tr = data(BATCH, 3)
+
+    def one_call(**kw):
+        a = dict(p=eng.flat, g=eng.grad, m=eng.m, v=eng.v, ema=eng.ema, lr=1e-3, lr_dev=None, betas=(0.9, 0.999), eps=1e-8,
+                 weight_decay=0.0, step_dev=eng.step_dev, max_norm=1.0, sumsq_parts=eng._sumsq512, ema_decay=0.99)
+        a.update(kw)
+        st = eng.state
+        return refused(N.train_step, st.basis, st.desc, st.params, eng.grads_t, tr.coords, tr.t.view(-1), None, tr.y, None,
+                       BATCH, 1.0 / BATCH, eng.loss_sum, eng.ws, st.flags, N.make_optim(**a))
+    rec["optim_errors"].update({"desc_ok": one_call(), "desc_no_step": one_call(step_dev=None),
+                                "desc_no_m": one_call(m=None), "desc_clip": one_call(sumsq_parts=None)})
     print("RECORD " + json.dumps(rec))
 
 
@@ -280,6 +323,25 @@ def test_argument_errors(rec):
     assert "workspace" in e["big_B"] and "workspace" in e["small_ws"]
     assert "metric_col" in e["metric_col"] and "metric_col" in e["metric_neg"]
     assert e["null_acc"][0] == -1 and "NULL pointer" in e["null_acc"][1]
+
+
+def test_optimiser_entry_points_refuse_with_code_and_text(rec):
+    """What the AdamW entries and the one-call step refuse, under the prefix of the entry that was called: a clip norm
+    without partials, half a non-finite guard, bf16 copies next to a buffer off its 16-byte boundary, an empty group of
+    the two-group call (a lone empty group is a no-op), step 0, an incomplete optimiser descriptor."""
+    e = rec["optim_errors"]
+    assert e["ok"] == "ok" and e["ok2"] == "ok" and e["empty_ok"] == "ok" and e["desc_ok"] == "ok"
+    for key, code, text in [
+            ("clip", -1, "adamw: max_norm > 0 needs sumsq parts"), ("clip2", -1, "adamw2: max_norm > 0 needs sumsq parts"),
+            ("watch", -1, "adamw: loss_watch and nonfinite_step go together (both or neither)"),
+            ("watch2", -1, "adamw2: loss_watch and nonfinite_step go together (both or neither)"),
+            ("shadow", -3, "adamw: bf16 shadows need 16-byte aligned buffers"),
+            ("shadow2", -3, "adamw2: bf16 shadows need 16-byte aligned buffers"),
+            ("empty2", -1, "adamw2: NULL pointer or empty group"), ("step0", -1, "adamw: step must be >= 1"),
+            ("desc_no_step", -1, "train_step: optimiser descriptor incomplete"),
+            ("desc_no_m", -1, "train_step: optimiser descriptor incomplete"),
+            ("desc_clip", -1, "train_step: max_norm > 0 needs sumsq_parts")]:
+        assert e[key].endswith(f"failed (code {code}): {text}"), (key, e[key])
 
 
 if __name__ == "__main__":
