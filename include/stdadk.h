@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define STDADK_ABI_VERSION 9
+#define STDADK_ABI_VERSION 10
 #define STDADK_MAX_HIDDEN 8
 #define STDADK_MAX_LEVELS 8
 #define STDADK_SUMSQ_PARTS 256 /* partial sums written by stdadk_sumsq_f32 */
@@ -514,6 +514,39 @@ int stdadk_eval_indexed_f32(const stdadk_basis_desc *basis, const stdadk_mlp_des
                             const stdadk_loss_desc *loss, int32_t metric_col, double batch_weight, double *acc,
                             float *y_pred, void *workspace, size_t workspace_bytes, int32_t flags,
                             stdadk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Grid scores (ABI 10): what the reference's driver does last with a trained model -- the (T, S) prediction grid
+ * against the full field, split by the train / valid / test masks (scripts/train_st_interp.py:1228-1252
+ * `site_mse = nanmean((pred - z)^2, axis=0)`, :1378-1409, :2242, :2551-2560) -- as a reduction on the device, one
+ * CHUNK of nT consecutive time slices per call, so that the grid never has to exist as a whole:
+ *   y_pred [nT*S][Q]  predictions, time-major: row = ti*S + s (what stdadk_forward_parts_f32 writes)
+ *   z      [nT][S]    the field's slice, NaN (or +-inf) = no value: such an entry counts NOWHERE, N included
+ *   split  [nT][S]    codes 0..3 (the Python face: 0 none, 1 train, 2 valid, 3 test), NULL = all 0; an entry with
+ *                     another code counts nowhere
+ * All sums are float64 on the device; every element term is formed in double from operands converted to double:
+ *   split_acc [4][STDADK_GRID_SLOTS]  += per split: N; SSE, SAE of column metric_col; CHECK + q, q < Q: the check loss
+ *                     max((tau_q-1) e, tau_q e), e = z - y_pred[:,q] (tau = taus_host[q], a HOST array read during the
+ *                     call, NULL = 0.5 each); with an interval (lo_col < hi_col; -1/-1 = none) COVER = the count of
+ *                     y_pred[lo_col] <= z <= y_pred[hi_col] and WIDTH = the sum of y_pred[hi_col] - y_pred[lo_col]
+ *   site_acc  [4][S][3]   (sse, sae, n) += per split and site: a site's slices are added one by one in time order,
+ *                     starting from the value already there, so chunked calls give the bits of one call
+ *   time_acc  [4][nT][3]  (sse, sae, n) =  per split and time slice of THIS chunk (assigned, not added)
+ * Deterministic (no atomics, fixed orders).  Workspace: stdadk_grid_score_workspace_bytes(S, nT) (0 = bad sizes),
+ * 8-byte aligned.  S*nT < 2^31.  No host read of device memory, no allocation, capturable.
+ * ------------------------------------------------------------------------------------------ */
+#define STDADK_GRID_N 0
+#define STDADK_GRID_SSE 1
+#define STDADK_GRID_SAE 2
+#define STDADK_GRID_COVER 3
+#define STDADK_GRID_WIDTH 4
+#define STDADK_GRID_CHECK 5
+#define STDADK_GRID_SLOTS 16
+size_t stdadk_grid_score_workspace_bytes(int64_t S, int64_t nT);
+int stdadk_grid_score_f32(const float *y_pred, const float *z, const uint8_t *split, int64_t S, int64_t nT,
+                          int32_t Q, int32_t metric_col, const float *taus_host, int32_t lo_col, int32_t hi_col,
+                          double *split_acc, double *site_acc, double *time_acc, void *workspace,
+                          size_t workspace_bytes, stdadk_stream_t stream);
 
 /* A10 on a site x time prediction grid (the dense inference callers loop over time slices with the SAME S
  * sites in each, scripts/train_st_interp.py:1091-1107,1232-1248,1378-1409).  Layer 0's pre-activation of row

@@ -64,6 +64,11 @@ __device__ __forceinline__ float check_elem(float tau, float yq, float yt) {
   const float e = yt - yq;
   return fmaxf((tau - 1.0f) * e, tau * e);
 }
+// the same term in double (grid scores, grid_score.hip)
+__device__ __forceinline__ double check_elem(double tau, double yq, double yt) {
+  const double e = yt - yq;
+  return fmax((tau - 1.0) * e, tau * e);
+}
 
 // Validation metrics of one batch (eval.hip): values a workgroup leaves per partial -- objective, squared and absolute
 // error of the metric column, per-level check loss.

@@ -48,7 +48,7 @@ class BasisDesc(C.Structure):
                 ("t_bw", C.c_void_p)]
 
 
-ABI_VERSION = 9            # STDADK_ABI_VERSION of include/stdadk.h this binding was written against
+ABI_VERSION = 10           # STDADK_ABI_VERSION of include/stdadk.h this binding was written against
 MAX_Q = 8
 LOSS_MSE, LOSS_PINBALL = 0, 1
 
@@ -186,6 +186,10 @@ _SIGNATURES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.POINTER(LossDesc), C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    "stdadk_grid_score_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "stdadk_grid_score_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                        C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
     "stdadk_bin_batch_f32": (C.c_int, [C.POINTER(BasisDesc), C.POINTER(MlpDesc), C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                        C.c_size_t, C.c_int32, C.c_void_p]),
@@ -652,6 +656,53 @@ def eval_indexed(basis, desc, params, coords_all, t_all, X_all, y_all, idx, loss
         C.byref(loss_desc) if loss_desc is not None else None, int(metric_col), float(batch_weight), acc.data_ptr(),
         _dev(y_pred, "y_pred"), workspace.data_ptr(), workspace.numel() * workspace.element_size(), flags, _stream())
     _check(rc, "stdadk_eval_indexed_f32")
+
+
+# slots per split of the float64 accumulator stdadk_grid_score_f32 adds into (include/stdadk.h)
+GRID_N, GRID_SSE, GRID_SAE, GRID_COVER, GRID_WIDTH, GRID_CHECK, GRID_SLOTS = 0, 1, 2, 3, 4, 5, 16
+
+
+def grid_score_workspace_bytes(S, nT):
+    n = lib().stdadk_grid_score_workspace_bytes(S, nT)
+    if n == 0:
+        raise RuntimeError(f"stdadk_grid_score_workspace_bytes: bad grid {S} x {nT} (S*nT must stay below 2^31)")
+    return n
+
+
+def _f64_acc(tensor, name, shape):
+    if tensor.dtype != torch.float64 or not _on_device(tensor) or not tensor.is_contiguous() \
+            or tuple(tensor.shape) != shape:
+        raise RuntimeError(f"grid_score: {name} must be a contiguous float64 tensor of shape {shape} on the device, "
+                           f"got {tensor.dtype} {tuple(tensor.shape)} on {tensor.device}")
+    return tensor.data_ptr()
+
+
+def grid_score(y_pred, z, split, metric_col, taus, lo_col, hi_col, split_acc, site_acc, time_acc, workspace):
+    """stdadk_grid_score_f32 on one chunk of time slices: y_pred (nT*S, Q) time-major, z (nT, S) float32 with NaN = no
+    value, split (nT, S) uint8 codes 0..3 or None; sums are ADDED into split_acc (4, GRID_SLOTS) and site_acc
+    (4, S, 3) and ASSIGNED to time_acc (4, nT, 3), all float64 on the device.  taus: Q levels or None (0.5 each);
+    lo_col / hi_col: the interval's columns or -1 / -1."""
+    if z.dim() != 2 or y_pred.dim() != 2:
+        raise RuntimeError("grid_score: z must be (nT, S) and y_pred (nT*S, Q)")
+    nT, S = z.shape
+    Q = y_pred.shape[1]
+    if y_pred.shape[0] != nT * S:
+        raise RuntimeError(f"grid_score: y_pred has {y_pred.shape[0]} rows, z is {nT} x {S}")
+    for name, x in (("y_pred", y_pred), ("z", z)):
+        if x.dtype != torch.float32:
+            raise RuntimeError(f"grid_score: {name} must be float32, got {x.dtype}")
+    if split is not None and (split.dtype != torch.uint8 or tuple(split.shape) != (nT, S)):
+        raise RuntimeError(f"grid_score: split must be uint8 of shape {(nT, S)}, got {split.dtype} {tuple(split.shape)}")
+    if taus is not None and len(taus) != Q:
+        raise RuntimeError(f"grid_score: {Q} quantile levels expected, got {len(taus)}")
+    if workspace.dtype != torch.float64 or not _on_device(workspace) or not workspace.is_contiguous():
+        raise RuntimeError("grid_score: workspace must be a contiguous float64 tensor on the device")
+    arr = (C.c_float * Q)(*[float(q) for q in taus]) if taus is not None else None
+    rc = lib().stdadk_grid_score_f32(
+        _dev(y_pred, "y_pred"), _dev(z, "z"), _dev(split, "split"), S, nT, Q, int(metric_col), arr, int(lo_col),
+        int(hi_col), _f64_acc(split_acc, "split_acc", (4, GRID_SLOTS)), _f64_acc(site_acc, "site_acc", (4, S, 3)),
+        _f64_acc(time_acc, "time_acc", (4, nT, 3)), workspace.data_ptr(), workspace.numel() * 8, _stream())
+    _check(rc, "stdadk_grid_score_f32")
 
 
 def make_knot_train(centers_init, gradient_damping=False, damping_threshold=0.3, damping_strength=1.0,

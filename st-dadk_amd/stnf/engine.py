@@ -955,6 +955,7 @@ class Predictor:
         self._graph = _GraphRunner()
         self._in = (torch.empty(self.chunk, 2, device=self.dev), torch.empty(self.chunk, device=self.dev))
         self._out = torch.empty(self.chunk, model.output_dim, device=self.dev)
+        self._scratch = {}             # score_grid's buffers and accumulators, by name
 
     def _param_key(self):
         """Identity + version of everything the cached state was derived from: parameter storage (a TrainStep
@@ -977,28 +978,34 @@ class Predictor:
         st = self.state
         N.forward(st.basis, st.desc, st.params, coords, t, None, B, out, self.ws, st.flags, training=False)
 
-    @torch.no_grad()
-    def predict_grid(self, coords, t_values, max_rows=None):
-        """The same S sites at every one of T times (what the reference's dense-grid callers loop over, one
-        model call per time slice): coords (S,2), t_values (T,) -> (T, S, Q).  Layer 0's pre-activation is a
-        per-site row plus a per-time row, so the basis evaluation and the gather of first-layer weights
-        happen once per site; the rest of the network runs on the T*S rows.  Needs the window path (fixed
-        grid knots, compact-support basis) and p = 0; otherwise falls back to predict() on the expanded rows."""
-        self._refresh()
+    @staticmethod
+    def _slices_per_call(S, max_rows):
+        """Time slices per grid chunk: at most `max_rows` rows (default 2^30: int32 row indices), at least one slice."""
+        return max(1, (max_rows or (1 << 30)) // max(S, 1))
+
+    def _grid_chunks(self, coords, t_values, max_rows, dest, alloc):
+        """The body of the grid passes: yields (t0, n, y) for consecutive chunks of n time slices, y = dest(t0, n)
+        filled with the chunk's predictions, (n*S, Q) time-major.  `alloc(name, shape)` hands out the scratch tensors
+        (fresh ones for predict_grid, the predictor's reused ones for score_grid).  Layer 0's pre-activation is a
+        per-site row plus a per-time row, so the basis evaluation and the gather of first-layer weights happen once per
+        site; that needs the first weight stored (in,out) and p = 0, otherwise every chunk's rows are expanded and
+        go through predict()."""
         st = self.state
         S, T = coords.shape[0], t_values.numel()
-        coords = coords.contiguous().float()
-        t_values = t_values.contiguous().float().view(-1)
-        Q = self.model.output_dim
         m = self.model
+        per = self._slices_per_call(S, max_rows)
         parts = m.p == 0 and bool(st.flags & N.FLAG_W0_T) and len(m.hidden_dims) >= 1 and S > 0 and T > 0
         window = parts and not m.spatial_basis.learnable and N.step_uses_window(st.basis, st.desc, st.flags)
         if not parts:
-            cc = coords.repeat(T, 1)
-            tt = t_values.repeat_interleave(S)
-            return self.predict(cc, tt).view(T, S, Q)
+            for t0 in range(0, T, per):
+                n = min(per, T - t0)
+                cc, tt = alloc("coords", (min(per, T), S, 2))[:n], alloc("t", (min(per, T), S))[:n]
+                cc.copy_(coords)
+                tt.copy_(t_values[t0:t0 + n, None])
+                yield t0, n, self.predict(cc.view(n * S, 2), tt.view(n * S), out=dest(t0, n))
+            return
         h0 = m.hidden_dims[0]
-        sp = torch.empty(S, h0, device=self.dev)
+        sp = alloc("sp", (S, h0))
         w0t = st.keep if st.keep is not None else m._body[0].weight.detach().t()    # (D, h0), contiguous
         # sites per call: the workspace's chunk on the window path; about 1 GiB of features on the other
         step = self.chunk if window else max(1024, min(self.chunk, (1 << 28) // max(m.input_dim, 1)))
@@ -1009,27 +1016,104 @@ class Predictor:
             else:
                 # materialising path (scattered or few knots, Gaussian bases): phi of the chunk's sites, then one
                 # GEMM with the spatial rows of W0^T (p = 0: they are the first k_spatial rows)
-                feats = m.build_features(None, coords[s0:s0 + n], torch.zeros(n, device=self.dev))
-                N.gemm(feats, False, w0t[:m.k_spatial], True, n, h0, m.k_spatial, out=sp[s0:s0 + n])
-        tp = torch.empty(T, h0, device=self.dev)
+                feats = m.build_features(None, coords[s0:s0 + n], alloc("t0", (n,)).zero_(),
+                                         out=alloc("feats", (n, -(-m.input_dim // 32) * 32)))
+                need = N.lib().stdadk_gemm_workspace_bytes(n, h0, m.k_spatial)
+                N.gemm(feats, False, w0t[:m.k_spatial], True, n, h0, m.k_spatial, out=sp[s0:s0 + n],
+                       workspace=alloc("gemm_ws", (need // 4,)) if need else None)
+        tp = alloc("tp", (T, h0))
         N.temporal_partial(st.basis, st.desc, st.params, t_values, tp, st.flags)
-        out = torch.empty(T * S, Q, device=self.dev)
-        per = max(1, (max_rows or (1 << 30)) // max(S, 1))        # time slices per call (int32 row indices)
         for t0 in range(0, T, per):
             n = min(per, T - t0)
-            N.forward_parts(st.desc, st.params, sp, tp[t0:t0 + n], out[t0 * S:(t0 + n) * S])
+            y = dest(t0, n)
+            N.forward_parts(st.desc, st.params, sp, tp[t0:t0 + n], y)
+            yield t0, n, y
+
+    def _fresh(self, name, shape):
+        return torch.empty(shape, device=self.dev)
+
+    def _reused(self, name, shape, dtype=torch.float32):
+        """Scratch of the scoring pass, kept between calls (a repeated call on the same grid allocates nothing)."""
+        cache = self._scratch
+        buf = cache.get(name)
+        if buf is None or tuple(buf.shape) != tuple(shape) or buf.dtype != dtype:
+            buf = cache[name] = torch.empty(shape, device=self.dev, dtype=dtype)
+        return buf
+
+    @torch.no_grad()
+    def predict_grid(self, coords, t_values, max_rows=None):
+        """The same S sites at every one of T times (what the reference's dense-grid callers loop over, one
+        model call per time slice): coords (S,2), t_values (T,) -> (T, S, Q).  Layer 0's pre-activation is a
+        per-site row plus a per-time row, so the basis evaluation and the gather of first-layer weights
+        happen once per site; the rest of the network runs on the T*S rows.  Needs the window path (fixed
+        grid knots, compact-support basis) and p = 0; otherwise falls back to predict() on the expanded rows."""
+        self._refresh()
+        S, T = coords.shape[0], t_values.numel()
+        coords = coords.contiguous().float()
+        t_values = t_values.contiguous().float().view(-1)
+        Q = self.model.output_dim
+        out = torch.empty(T * S, Q, device=self.dev)
+        for _ in self._grid_chunks(coords, t_values, max_rows, lambda t0, n: out[t0 * S:(t0 + n) * S], self._fresh):
+            pass
         return out.view(T, S, Q)
 
     @torch.no_grad()
-    def predict(self, coords, t):
-        """coords (N,2), t (N,) or (N,1) on the device -> (N,Q)."""
+    def score_grid(self, coords, t_values, z, split=None, quantile_levels=None, interval=None, max_rows=None):
+        """predict_grid scored against the field on the device, without the grid: coords (S,2), t_values (T,),
+        z (T,S) float32 with NaN where the field has no value, split (T,S) uint8 codes 0..3 or None (all 0).  The
+        predictions of every chunk of time slices (at most `max_rows` rows, default as predict_grid) go into one
+        reused buffer and are reduced at once by stdadk_grid_score_f32; the (T*S, Q) tensor is never allocated.
+        Returns (split_acc (4, GRID_SLOTS), site_acc (4, S, 3), time_acc (4, T, 3)): float64 sums on the device, slots
+        as in include/stdadk.h, of the metric column Q // 2.  `quantile_levels` (Q levels) weigh the check-loss
+        slots (default 0.5 each); `interval=(lo_level, hi_level)` picks the cover / width columns from them.
+        The three tensors and the scratch belong to the predictor and are overwritten by its next score_grid call."""
+        if self.model.p != 0:
+            raise RuntimeError("Predictor: covariates (p>0) are not wired into the dense-grid path")
+        self._refresh()
+        S, T = coords.shape[0], t_values.numel()
+        coords = coords.contiguous().float()
+        t_values = t_values.contiguous().float().view(-1)
+        Q = self.model.output_dim
+        if tuple(z.shape) != (T, S) or (split is not None and tuple(split.shape) != (T, S)):
+            raise RuntimeError(f"score_grid: z and split must be (T, S) = {(T, S)}")
+        z = z.contiguous().float()
+        levels = [float(q) for q in quantile_levels] if quantile_levels is not None else None
+        if levels is not None and len(levels) != Q:
+            raise ValueError(f"score_grid: output_dim={Q} quantile levels expected, got {len(levels)}")
+        lo = hi = -1
+        if interval is not None:
+            if levels is None or any(float(v) not in levels for v in interval):
+                raise ValueError(f"score_grid: interval {interval} must name two of quantile_levels {levels}")
+            lo, hi = levels.index(float(interval[0])), levels.index(float(interval[1]))
+        split_acc = self._reused("split_acc", (4, N.GRID_SLOTS), torch.float64).zero_()
+        site_acc = self._reused("site_acc", (4, S, 3), torch.float64).zero_()
+        time_acc = self._reused("time_acc", (4, T, 3), torch.float64).zero_()
+        if S == 0 or T == 0:
+            return split_acc, site_acc, time_acc
+        per = min(self._slices_per_call(S, max_rows), T)
+        buf = self._reused("y", (per * S, Q))
+        ws = self._reused("grid_ws", (N.grid_score_workspace_bytes(S, per) // 8,), torch.float64)
+        for t0, n, y in self._grid_chunks(coords, t_values, max_rows, lambda t0, n: buf[:n * S], self._reused):
+            # the kernel ASSIGNS its chunk's time sums: straight into time_acc when one chunk is the grid
+            tacc = time_acc if per == T else self._reused("time_part" if n == per else "time_tail", (4, n, 3),
+                                                          torch.float64)
+            N.grid_score(y, z[t0:t0 + n], None if split is None else split[t0:t0 + n], Q // 2, levels, lo, hi,
+                         split_acc, site_acc, tacc, ws)
+            if per < T:
+                time_acc[:, t0:t0 + n] = tacc
+        return split_acc, site_acc, time_acc
+
+    @torch.no_grad()
+    def predict(self, coords, t, out=None):
+        """coords (N,2), t (N,) or (N,1) on the device -> (N,Q) (written into `out` when given)."""
         if self.model.p != 0:
             raise RuntimeError("Predictor: covariates (p>0) are not wired into the dense-grid path")
         self._refresh()
         n = coords.shape[0]
         coords = coords.contiguous().float()
         t = t.contiguous().float().view(-1)
-        out = torch.empty(n, self.model.output_dim, device=self.dev)
+        if out is None:
+            out = torch.empty(n, self.model.output_dim, device=self.dev)
         for s in range(0, n, self.chunk):
             B = min(self.chunk, n - s)
             here = (coords[s:s + B], t[s:s + B], out[s:s + B])

@@ -13,6 +13,9 @@ import numpy as np
 import torch
 
 NPZ_KEYS = ("predictions", "true", "coords", "train_mask", "valid_mask", "test_mask")
+SPLIT_NAMES = ("other", "train", "valid", "test")          # split codes 0..3 of grid_scores
+# slots per split of the sums behind grid_scores (the STDADK_GRID_* slots of include/stdadk.h)
+_G_N, _G_SSE, _G_SAE, _G_COVER, _G_WIDTH, _G_CHECK, _G_SLOTS = 0, 1, 2, 3, 4, 5, 16
 
 
 @torch.no_grad()
@@ -102,3 +105,152 @@ def evaluate_model(model, dataset, config=None, predictor=None):
         out["crps"] = float(compute_crps_multi_quantile(pred, obs, levels))
         out["mean_check_loss"] = out["check_loss"] = float(np.mean(per_level))      # the reference keeps both names
     return out
+
+
+def _grid_times(T):
+    return torch.arange(T, dtype=torch.float32) / (T - 1) if T > 1 else torch.zeros(1, dtype=torch.float32)
+
+
+def _grid_sums_host(pred, z, code, levels, lo, hi):
+    """The sums of stdadk_grid_score_f32 in numpy float64: pred (T, S, Q), z (T, S) with NaN = no value, code (T, S)."""
+    T, S, Q = pred.shape
+    pred = pred.astype(np.float64)
+    z = z.astype(np.float64)
+    fin = np.isfinite(z)
+    zz = np.where(fin, z, 0.0)
+    d = pred[:, :, Q // 2] - zz
+    split_acc, site_acc, time_acc = np.zeros((4, _G_SLOTS)), np.zeros((4, S, 3)), np.zeros((4, T, 3))
+    for c in range(4):
+        m = fin & (code == c)
+        terms = np.stack([np.where(m, d * d, 0.0), np.where(m, np.abs(d), 0.0), m.astype(np.float64)], axis=2)
+        site_acc[c], time_acc[c] = terms.sum(axis=0), terms.sum(axis=1)
+        split_acc[c, [_G_SSE, _G_SAE, _G_N]] = terms.sum(axis=(0, 1))
+        for q in range(Q):
+            tau = 0.5 if levels is None else levels[q]
+            e = zz - pred[:, :, q]
+            split_acc[c, _G_CHECK + q] = np.where(m, np.maximum((tau - 1.0) * e, tau * e), 0.0).sum()
+        if lo >= 0:
+            split_acc[c, _G_COVER] = (m & (pred[:, :, lo] <= zz) & (zz <= pred[:, :, hi])).sum()
+            split_acc[c, _G_WIDTH] = np.where(m, pred[:, :, hi] - pred[:, :, lo], 0.0).sum()
+    return split_acc, site_acc, time_acc
+
+
+def _ratio(num, den):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den > 0, num / np.where(den > 0, den, 1.0), np.nan)
+
+
+def _split_metrics(sums, kind, Q, interval):
+    n = sums[_G_N]
+    mse = float(_ratio(sums[_G_SSE], n))
+    out = {"mse": mse, "mae": float(_ratio(sums[_G_SAE], n)), "rmse": mse ** 0.5, "rows": int(n)}
+    checks = [float(_ratio(sums[_G_CHECK + q], n)) for q in range(Q)]
+    if kind == "quantile":
+        out["check_loss"] = checks[0]
+    elif kind == "multi-quantile":
+        # compute_crps_multi_quantile with its default weights: 2 x sum_k (1/K) x check loss at level k
+        out["crps"] = 2.0 * sum(c / Q for c in checks)
+        out["mean_check_loss"] = out["check_loss"] = sum(checks) / Q
+    if interval:
+        out["coverage"] = float(_ratio(sums[_G_COVER], n))
+        out["mean_width"] = float(_ratio(sums[_G_WIDTH], n))
+    return out
+
+
+@torch.no_grad()
+def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_mask=None, config=None, max_rows=None):
+    """What the reference's driver computes last (scripts/train_st_interp.py:1228-1252, :1378-1409, :2242): the (T, S)
+    prediction grid of `predict_all_times` (t = t_idx / (T - 1), 0 when T == 1; the median column Q // 2) against the
+    full field `z_full` (T, S; NaN = no value, such entries count nowhere), per split, per site and per time.
+
+    Device models never hold the grid: `Predictor.score_grid` reduces it chunk by chunk (at most `max_rows` rows)
+    into float64 sums on the device, read by the host ONCE.  Host models (`device: cpu`) run their own forward time
+    slice by time slice and sum in numpy float64.  (The device takes the quantile levels as float32.)
+
+    Masks are (T, S) booleans; an entry's split code is 1 / 2 / 3 for train / valid / test and 0 in none of them, and
+    where masks overlap the HIGHER code wins (test over valid over train).  `config`: `regression_type`,
+    `quantile_levels` / `current_quantile` as for evaluate_model, and optionally `interval = (lo_level, hi_level)`,
+    two of the quantile levels, for coverage and width.  Returns a dict:
+      splits            {name: metrics} for all / train / valid / test / other: evaluate_model's keys (mse, mae, rmse,
+                        check_loss, and crps, mean_check_loss for several levels) plus rows, and with an interval
+                        coverage, mean_width; NaN where a split has no finite entry
+      site_mse, site_mae, site_count   (S,) over all finite entries (the reference's nanmean), NaN / 0 for an empty site
+      time_mse, time_mae, time_count   (T,)
+      site_mse_by_split, time_mse_by_split   (4, .), rows in the order of the codes: other, train, valid, test"""
+    if getattr(model, "p", 0) != 0:
+        raise ValueError("grid_scores: the dense grid has no covariates (p must be 0)")
+    z = np.asarray(z_full.detach().cpu() if torch.is_tensor(z_full) else z_full)
+    if z.ndim != 2:
+        raise ValueError(f"grid_scores: z_full must be (T, S), got {z.shape}")
+    T, S = z.shape
+    code = np.zeros((T, S), dtype=np.uint8)
+    for c, mask in ((1, train_mask), (2, valid_mask), (3, test_mask)):
+        if mask is not None:
+            mask = np.asarray(mask.detach().cpu() if torch.is_tensor(mask) else mask, dtype=bool)
+            if mask.shape != (T, S):
+                raise ValueError(f"grid_scores: mask of split {SPLIT_NAMES[c]} has shape {mask.shape}, z_full {(T, S)}")
+            code[mask] = c
+    config = config or {}
+    kind = config.get("regression_type", "mean")
+    Q = int(model.output_dim)
+    levels = None
+    if kind == "multi-quantile":
+        levels = [float(q) for q in config.get("quantile_levels", [0.1, 0.5, 0.9])]
+    elif kind == "quantile" and "current_quantile" in config:
+        levels = [float(config["current_quantile"])]
+    if levels is not None and len(levels) != Q:
+        raise ValueError(f"grid_scores: the model has {Q} outputs, config names {len(levels)} quantile levels")
+    if kind == "quantile" and levels is None:
+        kind = "mean"
+    interval = config.get("interval")
+    lo = hi = -1
+    if interval is not None:
+        if levels is None or any(float(v) not in levels for v in interval):
+            raise ValueError(f"grid_scores: interval {interval} must name two of the quantile levels {levels}")
+        lo, hi = levels.index(float(interval[0])), levels.index(float(interval[1]))
+        if lo >= hi:
+            raise ValueError(f"grid_scores: interval {interval} must be (lower level, upper level)")
+    dev = next(model.parameters()).device
+    c = torch.as_tensor(np.asarray(coords) if not torch.is_tensor(coords) else coords).float().to(dev)
+    if tuple(c.shape) != (S, 2):
+        raise ValueError(f"grid_scores: coords must be ({S}, 2), got {tuple(c.shape)}")
+    tv = _grid_times(T)
+    was_training = model.training
+    model.eval()
+    try:
+        if dev.type == "cuda":
+            from ..engine import Predictor
+            accs = Predictor(model).score_grid(c, tv.to(dev), torch.from_numpy(z.astype(np.float32)).to(dev),
+                                               torch.from_numpy(code).to(dev), quantile_levels=levels,
+                                               interval=interval, max_rows=max_rows)
+            flat = torch.cat([a.reshape(-1) for a in accs]).cpu().numpy()              # the ONE host read
+            split_acc = flat[:4 * _G_SLOTS].reshape(4, _G_SLOTS)
+            site_acc = flat[4 * _G_SLOTS:4 * _G_SLOTS + 12 * S].reshape(4, S, 3)
+            time_acc = flat[4 * _G_SLOTS + 12 * S:].reshape(4, T, 3)
+        else:
+            pred = torch.stack([model(torch.zeros(S, 0), c, torch.full((S, 1), float(tv[i]))) for i in range(T)])
+            split_acc, site_acc, time_acc = _grid_sums_host(pred.double().numpy(), z, code, levels, lo, hi)
+    finally:
+        model.train(was_training)
+    out = {"splits": {"all": _split_metrics(split_acc.sum(axis=0), kind, Q, interval is not None)}}
+    for k in (1, 2, 3, 0):
+        out["splits"][SPLIT_NAMES[k]] = _split_metrics(split_acc[k], kind, Q, interval is not None)
+    for name, acc in (("site", site_acc), ("time", time_acc)):
+        tot = acc.sum(axis=0)
+        out[f"{name}_mse"], out[f"{name}_mae"] = _ratio(tot[:, 0], tot[:, 2]), _ratio(tot[:, 1], tot[:, 2])
+        out[f"{name}_count"] = tot[:, 2].astype(np.int64)
+        out[f"{name}_mse_by_split"] = _ratio(acc[:, :, 0], acc[:, :, 2])
+    return out
+
+
+def save_grid_scores_npz(output_dir, scores):
+    """Writes `<output_dir>/grid_scores.npz` from the dict of grid_scores and returns its path: the per-site and
+    per-time arrays under their own names, every split metric as the 0-d array `splits/<split>/<metric>`."""
+    arrs = {k: np.asarray(v) for k, v in scores.items() if k != "splits"}
+    for name, metrics in scores["splits"].items():
+        for k, v in metrics.items():
+            arrs[f"splits/{name}/{k}"] = np.asarray(v)
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(str(output_dir), "grid_scores.npz")
+    np.savez(path, **arrs)
+    return path
