@@ -494,20 +494,21 @@ static int check_desc(const stdadk_mlp_desc *d) {
   return 0;
 }
 
-struct Ctx;
+// the default objective: plain MSE against y [B,Q] (y_cols 0 = Q), every quantile level 0.5
+static const LossDev LOSS_PLAIN_MSE = {STDADK_LOSS_MSE, 0, {0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f}, 0.f, 1};
+
 struct Ctx {
-  const stdadk_mlp_desc *d;
-  const stdadk_mlp_tensors *P;
-  const stdadk_mlp_tensors *G;
-  float *ws;
-  Plan pl;
-  hipStream_t st;
-  int64_t B;
-  bool w0t;             // W[0] / dW[0] stored (in,out)
-  float dp;             // effective dropout probability (0 in eval)
-  uint64_t seed;
-  const int *step_dev;
-  const uint8_t *const *masks;
+  const stdadk_mlp_desc *d = nullptr;
+  const stdadk_mlp_tensors *P = nullptr, *G = nullptr;
+  float *ws = nullptr;
+  Plan pl = {};
+  hipStream_t st = nullptr;
+  int64_t B = 0;
+  bool w0t = false;     // W[0] / dW[0] stored (in,out)
+  float dp = 0.f;       // effective dropout probability (0 in eval)
+  uint64_t seed = 0;
+  const int *step_dev = nullptr;
+  const uint8_t *const *masks = nullptr;
   // fused MSE (tail path): targets in the row order of the activations; outputs optional
   const float *mse_y = nullptr;
   float mse_scale = 0.f;
@@ -517,7 +518,7 @@ struct Ctx {
   // fused training step: run_forward parks the tail launch here and run_backward issues it together
   // with the backward chain as ONE kernel (the tail of a row tile is row-local through the loss)
   bool fuse_tail = false, pend_valid = false;
-  TailFwdArgs pend;
+  TailFwdArgs pend = {};
   // whole-step entry (stdadk_train_step_f32): squared-norm partials of the gradient ride along with the
   // reductions launch when every gradient is produced by it or by the per-knot gather
   float *gradsq = nullptr;      // [STDADK_GRADSQ_PARTS] or NULL
@@ -528,13 +529,13 @@ struct Ctx {
   bool merge_dw = false, dw_pend = false;   // window path: grouped dW products + per-knot gather as one launch
   int fin = 0;                  // ... 2: which also does the reductions (FinArgs; the tail launch cleared the counters);
                                 // 1: which leaves the squared-norm slots of its knot rows, reductions launch behind it
-  GemmGroup gg_pend;
-  ReduceGroup rg_pend;
+  GemmGroup gg_pend = {};
+  ReduceGroup rg_pend = {};
   // one-call step that announces its NEXT batch: the merged dW launch bins it when it is what the step runs
   const BinSmallArgs *bin_next = nullptr;
   bool bin_next_done = false;
   bool l1_pend_valid = false;   // window path, B <= 4096: the layer-0 launch is parked as well
-  L1FwdArgs l1_pend;
+  L1FwdArgs l1_pend = {};
   int l1_basis = 0;
   // materialising path, small D: layer 0 starts inside the tail launch from the raw observations (TailDense0)
   bool d0 = false;
@@ -546,19 +547,51 @@ struct Ctx {
   bool log_bw = false;          // basis->s_bw holds log-bandwidths (learnable knots)
   const int64_t *idx = nullptr; // window path: the batch is rows idx[b] of the resident observation arrays
   bool prebinned = false;       // window path: stdadk_bin_batch_f32 already filled the workspace's bins
-  LossDev loss = {STDADK_LOSS_MSE, 0, {0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f}, 0.f, 1};   // y_cols 0 = Q
+  LossDev loss = LOSS_PLAIN_MSE;
   const float *dz0 = nullptr;   // set by run_backward: dZ of layer 0
   // optional second stream: independent kernels of a step fork onto it (hipGraph-capturable
   // fork/join through events); NULL = everything on `st`
   hipStream_t aux = nullptr;
   int (*fork_after_dz)(Ctx &) = nullptr;   // called by run_backward (fused tail) right after the dZ kernel
   const stdadk_basis_desc *basis = nullptr;
-  const stdadk_basis_desc *basis_in = nullptr;   // set by step_common (scattered_bins reads the log-bandwidths)
+  const stdadk_basis_desc *basis_in = nullptr;   // set by open_step (scattered_bins reads the log-bandwidths)
   bool dw0_forked = false;        // the per-knot gather of dW0^T was forked onto the auxiliary stream
   // extra products C[M][H0] = A^T dZ_0 (reduction over the batch) to run with the dW GEMMs of the
   // fused-tail backward: the temporal / covariate rows of dW0^T on the window path
   int n_extra = 0;
-  struct { const float *A; int64_t lda; int M; float *C; } extra[2];
+  struct { const float *A; int64_t lda; int M; float *C; } extra[2] = {};
+};
+
+// One description of a training step call: what the public doors take positionally, by name
+struct StepCall {
+  const stdadk_basis_desc *b = nullptr;
+  const stdadk_mlp_desc *d = nullptr;
+  const stdadk_mlp_tensors *P = nullptr, *G = nullptr;
+  const float *coords = nullptr, *t = nullptr, *X = nullptr, *y = nullptr;   // the batch: these arrays, or with `idx`
+  const int64_t *idx = nullptr;                                              // (window path) their rows idx[0..B)
+  int64_t B = 0;
+  float grad_scale = 0.f;
+  const stdadk_loss_desc *loss = nullptr;
+  float *loss_sum = nullptr, *y_pred = nullptr;
+  void *workspace = nullptr;
+  size_t workspace_bytes = 0;
+  uint64_t drop_seed = 0;
+  const int32_t *step_dev = nullptr;
+  int32_t flags = 0;
+  stdadk_stream_t stream = nullptr, aux_stream = nullptr;
+};
+// StepRide: what the one-call step lets ride along with its launches -- squared-norm partials of the gradient with the step
+// counter their launch advances, the next batch for the merged dW launch to bin; StepOut: where the partials went (NULL:
+// no launch left them) and whether that batch is binned
+struct StepRide { float *gradsq_parts = nullptr; int32_t *step_inc = nullptr; const BinSmallArgs *bin_next = nullptr; };
+struct StepOut { const float *sq_parts = nullptr; int sq_n = 0; bool binned_next = false; };
+struct NextBatch {   // the batch a one-call step announces (stdadk_train_step_next_f32)
+  const int64_t *idx = nullptr;
+  int64_t B = 0;
+  int32_t y_cols = 0;
+  void *workspace = nullptr;
+  size_t workspace_bytes = 0;
+  int32_t *binned = nullptr;   // set to 1 once the batch sits binned in `workspace`
 };
 
 // fork/join between the main and the auxiliary stream (events are created once per thread)
@@ -592,19 +625,27 @@ static bool tail_enabled() {
   return v != 0;
 }
 
-static TailLayer tail_layer(const Ctx &c, int l) {
+// layer l of the model as the tail kernels take it: saving nothing (xhat, rstd, act NULL), or into the workspace of `c`
+static TailLayer tail_layer(const stdadk_mlp_desc *d, const stdadk_mlp_tensors *P, bool bf16, int l) {
   TailLayer t;
-  const stdadk_mlp_desc *d = c.d;
-  t.W = c.P->W[l]; t.b = c.P->b[l];
-  t.Wbf = c.bf16 ? c.P->W_bf16[l] : nullptr;
-  t.WTbf = c.bf16 ? c.P->WT_bf16[l] : nullptr;
-  t.g = d->layernorm ? c.P->ln_g[l] : nullptr;
-  t.be = d->layernorm ? c.P->ln_b[l] : nullptr;
-  t.h = d->hidden[l];
-  t.hp = l > 0 ? d->hidden[l - 1] : d->in_dim;
-  t.xhat = c.ws + c.pl.xhat[l]; t.rstd = c.ws + c.pl.rstd[l]; t.act = c.ws + c.pl.act[l];
+  t.W = P->W[l]; t.b = P->b[l];
+  t.Wbf = bf16 ? P->W_bf16[l] : nullptr; t.WTbf = bf16 ? P->WT_bf16[l] : nullptr;
+  t.g = d->layernorm ? P->ln_g[l] : nullptr; t.be = d->layernorm ? P->ln_b[l] : nullptr;
+  t.h = d->hidden[l]; t.hp = l > 0 ? d->hidden[l - 1] : d->in_dim;
+  t.xhat = t.rstd = t.act = nullptr;
   t.layer_id = l;
   return t;
+}
+static TailLayer tail_layer(const Ctx &c, int l) {
+  TailLayer t = tail_layer(c.d, c.P, c.bf16, l);
+  t.xhat = c.ws + c.pl.xhat[l]; t.rstd = c.ws + c.pl.rstd[l]; t.act = c.ws + c.pl.act[l];
+  return t;
+}
+// what a tail forward launch takes from the model alone: output layer, Q, LayerNorm; no loss, the default objective
+static void tail_fwd_model(TailFwdArgs &a, const stdadk_mlp_desc *d, const stdadk_mlp_tensors *P) {
+  a.Wo = P->W[d->n_hidden]; a.bo = P->b[d->n_hidden]; a.Q = d->out_dim;
+  a.layernorm = d->layernorm; a.eps = d->ln_eps;
+  a.y = nullptr; a.grad_scale = 0.f; a.dY = nullptr; a.loss_sum = nullptr; a.loss = LOSS_PLAIN_MSE; a.loss.y_cols = a.Q;
 }
 
 // one hidden layer with the generic kernels: z = in W^T (+b) -> LN -> ReLU -> Dropout
@@ -688,12 +729,12 @@ static int run_forward(Ctx &c, int l0, const float *in, int64_t ld_in, int K, fl
     a.a_in = ws + pl.act[l - 1];
     a.h_in = d->hidden[l - 1];
     a.B = (int)B;
-    a.Wo = P->W[L]; a.bo = P->b[L]; a.Q = Q;
+    tail_fwd_model(a, d, P);
     a.y_pred = y_pred;
     a.y = c.mse_y; a.grad_scale = c.mse_scale; a.dY = c.mse_dY; a.loss_sum = c.mse_loss;
     a.loss = c.loss;
     if (a.loss.y_cols == 0) a.loss.y_cols = Q;
-    a.layernorm = d->layernorm; a.eps = d->ln_eps; a.drop_p = c.dp; a.seed = c.seed; a.step_dev = c.step_dev;
+    a.drop_p = c.dp; a.seed = c.seed; a.step_dev = c.step_dev;
     a.bf16 = c.bf16 ? 1 : 0;
     c.cap32 = c.bf16 && a.d0.on != 0;
     c.mse_done = c.mse_y != nullptr;
@@ -1104,6 +1145,17 @@ static int window_layer0_forward(Ctx &c, const stdadk_basis_desc *b, const float
   return l1_window_forward(a, b->basis, c.d->layernorm != 0, c.st);
 }
 
+// The opener of the two stdadk_mlp_*_f32 doors: plans and fills `c`; false = workspace too small (worded by the door)
+static bool open_mlp(Ctx &c, const stdadk_mlp_desc *d, int64_t B, void *workspace, size_t workspace_bytes,
+                     const stdadk_mlp_tensors *P, const stdadk_mlp_tensors *G, stdadk_stream_t stream, bool training,
+                     uint64_t drop_seed, const uint8_t *const *drop_mask) {
+  make_plan(d, B, &c.pl);
+  if (workspace_bytes < c.pl.total_floats * sizeof(float)) return false;
+  c.d = d; c.P = P; c.G = G; c.ws = (float *)workspace; c.st = (hipStream_t)stream; c.B = B;
+  c.dp = training ? d->dropout_p : 0.f; c.seed = drop_seed; c.masks = drop_mask;
+  return true;
+}
+
 }  // namespace stdadk
 
 using namespace stdadk;
@@ -1130,12 +1182,9 @@ extern "C" int stdadk_mlp_forward_f32(const stdadk_mlp_desc *d, const stdadk_mlp
   STDADK_REQUIRE(ldf >= d->in_dim, STDADK_E_SHAPE, "mlp_forward: ldf %lld < in_dim %d", (long long)ldf, d->in_dim);
   STDADK_REQUIRE(aligned16(workspace), STDADK_E_ALIGN, "mlp_forward: workspace must be 16-byte aligned");
   Ctx c;
-  make_plan(d, B, &c.pl);
-  STDADK_REQUIRE(workspace_bytes >= c.pl.total_floats * sizeof(float), STDADK_E_WORKSPACE,
-                 "mlp_forward: workspace %zu < %zu bytes", workspace_bytes, c.pl.total_floats * sizeof(float));
-  c.d = d; c.P = P; c.G = nullptr; c.ws = (float *)workspace; c.st = (hipStream_t)stream; c.B = B;
-  c.w0t = false; c.dp = training ? d->dropout_p : 0.f; c.seed = drop_seed; c.step_dev = nullptr;
-  c.masks = drop_mask;
+  STDADK_REQUIRE(open_mlp(c, d, B, workspace, workspace_bytes, P, nullptr, stream, training != 0, drop_seed, drop_mask),
+                 STDADK_E_WORKSPACE, "mlp_forward: workspace %zu < %zu bytes", workspace_bytes,
+                 c.pl.total_floats * sizeof(float));
   return run_forward(c, 0, features, ldf, d->in_dim, y_pred);
 }
 
@@ -1150,11 +1199,8 @@ extern "C" int stdadk_mlp_backward_f32(const stdadk_mlp_desc *d, const stdadk_ml
   STDADK_REQUIRE(P && G && features && dY && workspace, STDADK_E_ARG, "mlp_backward: NULL pointer");
   STDADK_REQUIRE(ldf >= d->in_dim, STDADK_E_SHAPE, "mlp_backward: ldf < in_dim");
   Ctx c;
-  make_plan(d, B, &c.pl);
-  STDADK_REQUIRE(workspace_bytes >= c.pl.total_floats * sizeof(float), STDADK_E_WORKSPACE,
-                 "mlp_backward: workspace too small");
-  c.d = d; c.P = P; c.G = G; c.ws = (float *)workspace; c.st = (hipStream_t)stream; c.B = B;
-  c.w0t = false; c.dp = d->dropout_p; c.seed = drop_seed; c.step_dev = nullptr; c.masks = drop_mask;
+  STDADK_REQUIRE(open_mlp(c, d, B, workspace, workspace_bytes, P, G, stream, true, drop_seed, drop_mask),
+                 STDADK_E_WORKSPACE, "mlp_backward: workspace too small");
   return run_backward(c, dY, features, ldf, true);
 }
 
@@ -1188,8 +1234,12 @@ extern "C" size_t stdadk_step_workspace_bytes(const stdadk_basis_desc *b, const 
   return p.total_floats * sizeof(float);
 }
 
-static int step_common(Ctx &c, const stdadk_basis_desc *b, const stdadk_mlp_desc *d, int64_t B, void *workspace,
-                       size_t workspace_bytes, int32_t flags, bool *window) {
+// The one opener of a step-level Ctx: validates descriptors, batch size, workspace and flags, plans, fills `c` (`training`
+// false: no dropout, nothing kept for a backward).  P and G are stored unchecked: each door refuses NULLs in its own words.
+static int open_step(Ctx &c, const stdadk_basis_desc *b, const stdadk_mlp_desc *d, int64_t B, void *workspace,
+                     size_t workspace_bytes, int32_t flags, bool *window, const stdadk_mlp_tensors *P,
+                     const stdadk_mlp_tensors *G, stdadk_stream_t stream, bool training, uint64_t drop_seed = 0,
+                     const int32_t *step_dev = nullptr) {
   int rc = check_desc(d);
   if (rc) return rc;
   rc = check_basis(b, d);
@@ -1208,10 +1258,9 @@ static int step_common(Ctx &c, const stdadk_basis_desc *b, const stdadk_mlp_desc
                  TAIL_MAX_W, TAIL_MAXQ);
   STDADK_REQUIRE(workspace_bytes >= c.pl.total_floats * sizeof(float), STDADK_E_WORKSPACE,
                  "step: workspace %zu < %zu bytes", workspace_bytes, c.pl.total_floats * sizeof(float));
-  c.d = d; c.ws = (float *)workspace; c.B = B;
-  c.basis_in = b;
-  c.w0t = (flags & STDADK_FLAG_W0_T) != 0;
-  c.masks = nullptr;
+  c.d = d; c.P = P; c.G = G; c.ws = (float *)workspace; c.st = (hipStream_t)stream; c.B = B;
+  c.basis_in = b; c.w0t = (flags & STDADK_FLAG_W0_T) != 0;
+  c.dp = training ? d->dropout_p : 0.f; c.seed = drop_seed; c.step_dev = step_dev; c.save = training;
   c.prebinned = *window && (flags & STDADK_FLAG_PREBINNED) != 0;
   STDADK_REQUIRE(*window || !(flags & STDADK_FLAG_PREBINNED), STDADK_E_ARG,
                  "step: STDADK_FLAG_PREBINNED needs the window path");
@@ -1402,13 +1451,11 @@ extern "C" int stdadk_forward_f32(const stdadk_basis_desc *b, const stdadk_mlp_d
   if (B == 0) return 0;
   Ctx c;
   bool window;
-  int rc = step_common(c, b, d, B, workspace, workspace_bytes, flags, &window);
+  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags, &window, P, nullptr, stream, training != 0, drop_seed,
+                     step_dev);
   if (rc) return rc;
   STDADK_REQUIRE(P && coords && t && y_pred, STDADK_E_ARG, "forward: NULL pointer");
   STDADK_REQUIRE(b->p == 0 || X, STDADK_E_ARG, "forward: X is NULL with p=%d", b->p);
-  c.P = P; c.G = nullptr; c.st = (hipStream_t)stream;
-  c.dp = training ? d->dropout_p : 0.f; c.seed = drop_seed; c.step_dev = step_dev;
-  c.save = training != 0;
   return step_forward(c, b, window, coords, t, X, nullptr, y_pred, stream);
 }
 
@@ -1435,13 +1482,13 @@ extern "C" int stdadk_spatial_partial_f32(const stdadk_basis_desc *b, const stda
   if (S == 0) return 0;
   Ctx c;
   bool window;
-  int rc = step_common(c, b, d, S, workspace, workspace_bytes, flags, &window);
+  // (`training` false: this door reads neither dp nor save)
+  int rc = open_step(c, b, d, S, workspace, workspace_bytes, flags, &window, P, nullptr, stream, false);
   if (rc) return rc;
   STDADK_REQUIRE(window && !(flags & STDADK_FLAG_LOG_BW), STDADK_E_ARG,
                  "spatial_partial: needs the window path with fixed grid knots (compact-support basis, W0 stored (in,out))");
   STDADK_REQUIRE(b->p == 0, STDADK_E_ARG, "spatial_partial: covariates are per (site, time) row; p must be 0");
   STDADK_REQUIRE(P && P->W[0] && P->b[0] && coords && out, STDADK_E_ARG, "spatial_partial: NULL pointer");
-  c.P = P; c.st = (hipStream_t)stream;
   const Plan &pl = c.pl;
   BinBuffers bb = plan_bins(c.ws, pl);
   // the sites' x coordinates stand in for the (unused) time column of the binning
@@ -1489,38 +1536,25 @@ extern "C" int stdadk_forward_parts_f32(const stdadk_mlp_desc *d, const stdadk_m
   if (S == 0 || T == 0) return 0;
   int rc = check_desc(d);
   if (rc) return rc;
-  const int L = d->n_hidden, Q = d->out_dim;
+  const int L = d->n_hidden;
   STDADK_REQUIRE(P && sp && tp && y_pred && S * T < (1ll << 31), STDADK_E_ARG, "forward_parts: bad argument");
   STDADK_REQUIRE(L >= 1 && tail_supported(d, 1) && P->W[L] && P->b[L], STDADK_E_ARG,
                  "forward_parts: hidden widths must be multiples of 16 up to %d, out_dim <= %d", TAIL_MAX_W, TAIL_MAXQ);
-  auto layer = [&](int l) {
-    TailLayer tl;
-    tl.W = P->W[l]; tl.b = P->b[l];
-    tl.Wbf = P->W_bf16[l]; tl.WTbf = P->WT_bf16[l];
-    tl.g = d->layernorm ? P->ln_g[l] : nullptr; tl.be = d->layernorm ? P->ln_b[l] : nullptr;
-    tl.h = d->hidden[l]; tl.hp = l > 0 ? d->hidden[l - 1] : d->in_dim;
-    tl.xhat = tl.rstd = tl.act = nullptr;
-    tl.layer_id = l;
-    return tl;
-  };
   TailFwdArgs a;
   a.n_layers = L - 1;
   for (int l = 1; l < L; ++l) {
     STDADK_REQUIRE(P->W[l] && P->b[l] && (!d->layernorm || (P->ln_g[l] && P->ln_b[l])), STDADK_E_ARG,
                    "forward_parts: layer %d parameters NULL", l);
-    a.L[l - 1] = layer(l);
+    a.L[l - 1] = tail_layer(d, P, true, l);
   }
   STDADK_REQUIRE(P->b[0] && (!d->layernorm || (P->ln_g[0] && P->ln_b[0])), STDADK_E_ARG, "forward_parts: layer 0 parameters NULL");
   a.d0.on = 2; a.d0.sp = sp; a.d0.tp = tp; a.d0.S = (int)S;
-  a.d0.L0 = layer(0);
+  a.d0.L0 = tail_layer(d, P, true, 0);
   a.a_in = nullptr; a.h_in = d->hidden[0];
   a.B = (int)(S * T);
-  a.Wo = P->W[L]; a.bo = P->b[L]; a.Q = Q;
+  tail_fwd_model(a, d, P);
   a.y_pred = y_pred;
-  a.y = nullptr; a.grad_scale = 0.f; a.dY = nullptr; a.loss_sum = nullptr;
-  a.loss = LossDev{STDADK_LOSS_MSE, Q, {0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f}, 0.f, 1};
-  a.layernorm = d->layernorm; a.eps = d->ln_eps; a.drop_p = 0.f; a.seed = 0; a.step_dev = nullptr;
-  a.stamps = nullptr;
+  a.drop_p = 0.f; a.seed = 0; a.step_dev = nullptr; a.stamps = nullptr;
   // bf16 operands whenever the caller supplies the copies of every layer after the first
   a.bf16 = L > 1 ? 1 : 0;
   for (int l = 1; l < L; ++l) if (!P->W_bf16[l]) a.bf16 = 0;
@@ -1535,10 +1569,9 @@ extern "C" int stdadk_backward_f32(const stdadk_basis_desc *b, const stdadk_mlp_
   if (B == 0) return 0;
   Ctx c;
   bool window;
-  int rc = step_common(c, b, d, B, workspace, workspace_bytes, flags, &window);
+  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags, &window, P, G, stream, true, drop_seed, step_dev);
   if (rc) return rc;
   STDADK_REQUIRE(P && G && dY, STDADK_E_ARG, "backward: NULL pointer");
-  c.P = P; c.G = G; c.st = (hipStream_t)stream; c.dp = d->dropout_p; c.seed = drop_seed; c.step_dev = step_dev;
   return step_backward(c, b, window, dY, false);
 }
 
@@ -1550,7 +1583,8 @@ extern "C" int stdadk_knot_backward_f32(const stdadk_basis_desc *b, const stdadk
   if (B == 0) return 0;
   Ctx c;
   bool window;
-  int rc = step_common(c, b, d, B, workspace, workspace_bytes, flags, &window);
+  // (`training` false: this door reads neither dp nor save)
+  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags, &window, P, nullptr, stream, false);
   if (rc) return rc;
   STDADK_REQUIRE((flags & STDADK_FLAG_LOG_BW), STDADK_E_ARG,
                  "knot_backward: needs STDADK_FLAG_LOG_BW (the state of a learnable-knot forward/backward)");
@@ -1563,7 +1597,7 @@ extern "C" int stdadk_knot_backward_f32(const stdadk_basis_desc *b, const stdadk
     STDADK_REQUIRE(kt->domain_weight >= 0.f && kt->movement_weight >= 0.f, STDADK_E_ARG,
                    "knot_backward: negative penalty weight");
   }
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = c.st;
   float *ws = c.ws;
   const int H = d->hidden[0];
   KnotFinishArgs fa;
@@ -1596,104 +1630,77 @@ extern "C" int stdadk_knot_backward_f32(const stdadk_basis_desc *b, const stdadk
   return launch_knot_finish(fa, st);
 }
 
-static int train_fwd_bwd_impl(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
-                              const stdadk_mlp_tensors *P, const stdadk_mlp_tensors *G,
-                              const float *coords, const float *t, const float *X,
-                              const float *y, const int64_t *idx, int64_t B, float grad_scale,
-                              const stdadk_loss_desc *loss, float *loss_sum,
-                              float *y_pred, void *workspace, size_t workspace_bytes,
-                              uint64_t drop_seed, const int32_t *step_dev, int32_t flags,
-                              stdadk_stream_t stream, stdadk_stream_t aux_stream,
-                              float *gradsq_parts = nullptr, int32_t *step_inc = nullptr,
-                              const float **gradsq_out = nullptr, int *gradsq_n = nullptr,
-                              const BinSmallArgs *bin_next = nullptr, bool *bin_next_done = nullptr) {
-  if (bin_next_done) *bin_next_done = false;
-  if (B == 0) return 0;
-  Ctx c;
-  c.gradsq = gradsq_parts; c.step_inc = step_inc;
-  c.bin_next = bin_next;
-  struct Done {
-    Ctx &c; const float **out; int *n; bool *bin;
-    ~Done() {
-      if (out) { *out = c.gradsq_done ? c.gradsq_out : nullptr; *n = c.gradsq_done ? c.gradsq_n : 0; }
-      if (bin) *bin = c.bin_next_done;
-    }
-  } done_guard{c, gradsq_out, gradsq_n, bin_next_done};
-  bool window;
-  int rc = step_common(c, b, d, B, workspace, workspace_bytes, flags, &window);
-  if (rc) return rc;
-  STDADK_REQUIRE(!idx || window, STDADK_E_ARG,
-                 "train_fwd_bwd_indexed: only the window path gathers in place; use stdadk_gather_batch_f32 + "
-                 "stdadk_train_fwd_bwd_f32 for the materialising path");
-  c.idx = idx;
-  STDADK_REQUIRE(P && G && (c.prebinned || (coords && t && y)), STDADK_E_ARG, "train_fwd_bwd: NULL pointer");
-  c.aux = (aux_stream && aux_stream != stream) ? (hipStream_t)aux_stream : nullptr;
-  STDADK_REQUIRE(b->p == 0 || X || c.prebinned, STDADK_E_ARG, "train_fwd_bwd: X is NULL with p=%d", b->p);
-  c.P = P; c.G = G; c.st = (hipStream_t)stream; c.dp = d->dropout_p; c.seed = drop_seed; c.step_dev = step_dev;
-  rc = make_loss(loss, d->out_dim, &c.loss);
-  if (rc) return rc;
-  const bool plain = loss_is_plain_mse(c.loss, d->out_dim);
-  const int64_t n = B * d->out_dim;
-  c.mse_scale = grad_scale; c.mse_dY = c.ws + c.pl.dY; c.mse_loss = loss_sum;
-  // one launch for the forward and backward chains of the tail when nothing has to read the
-  // predictions in between (window path: the un-permute of y_pred) and the loss is fused
-  c.fuse_tail = getenv("STDADK_NO_TAIL_FWD_BWD") == nullptr && !(window && y_pred);
-  if (window) {
-    // everything between the binning and the weight gradients stays in sorted order
-    c.mse_y = c.ws + c.pl.y_s;
-    rc = step_forward(c, b, true, coords, t, X, y, y_pred, stream);
-    if (rc) return rc;
-    if (!c.mse_done) {
-      rc = plain ? launch_mse(c.ws + c.pl.ypred, c.ws + c.pl.y_s, n, grad_scale, c.ws + c.pl.dY, loss_sum, c.st)
-                 : launch_loss(c.loss, c.ws + c.pl.ypred, c.ws + c.pl.y_s, B, d->out_dim, grad_scale,
-                               c.ws + c.pl.dY, loss_sum, c.st);
-      if (rc) return rc;
-    }
-    rc = step_backward(c, b, true, c.ws + c.pl.dY, true);
-    STDADK_REQUIRE(rc || (!c.pend_valid && !c.l1_pend_valid), STDADK_E_ARG,
-                   "train_fwd_bwd: a parked launch was never issued");
-    return rc;
-  }
-  float *yp = y_pred ? y_pred : c.ws + c.pl.ypred;
-  c.mse_y = y;
-  rc = step_forward(c, b, false, coords, t, X, nullptr, yp, stream);
-  if (rc) return rc;
-  if (!c.mse_done) {
-    rc = plain ? launch_mse(yp, y, n, grad_scale, c.ws + c.pl.dY, loss_sum, c.st)
-               : launch_loss(c.loss, yp, y, B, d->out_dim, grad_scale, c.ws + c.pl.dY, loss_sum, c.st);
-    if (rc) return rc;
-  }
-  rc = step_backward(c, b, false, c.ws + c.pl.dY, false);
-  STDADK_REQUIRE(rc || !c.pend_valid, STDADK_E_ARG, "train_fwd_bwd: the parked tail launch was never issued");
-  return rc;
+// where a step's predictions land: the plan's buffer (window path: sorted order, y_pred gets the un-permuted copy)
+static float *pred_buffer(const Ctx &c, bool window, float *y_pred) { return (window || !y_pred) ? c.ws + c.pl.ypred : y_pred; }
+
+// the loss of a step on predictions `yp`, unless the tail launch fused it: c.mse_y -> c.mse_dY / c.mse_loss, as the tail does
+static int launch_step_loss(const Ctx &c, const float *yp) {
+  const int Q = c.d->out_dim;
+  if (c.mse_done) return 0;
+  if (loss_is_plain_mse(c.loss, Q)) return launch_mse(yp, c.mse_y, c.B * Q, c.mse_scale, c.mse_dY, c.mse_loss, c.st);
+  return launch_loss(c.loss, yp, c.mse_y, c.B, Q, c.mse_scale, c.mse_dY, c.mse_loss, c.st);
 }
 
-static int train_step_impl(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
-                           const stdadk_mlp_tensors *P, const stdadk_mlp_tensors *G,
-                           const float *coords, const float *t, const float *X, const float *y,
-                           const int64_t *idx, int64_t B, float grad_scale,
-                           const stdadk_loss_desc *loss, const stdadk_sparsity_desc *sparsity,
-                           float *loss_sum, void *workspace, size_t workspace_bytes,
-                           uint64_t drop_seed, int32_t flags, const stdadk_optim_desc *o,
-                           stdadk_stream_t stream, const int64_t *next_idx, int64_t next_B, int32_t next_y_cols,
-                           void *next_workspace, size_t next_workspace_bytes, int32_t *next_binned) {
-  if (next_binned) *next_binned = 0;
+// forward, loss and backward of one batch; `ride` / `out`: one-call step only (an error return leaves {NULL, 0, false})
+static int train_fwd_bwd_impl(const StepCall &s, const StepRide *ride, StepOut *out) {
+  if (out) *out = StepOut{};
+  if (s.B == 0) return 0;
+  const stdadk_basis_desc *b = s.b;
+  Ctx c;
+  if (ride) { c.gradsq = ride->gradsq_parts; c.step_inc = ride->step_inc; c.bin_next = ride->bin_next; }
+  bool window;
+  int rc = open_step(c, b, s.d, s.B, s.workspace, s.workspace_bytes, s.flags, &window, s.P, s.G, s.stream, true,
+                     s.drop_seed, s.step_dev);
+  if (rc) return rc;
+  STDADK_REQUIRE(!s.idx || window, STDADK_E_ARG,
+                 "train_fwd_bwd_indexed: only the window path gathers in place; use stdadk_gather_batch_f32 + "
+                 "stdadk_train_fwd_bwd_f32 for the materialising path");
+  c.idx = s.idx;
+  STDADK_REQUIRE(s.P && s.G && (c.prebinned || (s.coords && s.t && s.y)), STDADK_E_ARG, "train_fwd_bwd: NULL pointer");
+  c.aux = (s.aux_stream && s.aux_stream != s.stream) ? (hipStream_t)s.aux_stream : nullptr;
+  STDADK_REQUIRE(b->p == 0 || s.X || c.prebinned, STDADK_E_ARG, "train_fwd_bwd: X is NULL with p=%d", b->p);
+  rc = make_loss(s.loss, s.d->out_dim, &c.loss);
+  if (rc) return rc;
+  // window path: predictions, targets and dY stay in sorted order between the binning and the weight gradients
+  float *yp = pred_buffer(c, window, s.y_pred);
+  c.mse_y = window ? c.ws + c.pl.y_s : s.y; c.mse_scale = s.grad_scale; c.mse_dY = c.ws + c.pl.dY; c.mse_loss = s.loss_sum;
+  // one launch for the forward and backward chains of the tail when nothing has to read the
+  // predictions in between (window path: the un-permute of y_pred) and the loss is fused
+  c.fuse_tail = getenv("STDADK_NO_TAIL_FWD_BWD") == nullptr && !(window && s.y_pred);
+  rc = step_forward(c, b, window, s.coords, s.t, s.X, s.y, window ? s.y_pred : yp, s.stream);
+  if (rc) return rc;
+  rc = launch_step_loss(c, yp);
+  if (rc) return rc;
+  rc = step_backward(c, b, window, c.mse_dY, window);
+  if (rc) return rc;
+  STDADK_REQUIRE(!window || (!c.pend_valid && !c.l1_pend_valid), STDADK_E_ARG, "train_fwd_bwd: a parked launch was never issued");
+  STDADK_REQUIRE(window || !c.pend_valid, STDADK_E_ARG, "train_fwd_bwd: the parked tail launch was never issued");
+  if (out) *out = {c.gradsq_done ? c.gradsq_out : nullptr, c.gradsq_done ? c.gradsq_n : 0, c.bin_next_done};
+  return 0;
+}
+
+// forward / backward of `s`, sparsity penalty, clip norm, AdamW + EMA; `nb`, when complete, is binned along the way
+static int train_step_impl(StepCall s, const stdadk_sparsity_desc *sparsity, const stdadk_optim_desc *o,
+                           const NextBatch &nb) {
+  const stdadk_basis_desc *b = s.b; const stdadk_mlp_desc *d = s.d;
+  if (nb.binned) *nb.binned = 0;
   STDADK_REQUIRE(o && o->p && o->g && o->m && o->v && o->n > 0 && o->step_dev, STDADK_E_ARG,
                  "train_step: optimiser descriptor incomplete");
   STDADK_REQUIRE(o->max_norm <= 0.f || o->sumsq_parts, STDADK_E_ARG, "train_step: max_norm > 0 needs sumsq_parts");
-  if (B == 0) return 0;
+  if (s.B == 0) return 0;
+  s.step_dev = o->step_dev;
   // the NEXT batch is validated and planned before anything of this step is enqueued: a call that fails on it
   // leaves the parameters, moments, EMA, step counter and loss sum as they were
   Ctx cn;
   bool bin_next = false;
-  if (next_idx && next_B > 0 && next_workspace && next_binned) {
+  if (nb.idx && nb.B > 0 && nb.workspace && nb.binned) {
     bool window_n = false;
-    int rc = step_common(cn, b, d, next_B, next_workspace, next_workspace_bytes, flags & ~STDADK_FLAG_PREBINNED,
-                         &window_n);
+    int rc = open_step(cn, b, d, nb.B, nb.workspace, nb.workspace_bytes, s.flags & ~STDADK_FLAG_PREBINNED, &window_n, nullptr,
+                       nullptr, s.stream, false);   // planned only: cn.pl and cn.ws are read
     if (rc) return rc;
-    bin_next = window_n && bin_small_eligible((int)next_B, cn.pl.G) && coords && t && (b->p == 0 || X);
-    STDADK_REQUIRE(!bin_next || (next_y_cols >= 0 && next_y_cols <= d->out_dim && (next_y_cols == 0 || y)),
-                   STDADK_E_ARG, "train_step: next_y_cols=%d must be in 0..Q with y given", next_y_cols);
+    bin_next = window_n && bin_small_eligible((int)nb.B, cn.pl.G) && s.coords && s.t && (b->p == 0 || s.X);
+    STDADK_REQUIRE(!bin_next || (nb.y_cols >= 0 && nb.y_cols <= d->out_dim && (nb.y_cols == 0 || s.y)),
+                   STDADK_E_ARG, "train_step: next_y_cols=%d must be in 0..Q with y given", nb.y_cols);
   }
   // its carrier: the merged weight-gradient launch of this step (dw_all.hip), which has the time and the idle HBM for
   // the binning's chain of dependent loads, whenever that launch is what the step runs and can hold the batch;
@@ -1703,54 +1710,50 @@ static int train_step_impl(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
   bool bin_in_dw = false;
   if (bin_next) {
     const BinBuffers bb = plan_bins(cn.ws, cn.pl);
-    ba = bin_small_args(coords, t, next_y_cols > 0 ? y : nullptr, next_y_cols, X, b->p, (int)next_B, cn.pl.G, bb, next_idx);
-    const char *ws0 = (const char *)workspace, *ws1 = (const char *)next_workspace;
-    const bool apart = ws1 + next_workspace_bytes <= ws0 || ws0 + workspace_bytes <= ws1;
+    ba = bin_small_args(s.coords, s.t, nb.y_cols > 0 ? s.y : nullptr, nb.y_cols, s.X, b->p, (int)nb.B, cn.pl.G, bb, nb.idx);
+    const char *ws0 = (const char *)s.workspace, *ws1 = (const char *)nb.workspace;
+    const bool apart = ws1 + nb.workspace_bytes <= ws0 || ws0 + s.workspace_bytes <= ws1;
     const char *e = getenv("STDADK_BIN_IN");
     const bool in_adam = e && e[0] == 'a';
-    bin_in_dw = !in_adam && apart && dw_all_bins((int)next_B, cn.pl.G);
+    bin_in_dw = !in_adam && apart && dw_all_bins((int)nb.B, cn.pl.G);
   }
-  bool binned_in_dw = false;
   const bool clip = o->max_norm > 0.f;
   const bool sparse = sparsity && sparsity->kind != STDADK_SPARSITY_NONE;
-  const float *sq_parts = nullptr;   // where the step's own launches left the squared-norm partials, if they did
-  int sq_n = 0;
   // with a sparsity penalty the gradient changes once more after the reductions: the norm is a pass of its own
   const bool fuse_sq = clip && !sparse;
-  int rc = train_fwd_bwd_impl(b, d, P, G, coords, t, X, y, idx, B, grad_scale, loss, loss_sum, nullptr, workspace,
-                              workspace_bytes, drop_seed, o->step_dev, flags, stream, nullptr,
-                              fuse_sq ? o->sumsq_parts : nullptr, fuse_sq ? o->step_dev : nullptr, &sq_parts, &sq_n,
-                              bin_in_dw ? &ba : nullptr, &binned_in_dw);
+  const StepRide ride = {fuse_sq ? o->sumsq_parts : nullptr, fuse_sq ? o->step_dev : nullptr, bin_in_dw ? &ba : nullptr};
+  StepOut out;     // where the step's own launches left the squared-norm partials, if they did
+  int rc = train_fwd_bwd_impl(s, &ride, &out);
   // (a failure behind the weight-gradient launch: the next batch may be binned, but the caller is not told so and
   //  bins it again)
   if (rc) return rc;
   if (sparse) {
-    const bool w0_t = (flags & STDADK_FLAG_W0_T) != 0;
-    rc = stdadk_sparsity_f32(sparsity, P->W[0], G->W[0], w0_t ? d->hidden[0] : d->in_dim, w0_t, d->hidden[0],
-                             b->p, (int32_t)b->Ks, (int32_t)b->Kt, 1.0f, (float)B * (float)d->out_dim, loss_sum,
-                             nullptr, stream);
+    const bool w0_t = (s.flags & STDADK_FLAG_W0_T) != 0;
+    rc = stdadk_sparsity_f32(sparsity, s.P->W[0], s.G->W[0], w0_t ? d->hidden[0] : d->in_dim, w0_t, d->hidden[0],
+                             b->p, (int32_t)b->Ks, (int32_t)b->Kt, 1.0f, (float)s.B * (float)d->out_dim, s.loss_sum,
+                             nullptr, s.stream);
     if (rc) return rc;
   }
   int n_parts = 0;
   const float *parts = o->sumsq_parts;
-  if (clip && sq_parts) {
-    parts = sq_parts; n_parts = sq_n;              // partials (and the step advance) came out of the step's launches
+  if (clip && out.sq_parts) {
+    parts = out.sq_parts; n_parts = out.sq_n;      // partials (and the step advance) came out of the step's launches
   } else if (clip) {
-    rc = stdadk_sumsq_f32(o->g, o->n, o->sumsq_parts, o->step_dev, stream);
+    rc = stdadk_sumsq_f32(o->g, o->n, o->sumsq_parts, o->step_dev, s.stream);
     if (rc) return rc;
     n_parts = STDADK_SUMSQ_PARTS;
   } else {
-    rc = stdadk_step_advance(o->step_dev, stream);
+    rc = stdadk_step_advance(o->step_dev, s.stream);
     if (rc) return rc;
   }
   // with `bin`: the NEXT batch's binning inside this step's optimiser launch (optim.hip: adamw_bin_kernel), when it is
   // the one-launch binning of small batches; the caller then steps on `next_workspace` with STDADK_FLAG_PREBINNED
-  const BinSmallArgs *bin = bin_next && !binned_in_dw ? &ba : nullptr;
+  const BinSmallArgs *bin = bin_next && !out.binned_next ? &ba : nullptr;
   stdadk_adam_group gr;
   AdamHyper h;
-  optim_group(o, clip ? parts : nullptr, n_parts, loss_sum, &gr, &h);
-  rc = adamw_launch("adamw", 1, &gr, nullptr, h, bin, stream);
-  if (rc == 0 && (bin || binned_in_dw)) *next_binned = 1;
+  optim_group(o, clip ? parts : nullptr, n_parts, s.loss_sum, &gr, &h);
+  rc = adamw_launch("adamw", 1, &gr, nullptr, h, bin, s.stream);
+  if (rc == 0 && (bin || out.binned_next)) *nb.binned = 1;
   return rc;
 }
 
@@ -1762,8 +1765,12 @@ extern "C" int stdadk_train_step_f32(const stdadk_basis_desc *b, const stdadk_ml
                                      float *loss_sum, void *workspace, size_t workspace_bytes,
                                      uint64_t drop_seed, int32_t flags, const stdadk_optim_desc *o,
                                      stdadk_stream_t stream) {
-  return train_step_impl(b, d, P, G, coords, t, X, y, idx, B, grad_scale, loss, sparsity, loss_sum, workspace,
-                         workspace_bytes, drop_seed, flags, o, stream, nullptr, 0, 0, nullptr, 0, nullptr);
+  StepCall s;
+  s.b = b; s.d = d; s.P = P; s.G = G; s.coords = coords; s.t = t; s.X = X; s.y = y; s.B = B;
+  s.grad_scale = grad_scale; s.loss = loss; s.loss_sum = loss_sum; s.workspace = workspace;
+  s.workspace_bytes = workspace_bytes; s.drop_seed = drop_seed; s.flags = flags; s.stream = stream;
+  s.idx = idx;
+  return train_step_impl(s, sparsity, o, NextBatch{});
 }
 
 extern "C" int stdadk_train_step_next_f32(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
@@ -1777,9 +1784,12 @@ extern "C" int stdadk_train_step_next_f32(const stdadk_basis_desc *b, const stda
                                           void *next_workspace, size_t next_workspace_bytes, int32_t *next_binned,
                                           stdadk_stream_t stream) {
   STDADK_REQUIRE(next_binned, STDADK_E_ARG, "train_step_next: next_binned is NULL");
-  return train_step_impl(b, d, P, G, coords_all, t_all, X_all, y_all, idx, B, grad_scale, loss, sparsity, loss_sum,
-                         workspace, workspace_bytes, drop_seed, flags, o, stream, next_idx, next_B, next_y_cols,
-                         next_workspace, next_workspace_bytes, next_binned);
+  StepCall s;
+  s.b = b; s.d = d; s.P = P; s.G = G; s.coords = coords_all; s.t = t_all; s.X = X_all; s.y = y_all; s.B = B;
+  s.grad_scale = grad_scale; s.loss = loss; s.loss_sum = loss_sum; s.workspace = workspace;
+  s.workspace_bytes = workspace_bytes; s.drop_seed = drop_seed; s.flags = flags; s.stream = stream;
+  s.idx = idx;
+  return train_step_impl(s, sparsity, o, {next_idx, next_B, next_y_cols, next_workspace, next_workspace_bytes, next_binned});
 }
 
 extern "C" int stdadk_bin_batch_f32(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
@@ -1790,7 +1800,9 @@ extern "C" int stdadk_bin_batch_f32(const stdadk_basis_desc *b, const stdadk_mlp
   if (B == 0) return 0;
   Ctx c;
   bool window;
-  int rc = step_common(c, b, d, B, workspace, workspace_bytes, flags & ~STDADK_FLAG_PREBINNED, &window);
+  // (`training` false: this door reads neither dp nor save)
+  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags & ~STDADK_FLAG_PREBINNED, &window, nullptr, nullptr,
+                     stream, false);
   if (rc) return rc;
   STDADK_REQUIRE(window, STDADK_E_ARG, "bin_batch: only the window path bins its batches");
   STDADK_REQUIRE(coords_all && t_all && (b->p == 0 || X_all), STDADK_E_ARG, "bin_batch: NULL pointer");
@@ -1801,7 +1813,7 @@ extern "C" int stdadk_bin_batch_f32(const stdadk_basis_desc *b, const stdadk_mlp
   // with the step's one-workgroup-per-CU kernels; a single 1024-thread workgroup would take a whole CU
   // away from them for its entire duration
   return bin_obs(coords_all, t_all, y_cols > 0 ? y_all : nullptr, y_cols, X_all, b->p, (int)B, c.pl.G, bb,
-                 (hipStream_t)stream, idx, true);
+                 c.st, idx, true);
 }
 
 extern "C" int stdadk_train_fwd_bwd_f32(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
@@ -1812,8 +1824,12 @@ extern "C" int stdadk_train_fwd_bwd_f32(const stdadk_basis_desc *b, const stdadk
                                         float *y_pred, void *workspace, size_t workspace_bytes,
                                         uint64_t drop_seed, const int32_t *step_dev, int32_t flags,
                                         stdadk_stream_t stream, stdadk_stream_t aux_stream) {
-  return train_fwd_bwd_impl(b, d, P, G, coords, t, X, y, nullptr, B, grad_scale, loss, loss_sum, y_pred, workspace,
-                            workspace_bytes, drop_seed, step_dev, flags, stream, aux_stream);
+  StepCall s;
+  s.b = b; s.d = d; s.P = P; s.G = G; s.coords = coords; s.t = t; s.X = X; s.y = y; s.B = B;
+  s.grad_scale = grad_scale; s.loss = loss; s.loss_sum = loss_sum; s.workspace = workspace;
+  s.workspace_bytes = workspace_bytes; s.drop_seed = drop_seed; s.flags = flags; s.stream = stream;
+  s.y_pred = y_pred; s.step_dev = step_dev; s.aux_stream = aux_stream;
+  return train_fwd_bwd_impl(s, nullptr, nullptr);
 }
 
 extern "C" int stdadk_train_fwd_bwd_indexed_f32(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
@@ -1826,8 +1842,12 @@ extern "C" int stdadk_train_fwd_bwd_indexed_f32(const stdadk_basis_desc *b, cons
                                                 const int32_t *step_dev, int32_t flags,
                                                 stdadk_stream_t stream, stdadk_stream_t aux_stream) {
   STDADK_REQUIRE(idx || B == 0, STDADK_E_ARG, "train_fwd_bwd_indexed: idx is NULL");
-  return train_fwd_bwd_impl(b, d, P, G, coords_all, t_all, X_all, y_all, idx, B, grad_scale, loss, loss_sum, y_pred,
-                            workspace, workspace_bytes, drop_seed, step_dev, flags, stream, aux_stream);
+  StepCall s;
+  s.b = b; s.d = d; s.P = P; s.G = G; s.coords = coords_all; s.t = t_all; s.X = X_all; s.y = y_all; s.B = B;
+  s.grad_scale = grad_scale; s.loss = loss; s.loss_sum = loss_sum; s.workspace = workspace;
+  s.workspace_bytes = workspace_bytes; s.drop_seed = drop_seed; s.flags = flags; s.stream = stream;
+  s.idx = idx; s.y_pred = y_pred; s.step_dev = step_dev; s.aux_stream = aux_stream;
+  return train_fwd_bwd_impl(s, nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1873,7 +1893,7 @@ extern "C" int stdadk_eval_indexed_f32(const stdadk_basis_desc *b, const stdadk_
   Ctx c;
   bool window;
   // the step plan is validated against whatever the workspace holds; the evaluation's own buffers are checked below
-  int rc = step_common(c, b, d, B, workspace, workspace_bytes, flags, &window);
+  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags, &window, P, nullptr, stream, false);   // eval mode
   if (rc) return rc;
   const int Q = d->out_dim;
   const EvalPlan ep = eval_plan(c.pl.total_floats * sizeof(float), B, Q, b->p);
@@ -1888,8 +1908,6 @@ extern "C" int stdadk_eval_indexed_f32(const stdadk_basis_desc *b, const stdadk_
   rc = make_loss(loss, Q, &c.loss);
   if (rc) return rc;
   const LossDev L = c.loss;
-  c.P = P; c.G = nullptr; c.st = (hipStream_t)stream;
-  c.dp = 0.f; c.seed = 0; c.step_dev = nullptr; c.save = false;      // eval mode: no dropout, nothing kept for a backward
   char *base = (char *)workspace;
   double *part = (double *)(base + ep.part);
   if (window) {
@@ -1904,7 +1922,7 @@ extern "C" int stdadk_eval_indexed_f32(const stdadk_basis_desc *b, const stdadk_
   rc = stdadk_gather_batch_f32(coords_all, t_all, y_all, b->p > 0 ? X_all : nullptr, idx, B, L.y_cols, b->p, cg, tg, yg,
                                Xg, stream);
   if (rc) return rc;
-  float *yp = y_pred ? y_pred : c.ws + c.pl.ypred;
+  float *yp = pred_buffer(c, false, y_pred);
   rc = step_forward(c, b, false, cg, tg, Xg, nullptr, yp, stream);
   if (rc) return rc;
   return launch_eval_metrics(L, yp, yg, B, Q, metric_col, batch_weight, part, acc, c.st);

@@ -251,6 +251,106 @@ def _record(tmp):
                        BATCH, 1.0 / BATCH, eng.loss_sum, eng.ws, st.flags, N.make_optim(**a))
     rec["optim_errors"].update({"desc_ok": one_call(), "desc_no_step": one_call(step_dev=None),
                                 "desc_no_m": one_call(m=None), "desc_clip": one_call(sumsq_parts=None)})
+
+    # --- 5. refusals of the step opener and the four training doors: code and text, straight from the C ABI
+    DOORS = {   # argument names in ABI order
+        "train_fwd_bwd": "b d P G coords t X y B grad_scale loss loss_sum y_pred ws ws_bytes seed step_dev flags stream aux",
+        "train_fwd_bwd_indexed": "b d P G coords t X y idx B grad_scale loss loss_sum y_pred ws ws_bytes seed step_dev flags "
+                                 "stream aux",
+        "train_step": "b d P G coords t X y idx B grad_scale loss sparsity loss_sum ws ws_bytes seed flags o stream",
+        "train_step_next": "b d P G coords t X y idx B grad_scale loss sparsity loss_sum ws ws_bytes seed flags o next_idx "
+                           "next_B next_y_cols next_ws next_ws_bytes next_binned stream",
+    }
+
+    done = C.c_int32(7)
+
+    def doors_of(p):
+        """door(name, **changed arguments) -> [code, text] on a model with p covariates."""
+        torch.manual_seed(0)    # (the window path needs a first hidden layer of 128 or 256 units)
+        eng = TrainStep(STInterpMLP(p=p, k_spatial_centers=[25, 81], k_temporal_centers=[10, 15], hidden_dims=[128, 64],
+                                    dropout=0.0, layernorm=True), max_batch=BATCH, ema_decay=0.99, seed=1)
+        st = eng.state
+        win = st.flags | N.FLAG_WINDOW
+        assert N.step_uses_window(st.basis, st.desc, win) and not N.step_uses_window(st.basis, st.desc, st.flags)
+        idx, nxt = torch.arange(BATCH), torch.arange(BATCH)
+        ws_w = torch.empty(max(N.step_workspace_bytes(st.basis, st.desc, BATCH, f) for f in (win, st.flags)) // 4 + 4)
+        ws_n = torch.empty_like(ws_w)
+        no_hidden = type(st.desc)()
+        C.memmove(C.byref(no_hidden), C.byref(st.desc), C.sizeof(no_hidden))
+        no_hidden.n_hidden = 0
+        optim = N.make_optim(p=eng.flat, g=eng.grad, m=eng.m, v=eng.v, ema=eng.ema, lr=1e-3, lr_dev=None, betas=(0.9, 0.999),
+                             eps=1e-8, weight_decay=0.0, step_dev=eng.step_dev, max_norm=1.0, sumsq_parts=eng._sumsq512,
+                             ema_decay=0.99)
+        X = torch.randn(BATCH, max(p, 1))
+
+        def door(name, **kw):
+            a = dict(b=C.byref(st.basis), d=C.byref(st.desc), P=C.byref(st.params), G=C.byref(eng.grads_t),
+                     coords=tr.coords.data_ptr(), t=tr.t.data_ptr(), X=X.data_ptr() if p else None, y=tr.y.data_ptr(),
+                     idx=None, B=BATCH, grad_scale=1.0 / BATCH, loss=None, sparsity=None, loss_sum=eng.loss_sum.data_ptr(), y_pred=None,
+                     ws=ws_w.data_ptr(), ws_bytes=ws_w.numel() * 4, seed=0, step_dev=eng.step_dev.data_ptr(), flags=st.flags,
+                     stream=None, aux=None, o=C.byref(optim), next_idx=nxt.data_ptr(), next_B=BATCH, next_y_cols=1,
+                     next_ws=ws_n.data_ptr(), next_ws_bytes=ws_n.numel() * 4, next_binned=C.byref(done))
+            if name in ("train_fwd_bwd_indexed", "train_step_next"):
+                a.update(idx=idx.data_ptr(), flags=win)
+            a.update(kw)
+            rc = getattr(real, f"stdadk_{name}_f32")(*[a[k] for k in DOORS[name].split()])
+            return [rc, real.stdadk_last_error().decode() if rc else ""]
+        door.idx, door.ws, door.next_ws, door.no_hidden, door.dense, door.win = idx, ws_w, ws_n, no_hidden, st.flags, win
+        return door
+    door = doors_of(0)
+    dense, win = door.dense, door.win
+    r = {}
+    for name in DOORS:
+        r[name + ":ok"] = door(name)
+        r[name + ":null_P"] = door(name, P=None)
+        r[name + ":null_G"] = door(name, G=None)
+        r[name + ":null_desc"] = door(name, d=None)
+        r[name + ":null_basis"] = door(name, b=None)
+        r[name + ":bad_B"] = door(name, B=-1)
+        r[name + ":null_ws"] = door(name, ws=None)
+        r[name + ":ws_misaligned"] = door(name, ws=door.ws.data_ptr() + 4)
+        r[name + ":ws_small"] = door(name, ws_bytes=256)
+        r[name + ":null_coords"] = door(name, coords=None)
+        r[name + ":null_y"] = door(name, y=None)
+        r[name + ":bf16_no_tail"] = door(name, d=C.byref(door.no_hidden), flags=dense | N.FLAG_BF16)
+        r[name + ":bad_loss"] = door(name, loss=C.byref(N.make_loss("mse", Q=1, y_cols=3)))
+        # two mistakes at once: the first check in the door's order speaks
+        r[name + ":ws_small+null_P"] = door(name, ws_bytes=256, P=None)
+        r[name + ":null_P+bad_loss"] = door(name, P=None, loss=C.byref(N.make_loss("mse", Q=1, y_cols=3)))
+    for name in ("train_fwd_bwd", "train_step"):
+        r[name + ":prebinned_dense"] = door(name, flags=dense | N.FLAG_PREBINNED)
+        r[name + ":prebinned_window_ok"] = door(name, flags=win | N.FLAG_PREBINNED, coords=None, y=None)
+    r["train_step:idx_dense+null_P"] = door("train_step", idx=door.idx.data_ptr(), P=None)
+    r["train_step:idx_dense"] = door("train_step", idx=door.idx.data_ptr())
+    r["train_fwd_bwd_indexed:idx_dense"] = door("train_fwd_bwd_indexed", flags=dense)
+    r["train_fwd_bwd_indexed:null_idx"] = door("train_fwd_bwd_indexed", idx=None)
+    r["train_fwd_bwd_indexed:null_idx+null_P"] = door("train_fwd_bwd_indexed", idx=None, P=None)
+    r["train_fwd_bwd_indexed:null_idx_B0"] = door("train_fwd_bwd_indexed", idx=None, B=0)
+    r["train_step_next:null_binned"] = door("train_step_next", next_binned=None)
+    r["train_step_next:null_binned+no_optim"] = door("train_step_next", next_binned=None, o=None)
+    r["train_step_next:no_optim"] = door("train_step_next", o=None)
+    r["train_step_next:y_cols_high"] = door("train_step_next", next_y_cols=2)
+    r["train_step_next:y_cols_neg"] = door("train_step_next", next_y_cols=-1)
+    r["train_step_next:y_cols_no_y"] = door("train_step_next", y=None, flags=win | N.FLAG_PREBINNED)
+    r["train_step_next:next_ws_small"] = door("train_step_next", next_ws_bytes=256)
+    r["train_step_next:next_ws_small+null_P"] = door("train_step_next", next_ws_bytes=256, P=None)
+    r["train_step_next:next_ws_misaligned"] = door("train_step_next", next_ws=door.next_ws.data_ptr() + 4)
+    r["train_step_next:next_B_bad"] = door("train_step_next", next_B=1 << 31)
+    done.value = 7
+    r["train_step_next:binned_flag"] = [door("train_step_next")[0], done.value]
+    done.value = 7
+    r["train_step_next:binned_reset_on_error"] = [door("train_step_next", P=None)[0], done.value]
+    # covariates (p = 2): X is asked for after the other pointers and before the loss descriptor, unless the batch is binned
+    door = doors_of(2)
+    bad_loss = C.byref(N.make_loss("mse", Q=1, y_cols=3))
+    for name in DOORS:
+        r[name + ":p2_ok"] = door(name)
+        r[name + ":p2_null_X"] = door(name, X=None)
+        r[name + ":p2_null_X+bad_loss"] = door(name, X=None, loss=bad_loss)
+        r[name + ":p2_null_X+null_coords"] = door(name, X=None, coords=None)
+        r[name + ":p2_null_X+ws_small"] = door(name, X=None, ws_bytes=256)
+        r[name + ":p2_null_X_prebinned"] = door(name, X=None, flags=door.win | N.FLAG_PREBINNED)
+    rec["step_errors"] = r
     print("RECORD " + json.dumps(rec))
 
 
@@ -342,6 +442,74 @@ def test_optimiser_entry_points_refuse_with_code_and_text(rec):
             ("desc_no_m", -1, "train_step: optimiser descriptor incomplete"),
             ("desc_clip", -1, "train_step: max_norm > 0 needs sumsq_parts")]:
         assert e[key].endswith(f"failed (code {code}): {text}"), (key, e[key])
+
+
+_DOORS = ("train_fwd_bwd", "train_fwd_bwd_indexed", "train_step", "train_step_next")
+_NULL, _BF16, _IDX = "train_fwd_bwd: NULL pointer", ("step: STDADK_FLAG_BF16 needs the fused tail kernels (hidden widths "
+                                                     "multiples of 16 up to 256, out_dim <= 8)"), (
+    "train_fwd_bwd_indexed: only the window path gathers in place; use stdadk_gather_batch_f32 + "
+    "stdadk_train_fwd_bwd_f32 for the materialising path")
+
+
+def test_step_doors_refuse_with_code_and_text(rec):
+    """What the step opener and the four training doors refuse, by error code and text: NULL descriptors, a bad batch
+    size, a workspace that is NULL, off its 16-byte boundary or too small, bf16 without the fused tail, NULL parameter /
+    gradient tables and observations, a bad loss descriptor, STDADK_FLAG_PREBINNED or idx off the window path, idx or
+    next_binned NULL where the door needs them, next_y_cols out of range, and the next batch's own workspace."""
+    e = rec["step_errors"]
+    for door in _DOORS:
+        assert e[door + ":ok"] == [0, ""], (door, e[door + ":ok"])
+        for key, code, text in [
+                ("null_desc", -1, "mlp: desc is NULL"), ("null_basis", -1, "basis desc is NULL"), ("bad_B", -1, "step: bad B"),
+                ("null_ws", -3, "step: workspace NULL or not 16-byte aligned"),
+                ("ws_misaligned", -3, "step: workspace NULL or not 16-byte aligned"), ("bf16_no_tail", -1, _BF16),
+                ("null_P", -1, _NULL), ("null_G", -1, _NULL), ("null_coords", -1, _NULL),
+                ("bad_loss", -1, "loss: y_cols=3 must be 1 or Q=1")]:
+            assert e[f"{door}:{key}"] == [code, text], (door, key, e[f"{door}:{key}"])
+        code, text = e[door + ":ws_small"]
+        assert code == -4 and text.startswith("step: workspace 256 < ") and text.endswith(" bytes"), (door, text)
+    # without targets: the step doors refuse; a step that announces its next batch is asked for them by that batch first
+    assert e["train_fwd_bwd:null_y"] == e["train_fwd_bwd_indexed:null_y"] == e["train_step:null_y"] == [-1, _NULL]
+    no_y = [-1, "train_step: next_y_cols=1 must be in 0..Q with y given"]
+    assert e["train_step_next:null_y"] == no_y and e["train_step_next:y_cols_no_y"] == no_y
+    for door in ("train_fwd_bwd", "train_step"):
+        assert e[door + ":prebinned_dense"] == [-1, "step: STDADK_FLAG_PREBINNED needs the window path"]
+        assert e[door + ":prebinned_window_ok"] == [0, ""]       # a binned workspace needs no observations
+    assert e["train_step:idx_dense"] == [-1, _IDX] and e["train_fwd_bwd_indexed:idx_dense"] == [-1, _IDX]
+    assert e["train_fwd_bwd_indexed:null_idx"] == [-1, "train_fwd_bwd_indexed: idx is NULL"]
+    assert e["train_fwd_bwd_indexed:null_idx_B0"] == [0, ""]
+    assert e["train_step_next:null_binned"] == [-1, "train_step_next: next_binned is NULL"]
+    assert e["train_step_next:no_optim"] == [-1, "train_step: optimiser descriptor incomplete"]
+    for key, n in (("y_cols_high", 2), ("y_cols_neg", -1)):
+        assert e["train_step_next:" + key] == [-1, f"train_step: next_y_cols={n} must be in 0..Q with y given"]
+    code, text = e["train_step_next:next_ws_small"]
+    assert code == -4 and text.startswith("step: workspace 256 < ")
+    assert e["train_step_next:next_ws_misaligned"] == [-3, "step: workspace NULL or not 16-byte aligned"]
+    assert e["train_step_next:next_B_bad"] == [-1, "step: bad B"]
+    # covariates: every door asks for X when p > 0, except on a workspace that already holds the binned batch
+    for door in _DOORS:
+        assert e[door + ":p2_ok"] == [0, ""], (door, e[door + ":p2_ok"])
+        assert e[door + ":p2_null_X"] == [-1, "train_fwd_bwd: X is NULL with p=2"], (door, e[door + ":p2_null_X"])
+        assert e[door + ":p2_null_X_prebinned"] == [0, ""], (door, e[door + ":p2_null_X_prebinned"])
+    # next_binned: 1 after a call that binned, cleared by a call that failed
+    assert e["train_step_next:binned_flag"] == [0, 1] and e["train_step_next:binned_reset_on_error"] == [-1, 0]
+
+
+def test_step_doors_report_the_first_of_two_mistakes(rec):
+    """A call with two mistakes reports the one the door checks first: the opener's workspace check before a NULL
+    parameter table, the NULL table before the loss descriptor, idx off the window path before the NULL table, a door's
+    own argument before anything the shared code checks, the next batch's workspace before this batch's pointers."""
+    e = rec["step_errors"]
+    for door in _DOORS:
+        assert e[door + ":ws_small+null_P"] == e[door + ":ws_small"] and e[door + ":ws_small"][0] == -4
+        assert e[door + ":null_P+bad_loss"] == [-1, _NULL]
+        assert e[door + ":p2_null_X+bad_loss"] == [-1, "train_fwd_bwd: X is NULL with p=2"]
+        assert e[door + ":p2_null_X+null_coords"] == [-1, _NULL]
+        assert e[door + ":p2_null_X+ws_small"][0] == -4 and e[door + ":p2_null_X+ws_small"][1].startswith("step: workspace 256 < ")
+    assert e["train_step:idx_dense+null_P"] == [-1, _IDX]
+    assert e["train_fwd_bwd_indexed:null_idx+null_P"] == [-1, "train_fwd_bwd_indexed: idx is NULL"]
+    assert e["train_step_next:null_binned+no_optim"] == [-1, "train_step_next: next_binned is NULL"]
+    assert e["train_step_next:next_ws_small+null_P"] == e["train_step_next:next_ws_small"]
 
 
 if __name__ == "__main__":
