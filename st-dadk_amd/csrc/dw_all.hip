@@ -59,7 +59,7 @@ __global__ __launch_bounds__(GT) void dw_all_kernel(GemmGroup grp, int n_gemm_bl
   const int first = a.xcd_slots > 0 ? (n_front + n_mid + 7) & ~7 : n_front + n_mid;
   if (blk < first) return;
   float sq;
-  if constexpr (NK > 1) sq = l1_window_bwd_multi_body<CPL, BASIS, NK>(a, blk - first);
+  if constexpr (NK == 2) sq = l1_window_bwd_multi_body<CPL, BASIS>(a, blk - first);
   else sq = l1_window_bwd_body<CPL, BASIS, KNOTS>(a, blk - first);
   if (fin.slots) {                 // workgroup-uniform; every wave of the workgroup arrives (no wave exits early)
     const float t = block4_sum(sq, lds);
@@ -71,12 +71,7 @@ __global__ __launch_bounds__(GT) void dw_all_kernel(GemmGroup grp, int n_gemm_bl
 static_assert(sizeof(GemmGroup) + sizeof(L1BwdArgs) + sizeof(FinArgs) + sizeof(ReduceGroup) + sizeof(BinSmallArgs) + 32 <= 4096,
               "dw_all: kernel arguments exceed the kernarg segment");
 
-int dw_all_knot_blocks(const L1BwdArgs &a_in) {
-  L1BwdArgs a = a_in;
-  const int nk = knots_per_wave(a);
-  const int slots = knot_xcd_slots(a.g, a.kpart ? 1 : nk);
-  return slots > 0 ? 8 * slots : (int)ceil_div(knot_group_count(a.g, nk), BW_T / 64);
-}
+int dw_all_knot_blocks(const L1BwdArgs &a) { return knot_plan(a).blocks; }
 
 bool dw_all_bins(int B, int G) { return bin_dw_holds(B, G); }
 
@@ -89,10 +84,9 @@ int launch_dw_all(GemmGroup &grp, const L1BwdArgs &a_in, int basis, hipStream_t 
   int ng = 0;
   int rc = gemm_tn_grouped_prepare(grp, &ng);
   if (rc) return rc;
-  const int nk = knots_per_wave(a);
-  a.xcd_slots = knot_xcd_slots(a.g, a.kpart ? 1 : nk);
-  const unsigned n_knot = a.xcd_slots > 0 ? 8u * (unsigned)a.xcd_slots
-                                          : (unsigned)ceil_div(knot_group_count(a.g, nk), BW_T / 64);
+  const KnotPlan kp = knot_plan(a);
+  a.xcd_slots = kp.xcd_slots;
+  const unsigned n_knot = (unsigned)kp.blocks;
   FinArgs fin;
   ReduceGroup tall;
   if (fin_in && fin_in->cnt) {
@@ -133,8 +127,8 @@ int launch_dw_all(GemmGroup &grp, const L1BwdArgs &a_in, int basis, hipStream_t 
   do {                                                                                                     \
     if (a.kpart) STDADK_LAUNCH_NAMED("dw_all_kernel<knots>", (dw_all_kernel<CPL_, BS_, true, 1>),          \
                                      dim3(grid), dim3(GT), 0, st, grp, ng, a, fin, tall, bin, n_bin, bin_front); \
-    else if (nk == 2) STDADK_LAUNCH_NAMED("dw_all_kernel", (dw_all_kernel<CPL_, BS_, false, 2>), dim3(grid), \
-                                          dim3(GT), 0, st, grp, ng, a, fin, tall, bin, n_bin, bin_front);  \
+    else if (kp.nk == 2) STDADK_LAUNCH_NAMED("dw_all_kernel", (dw_all_kernel<CPL_, BS_, false, 2>), dim3(grid), \
+                                             dim3(GT), 0, st, grp, ng, a, fin, tall, bin, n_bin, bin_front); \
     else STDADK_LAUNCH_NAMED("dw_all_kernel", (dw_all_kernel<CPL_, BS_, false, 1>), dim3(grid),            \
                              dim3(GT), 0, st, grp, ng, a, fin, tall, bin, n_bin, bin_front);               \
   } while (0)

@@ -3,6 +3,7 @@
 #pragma once
 #include "window.h"
 #include "basis.h"
+#include "l1_walk.h"
 
 namespace stdadk {
 
@@ -43,6 +44,80 @@ __device__ __forceinline__ void fma_row(float *acc, float s, const float *row) {
   for (int c = 0; c < CPL; ++c) acc[c] = fmaf(s, f[c], acc[c]);
 }
 
+template <int CPL>
+__device__ __forceinline__ void store_vec(float *dst, const float *v) {
+  typename VecT<CPL>::T o;
+  float *fo = reinterpret_cast<float *>(&o);
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) fo[c] = v[c];
+  *reinterpret_cast<typename VecT<CPL>::T *>(dst) = o;
+}
+
+// temporal rows of W0^T into LDS: ALL of a thread's pieces requested first, then stored (Kt H 4 B <= 96 KiB =>
+// at most 6 float4 per thread; clamped, unconditional loads).  As a rolled `dst[i] = src[i]` loop this was
+// Kt H / 4096 dependent L2 round trips -- five for the 70 temporal knots -- at the head of every workgroup.
+template <int CPL>
+__device__ __forceinline__ void stage_temporal_rows(const L1FwdArgs &a, float *Wt, int tid) {
+  constexpr int H = 64 * CPL;
+  const float4 *src = reinterpret_cast<const float4 *>(a.W0T + (size_t)(a.g.p + a.g.Ks) * H);
+  float4 *dst = reinterpret_cast<float4 *>(Wt);
+  const int n4 = a.g.Kt * H / 4;
+  if (n4 > 0) {                                   // workgroup-uniform (a model without temporal knots)
+    float4 tmp[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) tmp[k] = src[min(tid + FW_T * k, n4 - 1)];
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+      if (tid + FW_T * k < n4) dst[tid + FW_T * k] = tmp[k];
+  }
+}
+
+// the dropout of a launch: seed of the step, scale of the kept units, threshold of drop_keep()
+struct L1Drop {
+  uint64_t seed;
+  float keep_scale;
+  uint32_t thr;
+};
+__device__ __forceinline__ L1Drop l1_drop(const L1FwdArgs &a) {
+  return {a.seed + (a.step_dev ? (uint64_t)a.step_dev[0] * 0x9E3779B97F4A7C15ULL : 0ULL),
+          a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f, drop_threshold(a.drop_p)};
+}
+
+// One row's pre-activations acc[CPL] (this lane's columns; the wave owns the whole row) through LayerNorm -> ReLU ->
+// Dropout; stores xhat, rstd and act.
+template <int CPL, bool LN>
+__device__ __forceinline__ void l1_row_epilogue(const L1FwdArgs &a, const L1Drop &dr, const float *acc, const float *gam,
+                                                const float *bet, int row, int lane) {
+  constexpr int H = 64 * CPL;
+  float mean = 0.f, rs = 1.f;
+  if (LN) {
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) s += acc[c];
+    mean = wave_sum(s) * (1.0f / (float)H);
+    float sq = 0.f;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) { float d = acc[c] - mean; sq += d * d; }
+    rs = ln_rstd(wave_sum(sq) * (1.0f / (float)H), a.eps);
+    if (lane == 0 && a.rstd) a.rstd[row] = rs;
+  }
+  float xh[CPL], av[CPL];
+  const uint32_t rowkey = drop_rowkey(dr.seed, 0, row);
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) {
+    xh[c] = LN ? (acc[c] - mean) * rs : acc[c];
+    float u = LN ? fmaf(xh[c], gam[c], bet[c]) : xh[c];
+    float v = fmaxf(u, 0.f);
+    if (a.drop_p > 0.f) {
+      bool keep = drop_keep(rowkey, CPL * lane + c, dr.thr);
+      v = keep ? v * dr.keep_scale : 0.f;
+    }
+    av[c] = v;
+  }
+  if (a.xhat) store_vec<CPL>(a.xhat + (size_t)row * H + CPL * lane, xh);
+  store_vec<CPL>(a.act + (size_t)row * H + CPL * lane, av);
+}
+
 // rows [r0, r1) of the sorted batch by this workgroup (one wave per observation)
 template <int CPL, bool LN, int BASIS, bool FREE>
 __device__ __forceinline__ void l1_window_fwd_body(const L1FwdArgs &a, float *smem, const int r0, const int r1) {
@@ -55,7 +130,6 @@ __device__ __forceinline__ void l1_window_fwd_body(const L1FwdArgs &a, float *sm
   float *lpsi = reinterpret_cast<float *>(lk + NW * LIST);  // [NW][Kt_pad]
   const int Kt_pad = (Kt + 3) & ~3;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int D0 = a.g.p + a.g.Ks;                      // first temporal row of W0^T
   // the wave's first observation and the per-column parameters are requested before the temporal rows
   // are staged, so that all of it shares one memory round trip ahead of the workgroup barrier
   const int rowf = min(r0 + wave, a.B - 1);
@@ -67,30 +141,13 @@ __device__ __forceinline__ void l1_window_fwd_body(const L1FwdArgs &a, float *sm
     gam[c] = LN ? a.gamma[CPL * lane + c] : 1.f;
     bet[c] = LN ? a.beta[CPL * lane + c] : 0.f;
   }
-  {
-    // temporal rows of W0^T into LDS: ALL of a thread's pieces requested first, then stored (Kt H 4 B <= 96 KiB =>
-    // at most 6 float4 per thread; clamped, unconditional loads).  As a rolled `dst[i] = src[i]` loop this was
-    // Kt H / 4096 dependent L2 round trips -- five for the 70 temporal knots -- at the head of every workgroup.
-    const float4 *src = reinterpret_cast<const float4 *>(a.W0T + (size_t)D0 * H);
-    float4 *dst = reinterpret_cast<float4 *>(Wt);
-    const int n4 = Kt * H / 4;
-    if (n4 > 0) {                                   // workgroup-uniform (a model without temporal knots)
-      float4 tmp[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) tmp[k] = src[min(tid + FW_T * k, n4 - 1)];
-#pragma unroll
-      for (int k = 0; k < 6; ++k)
-        if (tid + FW_T * k < n4) dst[tid + FW_T * k] = tmp[k];
-    }
-  }
+  stage_temporal_rows<CPL>(a, Wt, tid);
   __syncthreads();
   float *my_phi = lphi + wave * LIST;
   int *my_k = lk + wave * LIST;
   float *my_psi = lpsi + wave * Kt_pad;
-  const uint64_t seed = a.seed + (a.step_dev ? (uint64_t)a.step_dev[0] * 0x9E3779B97F4A7C15ULL : 0ULL);
-  const float keep_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
-  const uint32_t drop_thr = drop_threshold(a.drop_p);
-  const uint64_t below = (lane == 0) ? 0ULL : (~0ULL >> (64 - lane));
+  const L1Drop dr = l1_drop(a);
+  const uint64_t below = lanes_below(lane);
 
   for (int row = r0 + wave; row < r1; row += FW_T / 64) {
     const bool first = row == r0 + wave;
@@ -165,9 +222,8 @@ __device__ __forceinline__ void l1_window_fwd_body(const L1FwdArgs &a, float *sm
         // a candidate's value into the per-wave list (non-zeros compacted by ballot + popcount; a full list is
         // consumed, zero-padded to 8, and started over)
         auto push = [&](float phi, int k) {
-          const uint64_t mask = __ballot(phi != 0.f);
-          const int m = __popcll(mask);
-          if (n + m > LIST - 8) {
+          const Compacted c = compact(phi != 0.f, below);
+          if (n + c.m > LIST - 8) {
             const int npad = (n + 7) & ~7;
             if (lane < npad - n) { my_phi[n + lane] = 0.f; my_k[n + lane] = 0; }
             __builtin_amdgcn_wave_barrier();
@@ -176,18 +232,19 @@ __device__ __forceinline__ void l1_window_fwd_body(const L1FwdArgs &a, float *sm
             n = 0;
           }
           if (phi != 0.f) {
-            const int pos = n + __popcll(mask & below);
-            my_phi[pos] = phi;
-            my_k[pos] = a.g.p + k;
+            my_phi[n + c.pos] = phi;
+            my_k[n + c.pos] = a.g.p + k;
           }
-          n += m;
+          n += c.m;
         };
         if (a.kperm) {
           // scattered knots: the level's knots were binned into a Gk x Gk cell grid (knot_bins); the candidates are
           // the knots of the cells within ceil(reach Gk) + 1 of the observation's cell -- every knot whose support
           // can reach it (a knot outside the domain sits in a border cell: never farther in cells than in fact).
           // A row of cells is one contiguous run of kperm: the rows' runs are walked as ONE flat list, 64 candidates
-          // per pass (the same segment walk as the per-knot gather of dW0^T).
+          // per pass.  This is walk_cell_runs() of l1_walk.h written out for Gk <= 64 (one lane per cell row): through
+          // the shared walk every free-knot forward kernel needs more registers and scratch (figures in
+          // profiles/l1_walk_refactor.md).
           const int Gk = a.Gk;
           const float rc = a.reach[l];
           const int rad = (rc < 4.0f) ? (int)ceilf(rc * (float)Gk) + 1 : Gk;        // NaN / huge: the whole level
@@ -195,7 +252,7 @@ __device__ __forceinline__ void l1_window_fwd_body(const L1FwdArgs &a, float *sm
           const int cx_lo = max(ocx - rad, 0), cx_hi = min(ocx + rad, Gk - 1);
           const int cy_lo = max(ocy - rad, 0), cy_hi = min(ocy + rad, Gk - 1);
           const int *cs = a.kcs + (size_t)l * (Gk * Gk + 1);
-          const int cxl = cx_lo + lane;                                              // Gk <= 64: one lane per cell row
+          const int cxl = cx_lo + lane;
           int seg0 = 0, seg1 = 0;
           if (cxl <= cx_hi) { seg0 = cs[cxl * Gk + cy_lo]; seg1 = cs[cxl * Gk + cy_hi + 1]; }
           int incl = seg1 - seg0;
@@ -275,13 +332,12 @@ __device__ __forceinline__ void l1_window_fwd_body(const L1FwdArgs &a, float *sm
         for (int j = 0; j < 3; ++j) {
           if (l0 + j < l1) {
             const float phi = ok[j] ? phi_eval<BASIS>(x, y, kx[j], ky[j], knot_scale(kb[j], a.g.cal)) : 0.f;
-            const uint64_t mask = __ballot(phi != 0.f);
+            const Compacted c = compact(phi != 0.f, below);
             if (phi != 0.f) {
-              const int pos = n + __popcll(mask & below);
-              my_phi[pos] = phi;
-              my_k[pos] = a.g.p + kk[j];
+              my_phi[n + c.pos] = phi;
+              my_k[n + c.pos] = a.g.p + kk[j];
             }
-            n += __popcll(mask);
+            n += c.m;
           }
         }
       }
@@ -307,11 +363,7 @@ __device__ __forceinline__ void l1_window_fwd_body(const L1FwdArgs &a, float *sm
     }
 
     if (a.raw) {                           // wave-uniform: the spatial part alone
-      typename VecT<CPL>::T o;
-      float *fo = reinterpret_cast<float *>(&o);
-#pragma unroll
-      for (int c = 0; c < CPL; ++c) fo[c] = acc[c];
-      *reinterpret_cast<typename VecT<CPL>::T *>(a.act + (size_t)row * H + CPL * lane) = o;
+      store_vec<CPL>(a.act + (size_t)row * H + CPL * lane, acc);
       continue;
     }
     // ---- temporal basis: rows from LDS
@@ -346,7 +398,9 @@ __device__ __forceinline__ void l1_window_fwd_body(const L1FwdArgs &a, float *sm
     }
     __builtin_amdgcn_wave_barrier();
 
-    // ---- LayerNorm -> ReLU -> Dropout (row-local: this wave owns the whole row)
+    // ---- LayerNorm -> ReLU -> Dropout (row-local: this wave owns the whole row).  l1_row_epilogue() written out:
+    // through the helper the fused step kernels for H = 128 with free knots spill two more SGPRs and reserve a
+    // scratch frame they do not have otherwise (profiles/l1_walk_refactor.md)
     float mean = 0.f, rs = 1.f;
     if (LN) {
       float s = 0.f;
@@ -360,15 +414,15 @@ __device__ __forceinline__ void l1_window_fwd_body(const L1FwdArgs &a, float *sm
       if (lane == 0 && a.rstd) a.rstd[row] = rs;
     }
     float xh[CPL], av[CPL];
-    const uint32_t rowkey = drop_rowkey(seed, 0, row);
+    const uint32_t rowkey = drop_rowkey(dr.seed, 0, row);
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
       xh[c] = LN ? (acc[c] - mean) * rs : acc[c];
       float u = LN ? fmaf(xh[c], gam[c], bet[c]) : xh[c];
       float v = fmaxf(u, 0.f);
       if (a.drop_p > 0.f) {
-        bool keep = drop_keep(rowkey, CPL * lane + c, drop_thr);
-        v = keep ? v * keep_scale : 0.f;
+        bool keep = drop_keep(rowkey, CPL * lane + c, dr.thr);
+        v = keep ? v * dr.keep_scale : 0.f;
       }
       av[c] = v;
     }
@@ -402,32 +456,14 @@ __device__ __forceinline__ void l1_window_fwd_multi_body(const L1FwdArgs &a, flo
   int *lk = reinterpret_cast<int *>(lphi + NW * LIST * R);   // [NW][LIST]
   float *lpsi = reinterpret_cast<float *>(lk + NW * LIST);   // [NW][Kt_pad][R]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int D0 = a.g.p + a.g.Ks;
   const int rowf = r0 + R * wave;
-  {
-    // temporal rows of W0^T into LDS: ALL of a thread's pieces requested first, then stored (Kt H 4 B <= 96 KiB =>
-    // at most 6 float4 per thread; clamped, unconditional loads).  As a rolled `dst[i] = src[i]` loop this was
-    // Kt H / 4096 dependent L2 round trips -- five for the 70 temporal knots -- at the head of every workgroup.
-    const float4 *src = reinterpret_cast<const float4 *>(a.W0T + (size_t)D0 * H);
-    float4 *dst = reinterpret_cast<float4 *>(Wt);
-    const int n4 = Kt * H / 4;
-    if (n4 > 0) {                                   // workgroup-uniform (a model without temporal knots)
-      float4 tmp[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) tmp[k] = src[min(tid + FW_T * k, n4 - 1)];
-#pragma unroll
-      for (int k = 0; k < 6; ++k)
-        if (tid + FW_T * k < n4) dst[tid + FW_T * k] = tmp[k];
-    }
-  }
+  stage_temporal_rows<CPL>(a, Wt, tid);
   __syncthreads();
   float *my_phi = lphi + wave * LIST * R;
   int *my_k = lk + wave * LIST;
   float *my_psi = lpsi + wave * Kt_pad * R;
-  const uint64_t seed = a.seed + (a.step_dev ? (uint64_t)a.step_dev[0] * 0x9E3779B97F4A7C15ULL : 0ULL);
-  const float keep_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
-  const uint32_t drop_thr = drop_threshold(a.drop_p);
-  const uint64_t below = (lane == 0) ? 0ULL : (~0ULL >> (64 - lane));
+  const L1Drop dr = l1_drop(a);
+  const uint64_t below = lanes_below(lane);
   const int bdx = lane >> 3, bdy = lane & 7;              // this lane's place in an 8 x 8 candidate box
 
   for (int row = rowf; row < r1; row += R * NW) {
@@ -541,16 +577,15 @@ __device__ __forceinline__ void l1_window_fwd_multi_body(const L1FwdArgs &a, flo
               phi[r] = (ok[j] && (!far || r == pass)) ? phi_eval<BASIS>(x[r], y[r], kx[j], ky[j], sc) : 0.f;
               any = any || phi[r] != 0.f;
             }
-            const uint64_t mask = __ballot(any);
-            const int m = __popcll(mask);
-            if (n + m > LIST - 8 - WIN_MAX_P) { flush(n); n = 0; }     // wave-uniform
+            const Compacted c = compact(any, below);
+            if (n + c.m > LIST - 8 - WIN_MAX_P) { flush(n); n = 0; }     // wave-uniform
             if (any) {
-              const int pos = n + __popcll(mask & below);
+              const int pos = n + c.pos;
 #pragma unroll
               for (int r = 0; r < R; ++r) my_phi[pos * R + r] = phi[r];
               my_k[pos] = a.g.p + kk[j];
             }
-            n += m;
+            n += c.m;
           }
         }
         if (l0 == 0 && a.g.p > 0) {            // covariate columns [0, p): dense, per observation
@@ -570,13 +605,7 @@ __device__ __forceinline__ void l1_window_fwd_multi_body(const L1FwdArgs &a, flo
     if (a.raw) {                           // wave-uniform: the spatial part alone
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        if (r < nv) {
-          typename VecT<CPL>::T o;
-          float *fo = reinterpret_cast<float *>(&o);
-#pragma unroll
-          for (int c = 0; c < CPL; ++c) fo[c] = acc[r][c];
-          *reinterpret_cast<typename VecT<CPL>::T *>(a.act + (size_t)(row + r) * H + CPL * lane) = o;
-        }
+        if (r < nv) store_vec<CPL>(a.act + (size_t)(row + r) * H + CPL * lane, acc[r]);
       }
       continue;
     }
@@ -635,39 +664,8 @@ __device__ __forceinline__ void l1_window_fwd_multi_body(const L1FwdArgs &a, flo
       bet[c] = LN ? a.beta[CPL * lane + c] : 0.f;
     }
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (r < nv) {
-        const int orow = row + r;
-        float mean = 0.f, rs = 1.f;
-        if (LN) {
-          float s = 0.f;
-#pragma unroll
-          for (int c = 0; c < CPL; ++c) s += acc[r][c];
-          mean = wave_sum(s) * (1.0f / (float)H);
-          float sq = 0.f;
-#pragma unroll
-          for (int c = 0; c < CPL; ++c) { float d = acc[r][c] - mean; sq += d * d; }
-          rs = ln_rstd(wave_sum(sq) * (1.0f / (float)H), a.eps);
-          if (lane == 0 && a.rstd) a.rstd[orow] = rs;
-        }
-        typename VecT<CPL>::T o1, o2;
-        float *f1 = reinterpret_cast<float *>(&o1), *f2 = reinterpret_cast<float *>(&o2);
-        const uint32_t rowkey = drop_rowkey(seed, 0, orow);
-#pragma unroll
-        for (int c = 0; c < CPL; ++c) {
-          const float xh = LN ? (acc[r][c] - mean) * rs : acc[r][c];
-          const float u = LN ? fmaf(xh, gam[c], bet[c]) : xh;
-          float v = fmaxf(u, 0.f);
-          if (a.drop_p > 0.f) {
-            const bool keep = drop_keep(rowkey, CPL * lane + c, drop_thr);
-            v = keep ? v * keep_scale : 0.f;
-          }
-          f1[c] = xh; f2[c] = v;
-        }
-        if (a.xhat) *reinterpret_cast<typename VecT<CPL>::T *>(a.xhat + (size_t)orow * H + CPL * lane) = o1;
-        *reinterpret_cast<typename VecT<CPL>::T *>(a.act + (size_t)orow * H + CPL * lane) = o2;
-      }
-    }
+    for (int r = 0; r < R; ++r)
+      if (r < nv) l1_row_epilogue<CPL, LN>(a, dr, acc[r], gam, bet, row + r, lane);
   }
 }
 

@@ -7,7 +7,6 @@
 
 namespace stdadk {
 
-constexpr int BW_T = 256;        // 4 waves = 4 knots per workgroup
 constexpr int BW_LIST = 64;      // compacted candidates per flush
 
 // d phi / d r as autograd differentiates the forward formulas (compact-support bases of this path)
@@ -35,19 +34,9 @@ __device__ __forceinline__ float l1_window_bwd_body(const L1BwdArgs &a, const in
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int k;
   if (a.xcd_slots > 0) {
-    // XCD-striped order (see l1_window_bwd_multi_body): XCD block & 7 owns the grid rows [x side/8, (x+1) side/8)
-    // of every level
-    const int x = block & 7;
-    int q = (block >> 3) * (BW_T / 64) + wave, l = 0, r0 = 0;
-    for (; l < a.g.n_levels; ++l) {
-      const int side = a.g.side[l];
-      r0 = (x * side) >> 3;
-      const int np = ((((x + 1) * side) >> 3) - r0) * side;
-      if (q < np) break;
-      q -= np;
-    }
-    if (l >= a.g.n_levels) return 0.f;
-    k = a.g.off[l] + r0 * a.g.side[l] + q;            // q = (ix - r0) * side + iy
+    const XcdGroup s = xcd_group_of(a.g, 1, block, wave);
+    if (s.l >= a.g.n_levels) return 0.f;
+    k = a.g.off[s.l] + s.r0 * a.g.side[s.l] + s.q;    // q = (ix - r0) * side + iy
   } else {
     k = block * (BW_T / 64) + wave;                   // knots in table order: level 0 (coarsest) first
     if (k >= a.g.Ks) return 0.f;
@@ -64,7 +53,7 @@ __device__ __forceinline__ float l1_window_bwd_body(const L1BwdArgs &a, const in
   const int cx_hi = min(floor_clamp((kcx + r) * (float)G, G) + 1, G - 1);
   const int cy_lo = max(floor_clamp((kcy - r) * (float)G, G) - 1, 0);
   const int cy_hi = min(floor_clamp((kcy + r) * (float)G, G) + 1, G - 1);
-  const uint64_t below = (lane == 0) ? 0ULL : (~0ULL >> (64 - lane));
+  const uint64_t below = lanes_below(lane);
 
   float acc[CPL];
   float qacc[KNOTS ? 3 : 1][CPL];
@@ -103,80 +92,50 @@ __device__ __forceinline__ float l1_window_bwd_body(const L1BwdArgs &a, const in
     }
   };
 
-  // The sorted-observation segments of up to 64 cell columns are fetched by 64 lanes at once and
-  // walked as ONE flat candidate list (same order as column by column), so a knot's ~40 candidates
-  // cost two dependent memory round trips instead of two per column.
-  for (int cxb = cx_lo; cxb <= cx_hi; cxb += 64) {
-    const int cxl = cxb + lane;
-    int seg0 = 0, seg1 = 0;
-    if (cxl <= cx_hi) { seg0 = a.cell_start[cxl * G + cy_lo]; seg1 = a.cell_start[cxl * G + cy_hi + 1]; }
-    int incl = seg1 - seg0;                       // inclusive prefix of the segment lengths
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += u;
+  walk_cell_runs(a.cell_start, G, cx_lo, cx_hi, cy_lo, cy_hi, lane, [&](int i, bool valid) {
+    float phi = 0.f;
+    float q0 = 0.f, q1 = 0.f, q2 = 0.f;
+    if (valid) {
+      if (KNOTS) {
+        const float dx = a.xs[i] - kcx, dy = a.ys[i] - kcy;
+        const float d = __builtin_amdgcn_sqrtf(fmaf(dx, dx, dy * dy));
+        const float rr = d * ksc;
+        phi = basis_eval<BASIS>(rr);
+        const float gp = basis_prime_cs<BASIS>(rr);
+        const float qd = d > 0.f ? gp * ksc / d : 0.f;      // cdist's backward: no pull at zero distance
+        q0 = -qd * dx; q1 = -qd * dy; q2 = -gp * rr;
+      } else {
+        phi = phi_eval<BASIS>(a.xs[i], a.ys[i], kcx, kcy, ksc);
+      }
     }
-    const int total = __shfl(incl, 63, 64);
-    for (int f0 = 0; f0 < total; f0 += 64) {
-      const int f = f0 + lane;
-      // segment j with incl[j-1] <= f < incl[j]: first lane whose inclusive prefix exceeds f
-      int lo = 0;
-#pragma unroll
-      for (int st = 32; st > 0; st >>= 1) {
-        const int probe = __shfl(incl, lo + st - 1, 64);
-        if (probe <= f) lo += st;
+    const Compacted c = compact(phi != 0.f, below);
+    if (n + c.m > BW_LIST) {      // not enough room: flush the full groups of 8, keep the remainder
+      __builtin_amdgcn_wave_barrier();
+      const int full = n & ~7;
+      flush(full);
+      __builtin_amdgcn_wave_barrier();
+      const int rem = n - full;
+      float tp = 0.f; int ti = 0;
+      float tq[3] = {0.f, 0.f, 0.f};
+      if (lane < rem) {
+        tp = my_phi[full + lane]; ti = my_idx[full + lane];
+        if (KNOTS) { tq[0] = lq[0][wave][full + lane]; tq[1] = lq[1][wave][full + lane]; tq[2] = lq[2][wave][full + lane]; }
       }
-      const int jl = lo < 63 ? lo : 63;
-      const int pin = __shfl(incl, jl, 64);
-      const int pl = __shfl(seg1 - seg0, jl, 64);
-      const int ps0 = __shfl(seg0, jl, 64);
-      const int i = ps0 + (f - (pin - pl));
-      const int s1 = f < total ? i + 1 : i;       // keeps the `i < s1` form of the validity test below
-      float phi = 0.f;
-      float q0 = 0.f, q1 = 0.f, q2 = 0.f;
-      if (i < s1) {
-        if (KNOTS) {
-          const float dx = a.xs[i] - kcx, dy = a.ys[i] - kcy;
-          const float d = __builtin_amdgcn_sqrtf(fmaf(dx, dx, dy * dy));
-          const float rr = d * ksc;
-          phi = basis_eval<BASIS>(rr);
-          const float gp = basis_prime_cs<BASIS>(rr);
-          const float qd = d > 0.f ? gp * ksc / d : 0.f;      // cdist's backward: no pull at zero distance
-          q0 = -qd * dx; q1 = -qd * dy; q2 = -gp * rr;
-        } else {
-          phi = phi_eval<BASIS>(a.xs[i], a.ys[i], kcx, kcy, ksc);
-        }
+      __builtin_amdgcn_wave_barrier();
+      if (lane < rem) {
+        my_phi[lane] = tp; my_idx[lane] = ti;
+        if (KNOTS) { lq[0][wave][lane] = tq[0]; lq[1][wave][lane] = tq[1]; lq[2][wave][lane] = tq[2]; }
       }
-      const uint64_t mask = __ballot(phi != 0.f);
-      const int m = __popcll(mask);
-      if (n + m > BW_LIST) {      // not enough room: flush the full groups of 8, keep the remainder
-        __builtin_amdgcn_wave_barrier();
-        const int full = n & ~7;
-        flush(full);
-        __builtin_amdgcn_wave_barrier();
-        const int rem = n - full;
-        float tp = 0.f; int ti = 0;
-        float tq[3] = {0.f, 0.f, 0.f};
-        if (lane < rem) {
-          tp = my_phi[full + lane]; ti = my_idx[full + lane];
-          if (KNOTS) { tq[0] = lq[0][wave][full + lane]; tq[1] = lq[1][wave][full + lane]; tq[2] = lq[2][wave][full + lane]; }
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (lane < rem) {
-          my_phi[lane] = tp; my_idx[lane] = ti;
-          if (KNOTS) { lq[0][wave][lane] = tq[0]; lq[1][wave][lane] = tq[1]; lq[2][wave][lane] = tq[2]; }
-        }
-        n = rem;
-      }
-      if (phi != 0.f) {
-        const int pos = n + __popcll(mask & below);
-        my_phi[pos] = phi;
-        my_idx[pos] = i;
-        if (KNOTS) { lq[0][wave][pos] = q0; lq[1][wave][pos] = q1; lq[2][wave][pos] = q2; }
-      }
-      n += m;
+      n = rem;
     }
-  }
+    if (phi != 0.f) {
+      const int pos = n + c.pos;
+      my_phi[pos] = phi;
+      my_idx[pos] = i;
+      if (KNOTS) { lq[0][wave][pos] = q0; lq[1][wave][pos] = q1; lq[2][wave][pos] = q2; }
+    }
+    n += c.m;
+  });
   // final flush, zero-padded to a multiple of 8 (row 0 of dZ is a valid address)
   const int npad = (n + 7) & ~7;
   if (lane < npad - n) {
@@ -198,11 +157,7 @@ __device__ __forceinline__ float l1_window_bwd_body(const L1BwdArgs &a, const in
     }
   }
 
-  typename VecT<CPL>::T o;
-  float *f = reinterpret_cast<float *>(&o);
-#pragma unroll
-  for (int c = 0; c < CPL; ++c) f[c] = acc[c];
-  *reinterpret_cast<typename VecT<CPL>::T *>(a.dW0T + (size_t)(a.g.p + k) * H + CPL * lane) = o;
+  store_vec<CPL>(a.dW0T + (size_t)(a.g.p + k) * H + CPL * lane, acc);
   float sq = 0.f;
 #pragma unroll
   for (int c = 0; c < CPL; ++c) sq = fmaf(acc[c], acc[c], sq);
@@ -210,54 +165,37 @@ __device__ __forceinline__ float l1_window_bwd_body(const L1BwdArgs &a, const in
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// NK = 2 or 4 neighbouring knots per wave (fixed grid knots): knots (ix, iy), (ix, iy + 1) [and (ix + 1, iy),
-// (ix + 1, iy + 1)] of a level see almost the same observations (supports of 5 spacings, one spacing apart), so
-// the candidates are walked once over the union of the supports, a dZ row is fetched once and feeds all NK
-// accumulators.  Every knot still sums its own non-zero observations in sorted order and fmaf(0, dz, acc) == acc,
-// so the rows of dW0^T are bit-identical to the one-knot-per-wave body.  Groups: level by level, ceil(side / 2)
-// pairs per grid row (NK = 2) or ceil(side / 2)^2 blocks of 2 x 2 (NK = 4); knots past the edge of an odd grid
-// are absent.  knot_group_count() in window.hip counts the groups for the launch.
+// Two neighbouring knots per wave (fixed grid knots): knots (ix, iy), (ix, iy + 1) of a level see almost the same
+// observations (supports of 5 spacings, one spacing apart), so the candidates are walked once over the union of the
+// supports, a dZ row is fetched once and feeds both accumulators.  Every knot still sums its own non-zero observations
+// in sorted order and fmaf(0, dz, acc) == acc, so the rows of dW0^T are bit-identical to the one-knot-per-wave body.
+// Groups: level by level, ceil(side / 2) pairs per grid row; the knot past the edge of an odd grid is absent.
+// knot_plan() in window.hip counts the groups for the launch.
 // Returns this lane's share of the squares of the rows its wave wrote, as l1_window_bwd_body.
-template <int CPL, int BASIS, int NK>
+template <int CPL, int BASIS>
 __device__ __forceinline__ float l1_window_bwd_multi_body(const L1BwdArgs &a, const int block) {
   constexpr int H = 64 * CPL;
-  constexpr int NX = NK / 2;                          // knots along ix
+  constexpr int NK = 2;
   __shared__ float lphi[BW_T / 64][NK][BW_LIST + 8];
   __shared__ int lidx[BW_T / 64][BW_LIST + 8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int l = 0, ix, iy;
-  if (NX == 1 && a.xcd_slots > 0) {
-    // XCD-aware order: workgroup `block` runs on XCD block & 7 (round-robin dispatch; the launch pads the
-    // blocks before the knot groups to a multiple of 8).  XCD x owns the grid rows [x side/8, (x+1) side/8) of
-    // every level: its knots see the observations of one stripe of the domain (+ halo), a contiguous eighth of
-    // the cell-sorted dZ rows, so each XCD's L2 fetches about 1/5 of dZ_0 instead of all of it.
-    const int x = block & 7;
-    int q = (block >> 3) * (BW_T / 64) + wave;        // group index inside XCD x's list, level by level
-    int r0 = 0;
-    for (; l < a.g.n_levels; ++l) {
-      const int side = a.g.side[l], hp = (side + 1) >> 1;
-      r0 = (x * side) >> 3;
-      const int np = ((((x + 1) * side) >> 3) - r0) * hp;
-      if (q < np) break;
-      q -= np;
-    }
-    if (l >= a.g.n_levels) return 0.f;
-    const int hp = (a.g.side[l] + 1) >> 1;
-    const int gx = q / hp;
-    ix = r0 + gx; iy = 2 * (q - gx * hp);
+  int l, ix, q;
+  if (a.xcd_slots > 0) {
+    const XcdGroup s = xcd_group_of(a.g, NK, block, wave);
+    l = s.l; ix = s.r0; q = s.q;
   } else {
-    int q = block * (BW_T / 64) + wave;               // group index, level by level
+    l = 0; ix = 0;
+    q = block * (BW_T / 64) + wave;                   // group index, level by level
     for (; l < a.g.n_levels; ++l) {
-      const int hp = (a.g.side[l] + 1) >> 1;
-      const int np = (NX == 2 ? hp : a.g.side[l]) * hp;
+      const int np = a.g.side[l] * knot_groups_per_row(a.g.side[l], NK);
       if (q < np) break;
       q -= np;
     }
-    if (l >= a.g.n_levels) return 0.f;
-    const int hp = (a.g.side[l] + 1) >> 1;
-    const int gx = q / hp;
-    ix = NX * gx; iy = 2 * (q - gx * hp);
   }
+  if (l >= a.g.n_levels) return 0.f;
+  const int hp = knot_groups_per_row(a.g.side[l], NK);
+  ix += q / hp;
+  const int iy = 2 * (q % hp);
   const int side = a.g.side[l];
   int kk[NK];
   bool has[NK];
@@ -265,9 +203,8 @@ __device__ __forceinline__ float l1_window_bwd_multi_body(const L1BwdArgs &a, co
   float xlo = 3.0e38f, xhi = -3.0e38f, ylo = 3.0e38f, yhi = -3.0e38f;
 #pragma unroll
   for (int j = 0; j < NK; ++j) {
-    const int dx = j >> 1, dy = j & 1;
-    has[j] = ix + dx < side && iy + dy < side;
-    kk[j] = a.g.off[l] + (has[j] ? (ix + dx) * side + iy + dy : ix * side + iy);
+    has[j] = iy + j < side;
+    kk[j] = a.g.off[l] + ix * side + iy + (has[j] ? j : 0);
     kx[j] = a.g.centers[2 * kk[j]]; ky[j] = a.g.centers[2 * kk[j] + 1];
     const float bw = a.g.bw[kk[j]];
     ksc[j] = knot_scale(bw, a.g.cal);
@@ -282,7 +219,7 @@ __device__ __forceinline__ float l1_window_bwd_multi_body(const L1BwdArgs &a, co
   const int cx_hi = min(floor_clamp(xhi * (float)G, G) + 1, G - 1);
   const int cy_lo = max(floor_clamp(ylo * (float)G, G) - 1, 0);
   const int cy_hi = min(floor_clamp(yhi * (float)G, G) + 1, G - 1);
-  const uint64_t below = (lane == 0) ? 0ULL : (~0ULL >> (64 - lane));
+  const uint64_t below = lanes_below(lane);
 
   float acc[NK][CPL];
 #pragma unroll
@@ -311,75 +248,50 @@ __device__ __forceinline__ float l1_window_bwd_multi_body(const L1BwdArgs &a, co
     }
   };
 
-  for (int cxb = cx_lo; cxb <= cx_hi; cxb += 64) {
-    const int cxl = cxb + lane;
-    int seg0 = 0, seg1 = 0;
-    if (cxl <= cx_hi) { seg0 = a.cell_start[cxl * G + cy_lo]; seg1 = a.cell_start[cxl * G + cy_hi + 1]; }
-    int incl = seg1 - seg0;
+  walk_cell_runs(a.cell_start, G, cx_lo, cx_hi, cy_lo, cy_hi, lane, [&](int i, bool valid) {
+    float pv[NK];
+    bool any = false;
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += u;
+    for (int j = 0; j < NK; ++j) pv[j] = 0.f;
+    if (valid) {
+      const float x = a.xs[i], y = a.ys[i];
+#pragma unroll
+      for (int j = 0; j < NK; ++j) {
+        pv[j] = has[j] ? phi_eval<BASIS>(x, y, kx[j], ky[j], ksc[j]) : 0.f;
+        any = any || pv[j] != 0.f;
+      }
     }
-    const int total = __shfl(incl, 63, 64);
-    for (int f0 = 0; f0 < total; f0 += 64) {
-      const int f = f0 + lane;
-      int lo = 0;
+    const Compacted c = compact(any, below);
+    if (n + c.m > BW_LIST) {      // not enough room: flush the full groups of 8, keep the remainder
+      __builtin_amdgcn_wave_barrier();
+      const int full = n & ~7;
+      flush(full);
+      __builtin_amdgcn_wave_barrier();
+      const int rem = n - full;
+      float tp[NK]; int ti = 0;
 #pragma unroll
-      for (int st = 32; st > 0; st >>= 1) {
-        const int probe = __shfl(incl, lo + st - 1, 64);
-        if (probe <= f) lo += st;
+      for (int j = 0; j < NK; ++j) tp[j] = 0.f;
+      if (lane < rem) {
+#pragma unroll
+        for (int j = 0; j < NK; ++j) tp[j] = lphi[wave][j][full + lane];
+        ti = my_idx[full + lane];
       }
-      const int jl = lo < 63 ? lo : 63;
-      const int pin = __shfl(incl, jl, 64);
-      const int pl = __shfl(seg1 - seg0, jl, 64);
-      const int ps0 = __shfl(seg0, jl, 64);
-      const int i = ps0 + (f - (pin - pl));
-      float pv[NK];
-      bool any = false;
+      __builtin_amdgcn_wave_barrier();
+      if (lane < rem) {
 #pragma unroll
-      for (int j = 0; j < NK; ++j) pv[j] = 0.f;
-      if (f < total) {
-        const float x = a.xs[i], y = a.ys[i];
-#pragma unroll
-        for (int j = 0; j < NK; ++j) {
-          pv[j] = has[j] ? phi_eval<BASIS>(x, y, kx[j], ky[j], ksc[j]) : 0.f;
-          any = any || pv[j] != 0.f;
-        }
+        for (int j = 0; j < NK; ++j) lphi[wave][j][lane] = tp[j];
+        my_idx[lane] = ti;
       }
-      const uint64_t mask = __ballot(any);
-      const int m = __popcll(mask);
-      if (n + m > BW_LIST) {      // not enough room: flush the full groups of 8, keep the remainder
-        __builtin_amdgcn_wave_barrier();
-        const int full = n & ~7;
-        flush(full);
-        __builtin_amdgcn_wave_barrier();
-        const int rem = n - full;
-        float tp[NK]; int ti = 0;
-#pragma unroll
-        for (int j = 0; j < NK; ++j) tp[j] = 0.f;
-        if (lane < rem) {
-#pragma unroll
-          for (int j = 0; j < NK; ++j) tp[j] = lphi[wave][j][full + lane];
-          ti = my_idx[full + lane];
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (lane < rem) {
-#pragma unroll
-          for (int j = 0; j < NK; ++j) lphi[wave][j][lane] = tp[j];
-          my_idx[lane] = ti;
-        }
-        n = rem;
-      }
-      if (any) {
-        const int pos = n + __popcll(mask & below);
-#pragma unroll
-        for (int j = 0; j < NK; ++j) lphi[wave][j][pos] = pv[j];
-        my_idx[pos] = i;
-      }
-      n += m;
+      n = rem;
     }
-  }
+    if (any) {
+      const int pos = n + c.pos;
+#pragma unroll
+      for (int j = 0; j < NK; ++j) lphi[wave][j][pos] = pv[j];
+      my_idx[pos] = i;
+    }
+    n += c.m;
+  });
   const int npad = (n + 7) & ~7;
   if (lane < npad - n) {
 #pragma unroll
@@ -393,11 +305,9 @@ __device__ __forceinline__ float l1_window_bwd_multi_body(const L1BwdArgs &a, co
 #pragma unroll
   for (int j = 0; j < NK; ++j) {
     if (has[j]) {
-      typename VecT<CPL>::T o;
-      float *fo = reinterpret_cast<float *>(&o);
 #pragma unroll
-      for (int c = 0; c < CPL; ++c) { fo[c] = acc[j][c]; sq = fmaf(acc[j][c], acc[j][c], sq); }
-      *reinterpret_cast<typename VecT<CPL>::T *>(a.dW0T + (size_t)(a.g.p + kk[j]) * H + CPL * lane) = o;
+      for (int c = 0; c < CPL; ++c) sq = fmaf(acc[j][c], acc[j][c], sq);
+      store_vec<CPL>(a.dW0T + (size_t)(a.g.p + kk[j]) * H + CPL * lane, acc[j]);
     }
   }
   return sq;

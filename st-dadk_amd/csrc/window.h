@@ -83,10 +83,6 @@ struct L1FwdArgs {
 // z0 = [X|phi|psi] W0 + b0 -> LN -> ReLU -> Dropout for sorted observations; also writes psi.
 int l1_window_forward(const L1FwdArgs &a, int basis, bool layernorm, hipStream_t st);
 bool l1_window_supported(int n_levels, int basis, int H, int p, int Kt);
-struct L1BwdArgs;
-int knot_group_count(const GridView &g, int nk);  // groups of the per-knot gather of dW0^T, nk knots per wave
-int knots_per_wave(const L1BwdArgs &a);
-int knot_xcd_slots(const GridView &g, int nk);    // workgroups per XCD of the XCD-striped group order, 0 = off
 
 struct L1BwdArgs {
   GridView g;
@@ -96,7 +92,7 @@ struct L1BwdArgs {
   const float *dZ;      // [B][H] sorted order
   float *dW0T;          // [D][H]
   int xcd_slots = 0;    // > 0: two-knots-per-wave groups in XCD-striped order, this many workgroups per XCD
-                        // (set by the launchers, see knot_xcd_slots)
+                        // (set by the launchers, see knot_plan)
   // learnable knots: W0^T (rows p + k) and the raw knot sums [3][Ks] (d cx, d cy, d log_bw) this kernel
   // also produces; NULL = fixed knots
   const float *W0T;
@@ -121,6 +117,11 @@ int knot_halo(const GridView &g, float *halo, hipStream_t st, const float *log_b
 // dW0T[p + k, :] = sum_b phi[b,k] dZ[b,:] for every spatial knot k (each knot row owned by one
 // wave: no atomics, summation in sorted-observation order => bitwise reproducible).
 int l1_window_backward(L1BwdArgs a, int basis, hipStream_t st);
+
+// the knot part of a launch of the per-knot gather: knots per wave (1 or 2), workgroups per XCD of the XCD-striped
+// group order (0 = table order) and the number of knot workgroups
+struct KnotPlan { int nk, xcd_slots, blocks; };
+KnotPlan knot_plan(const L1BwdArgs &a);
 
 }  // namespace stdadk
 #include "gemm_f32.h"

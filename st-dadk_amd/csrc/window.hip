@@ -460,68 +460,58 @@ __global__ __launch_bounds__(BW_T) void l1_window_bwd_kernel(L1BwdArgs a) {
   l1_window_bwd_body<CPL, BASIS, KNOTS>(a, (int)blockIdx.x);
 }
 
-template <int CPL, int BASIS, int NK>
+template <int CPL, int BASIS>
 __global__ __launch_bounds__(BW_T) void l1_window_bwd_multi_kernel(L1BwdArgs a) {
-  l1_window_bwd_multi_body<CPL, BASIS, NK>(a, (int)blockIdx.x);
+  l1_window_bwd_multi_body<CPL, BASIS>(a, (int)blockIdx.x);
 }
 
-// groups of the per-knot gather with nk knots per wave: level by level, ceil(side / 2) pairs per grid row
-// (nk = 2) or ceil(side / 2)^2 blocks of 2 x 2 (nk = 4)
-int knot_group_count(const GridView &g, int nk) {
-  if (nk <= 1) return g.Ks;
-  int n = 0;
-  for (int l = 0; l < g.n_levels; ++l) {
-    const int hp = (g.side[l] + 1) / 2;
-    n += (nk == 4 ? hp : g.side[l]) * hp;
+// Knots per wave: learnable and scattered knots 1; fixed grid knots 2 (environment STDADK_KNOTS_PER_WAVE = 1 | 2
+// overrides, diagnostic).  Measured on MI355X, C2 model: 2 per wave is -2.5 us on the merged weight-gradient launch
+// at B = 4096 and -14 % on it at B = 65 536; blocks of 2 x 2 were slower than pairs up to B = 16 384 and no faster
+// at 65 536.
+// Grid knots go in XCD-striped order (xcd_group_of in l1_walk.h): workgroups per XCD = the longest of the eight
+// lists (equal when every side is a multiple of 8); environment STDADK_KNOT_XCD=0 switches the striping off
+// (diagnostic).  Otherwise the groups go in table order, level by level: the knots, or ceil(side / 2) pairs per
+// grid row.
+KnotPlan knot_plan(const L1BwdArgs &a) {
+  const GridView &g = a.g;
+  KnotPlan p = {1, 0, 0};
+  if (!a.kpart && !g.scattered) {
+    const char *e = getenv("STDADK_KNOTS_PER_WAVE");
+    p.nk = (e && atoi(e) == 1) ? 1 : 2;
   }
-  return n;
-}
-
-// XCD-striped order of the knot groups (nk = 1 or 2 knots per wave): workgroups per XCD = the longest of the eight lists (equal when every
-// side is a multiple of 8); environment STDADK_KNOT_XCD=0 switches the striping off (diagnostic)
-int knot_xcd_slots(const GridView &g, int nk) {
   const char *e = getenv("STDADK_KNOT_XCD");
-  if ((e && e[0] == '0') || (nk != 1 && nk != 2) || g.scattered) return 0;
-  int most = 0;
-  for (int x = 0; x < 8; ++x) {
-    int n = 0;
-    for (int l = 0; l < g.n_levels; ++l) {
-      const int side = g.side[l];
-      n += ((((x + 1) * side) >> 3) - ((x * side) >> 3)) * (nk == 2 ? (side + 1) / 2 : side);
+  if (!(e && e[0] == '0') && !g.scattered) {
+    int most = 0;
+    for (int x = 0; x < 8; ++x) {
+      int n = 0;
+      for (int l = 0; l < g.n_levels; ++l) n += xcd_level_groups(x, g.side[l], p.nk);
+      most = n > most ? n : most;
     }
-    most = n > most ? n : most;
+    p.xcd_slots = (int)ceil_div(most, BW_T / 64);
   }
-  return (int)ceil_div(most, BW_T / 64);
-}
-
-// knots per wave of the per-knot gather: learnable knots 1; fixed grid knots 2 (environment
-// STDADK_KNOTS_PER_WAVE = 1 | 2 overrides, diagnostic).  Measured on MI355X, C2 model: 2 per wave is
-// -2.5 us on the merged weight-gradient launch at B = 4096 and -14 % on it at B = 65 536; blocks of 2 x 2
-// (the body supports NK = 4) are slower than pairs up to B = 16 384 and no faster at 65 536.
-int knots_per_wave(const L1BwdArgs &a) {
-  if (a.kpart || a.g.scattered) return 1;
-  int nk = 2;
-  if (const char *e = getenv("STDADK_KNOTS_PER_WAVE")) {
-    const int v = atoi(e);
-    if (v == 1 || v == 2) nk = v;
+  int groups = g.Ks;
+  if (p.nk == 2) {
+    groups = 0;
+    for (int l = 0; l < g.n_levels; ++l) groups += g.side[l] * knot_groups_per_row(g.side[l], 2);
   }
-  return nk;
+  p.blocks = p.xcd_slots > 0 ? 8 * p.xcd_slots : (int)ceil_div(groups, BW_T / 64);
+  return p;
 }
 
 int l1_window_backward(L1BwdArgs a, int basis, hipStream_t st) {
   STDADK_REQUIRE(a.G <= 256, STDADK_E_ARG, "l1_window_backward: G too large");
   STDADK_REQUIRE((int64_t)a.B * a.H < (1ll << 32), STDADK_E_ARG, "l1_window_backward: B*H exceeds 32-bit offsets");
-  const int nk = knots_per_wave(a);
-  a.xcd_slots = knot_xcd_slots(a.g, nk);
-  const unsigned grid = a.xcd_slots > 0 ? 8u * (unsigned)a.xcd_slots
-                                        : (unsigned)ceil_div(knot_group_count(a.g, nk), BW_T / 64);
+  const KnotPlan kp = knot_plan(a);
+  a.xcd_slots = kp.xcd_slots;
+  const unsigned grid = (unsigned)kp.blocks;
   STDADK_REQUIRE(!a.kpart || a.W0T, STDADK_E_ARG, "l1_window_backward: knot sums need W0^T");
 #define GO(CPL_, BS_)                                                                                        \
   do {                                                                                                       \
     if (a.kpart) STDADK_LAUNCH_NAMED("l1_window_bwd_kernel<knots>", (l1_window_bwd_kernel<CPL_, BS_, true>), \
                                      dim3(grid), dim3(BW_T), 0, st, a);                                      \
-    else if (nk == 2) STDADK_LAUNCH_NAMED("l1_window_bwd_kernel", (l1_window_bwd_multi_kernel<CPL_, BS_, 2>), \
-                                          dim3(grid), dim3(BW_T), 0, st, a);                                 \
+    else if (kp.nk == 2) STDADK_LAUNCH_NAMED("l1_window_bwd_kernel", (l1_window_bwd_multi_kernel<CPL_, BS_>), \
+                                             dim3(grid), dim3(BW_T), 0, st, a);                              \
     else STDADK_LAUNCH_NAMED("l1_window_bwd_kernel", (l1_window_bwd_kernel<CPL_, BS_, false>), dim3(grid),   \
                              dim3(BW_T), 0, st, a);                                                          \
   } while (0)

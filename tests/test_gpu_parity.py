@@ -1306,13 +1306,10 @@ def test_pipelined_batch_preparation_equals_inline(name):
     assert abs(res[0][1] - res[1][1]) <= 1e-6 * abs(res[0][1])
 
 
-def test_coarse_knots_learnable_large_batch():
-    """B = 3000 on the 227-knot table: every knot sees hundreds to thousands of rows (long per-knot
-    gathers, many list flushes); values and all gradients, knots included, against the oracle and
-    bit-identical between two runs.  (Splitting such knots over several waves was measured and is NOT
-    done: at B = 65 536 it made the gather 15 % slower — the kernel is L2-throughput-bound there.)"""
+def check_coarse_learnable_batch(cfg):
+    """Window path with learnable (perturbed) knots on a large batch: values and all gradients, knots included,
+    against the float64 oracle, and bit-identical between two runs."""
     from stnf.models import STInterpMLP
-    cfg = dict(cases.MODEL_CASES["default227"], B=3000, seed=71)
     d = dev()
     X, coords, t, y = cases.make_inputs(cfg)
     st = cases.make_state(cfg)
@@ -1342,6 +1339,25 @@ def test_coarse_knots_learnable_large_batch():
     assert np.abs(yp.detach().cpu().numpy() - yo).max() <= TOL * max(1.0, np.abs(yo).max())
     for k in go:
         assert rel_l2(outs[0][k].cpu().numpy(), go[k]) <= 2e-5, (k, rel_l2(outs[0][k].cpu().numpy(), go[k]))
+
+
+def test_coarse_knots_learnable_large_batch():
+    """B = 3000 on the 227-knot table: every knot sees hundreds to thousands of rows (long per-knot
+    gathers, many list flushes); values and all gradients, knots included, against the oracle and
+    bit-identical between two runs.  (Splitting such knots over several waves was measured and is NOT
+    done: at B = 65 536 it made the gather 15 % slower — the kernel is L2-throughput-bound there.)"""
+    check_coarse_learnable_batch(dict(cases.MODEL_CASES["default227"], B=3000, seed=71))
+
+
+# 4099 rows are binned on a 128 x 128 cell grid, where the support square of a knot of the 8 x 8 level (radius
+# 2.5 / 7 of the domain) spans about 91 cell columns: the per-knot gather takes a second pass of 64 columns
+COARSE_B4099 = dict(p=0, k_spatial_centers=[64, 144], k_temporal_centers=[10, 15], hidden_dims=[256, 128],
+                    layernorm=True, basis="wendland", output_dim=1, B=4099, seed=73)
+
+
+def test_coarse_knots_learnable_second_column_pass():
+    """The same comparison where a knot's support square spans more than 64 cell columns (see COARSE_B4099)."""
+    check_coarse_learnable_batch(COARSE_B4099)
 
 
 def test_run_epoch_equals_manual_loop():
@@ -1646,17 +1662,20 @@ def test_layer0_observation_groups_are_bit_identical(name, monkeypatch):
             assert torch.equal(ga, gb), grp
 
 
-@pytest.mark.parametrize("name", ["default227", "default227_tri", "c2_b257", "c2_b257_noln", "four_levels"])
+@pytest.mark.parametrize("name", ["default227", "default227_tri", "c2_b257", "c2_b257_noln", "four_levels",
+                                  "coarse_b4099"])
 def test_knot_groups_are_bit_identical(name, monkeypatch):
     """Per-knot gather of dW0^T with two neighbouring knots per wave (one fetch of a dZ row feeds both; the
     default for fixed knots) against one knot per wave: every knot sums its own observations in the same
     order, so the gradients are bit-identical -- through the split backward (own kernel, module autograd) and
-    through the engine step (merged weight-gradient kernel); odd grid sides leave the last knot of a row alone."""
+    through the engine step (merged weight-gradient kernel); odd grid sides leave the last knot of a row alone;
+    coarse_b4099 walks more than 64 cell columns per knot (see COARSE_B4099)."""
     from stnf.engine import TrainStep
-    cfg = cases.MODEL_CASES[name] if name in cases.MODEL_CASES else dict(FOUR_LEVELS, p=0)
+    cfg = cases.MODEL_CASES[name] if name in cases.MODEL_CASES else \
+        COARSE_B4099 if name == "coarse_b4099" else dict(FOUR_LEVELS, p=0)
     d = dev()
     rs = np.random.RandomState(6)
-    n = 1501
+    n = 4099 if name == "coarse_b4099" else 1501
     c2 = torch.from_numpy(np.concatenate([rs.uniform(-0.05, 1.05, (n // 2, 2)), 0.6 + 0.03 * rs.standard_normal((n - n // 2, 2))])
                           .astype(np.float32)).to(d)
     t2 = torch.from_numpy(rs.uniform(0, 1, (n, 1)).astype(np.float32)).to(d)
