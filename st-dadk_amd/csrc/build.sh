@@ -5,9 +5,17 @@ cd "$(dirname "$0")"
 mkdir -p ../lib obj
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function ${STDADK_EXTRA_FLAGS:-}"
+# an object is out of date when its source, ANY header of this directory or the public header is newer than it
+stale() {  # stale <object> <source>
+  local dep
+  for dep in "$2" *.h ../../include/stdadk.h; do
+    if [ ! -f "$1" ] || [ "$dep" -nt "$1" ]; then return 0; fi
+  done
+  return 1
+}
 pids=()
 for f in rbf_build gemm_f32 mlp optim window tail loss knots fused_step dw_all sparsity eval grid_score; do
-  if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ common.h -nt obj/$f.o ] || [ gemm_f32.h -nt obj/$f.o ] || [ window.h -nt obj/$f.o ] || [ tail.h -nt obj/$f.o ] || [ loss.h -nt obj/$f.o ] || [ knots.h -nt obj/$f.o ] || [ l1_body.h -nt obj/$f.o ] || [ l1_walk.h -nt obj/$f.o ] || [ bin_body.h -nt obj/$f.o ] || [ optim.h -nt obj/$f.o ] || [ tail_body.h -nt obj/$f.o ] || [ gemm_body.h -nt obj/$f.o ] || [ l1_bwd_body.h -nt obj/$f.o ] || [ basis.h -nt obj/$f.o ] || [ ../../include/stdadk.h -nt obj/$f.o ]; then
+  if stale obj/$f.o $f.hip; then
     $HIPCC $FLAGS -c $f.hip -o obj/$f.o &
     pids+=($!)
   fi

@@ -67,6 +67,20 @@ static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t
 
 constexpr int kWave = 64;
 
+typedef unsigned short u16;            // a bf16 value as stored (weight copies, LDS images)
+
+// Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding
+// GLOBAL access (vmcnt(0)); the kernels that use this one read no global data written by another wave.
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
+  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+  const bf2 v = {(__bf16)a, (__bf16)b};       // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
+  return __builtin_bit_cast(uint32_t, v);
+}
+
 // Sum over the 64 lanes of a wave, the same value in every lane.  Data-parallel primitives (DPP) inside the rows of
 // 16 lanes -- quad swaps, then the half-row and row mirrors: four v_add_f32_dpp, no LDS crossbar -- then the row sums
 // chained over the four rows (row_bcast15 / row_bcast31) and lane 63 read back through an SGPR.  The butterfly through

@@ -32,6 +32,26 @@ struct TileGeom {
   static constexpr int ELEMS = ROWS * BK / GT;  // floats per thread per stage
 };
 
+// VEC contiguous floats as one access
+template <int VEC>
+__device__ __forceinline__ void load_floats(const float *src, float *reg) {
+  if (VEC == 4) {
+    const float4 v = *reinterpret_cast<const float4 *>(src);
+    reg[0] = v.x; reg[1] = v.y; reg[2] = v.z; reg[3] = v.w;
+  } else if (VEC == 2) {
+    const float2 v = *reinterpret_cast<const float2 *>(src);
+    reg[0] = v.x; reg[1] = v.y;
+  } else {
+    reg[0] = *src;
+  }
+}
+template <int VEC>
+__device__ __forceinline__ void store_floats(float *dst, const float *m) {
+  if (VEC == 4) *reinterpret_cast<float4 *>(dst) = make_float4(m[0], m[1], m[2], m[3]);
+  else if (VEC == 2) *reinterpret_cast<float2 *>(dst) = make_float2(m[0], m[1]);
+  else *dst = m[0];
+}
+
 // Global -> registers for one operand tile.  `r0` first row (m or n) of the tile, `k0` first k.
 // VEC = contiguous floats per load along the operand's contiguous dimension.
 // Every load is UNCONDITIONAL from a clamped, always-valid address (the tile's first row / k when out of range) and
@@ -53,15 +73,7 @@ __device__ __forceinline__ void load_tile(const float *__restrict__ P, int64_t l
       const int k = k0 + (tid % VPR) * VEC;
       const bool rok = (r0 + row) < nrows;
       const float *src = P + (int64_t)(rok ? r0 + row : r0) * ld + (k < kend ? k : k0);
-      if (VEC == 4) {
-        const float4 v = *reinterpret_cast<const float4 *>(src);
-        reg[i * 4 + 0] = v.x; reg[i * 4 + 1] = v.y; reg[i * 4 + 2] = v.z; reg[i * 4 + 3] = v.w;
-      } else if (VEC == 2) {
-        const float2 v = *reinterpret_cast<const float2 *>(src);
-        reg[i * 2 + 0] = v.x; reg[i * 2 + 1] = v.y;
-      } else {
-        reg[i] = *src;
-      }
+      load_floats<VEC>(src, reg + i * VEC);
     }
   } else {
     constexpr int VPR = ROWS / VEC;     // vectors per k-row
@@ -72,15 +84,7 @@ __device__ __forceinline__ void load_tile(const float *__restrict__ P, int64_t l
       const int r = r0 + (tid % VPR) * VEC;
       const bool kok = (k0 + kk) < kend;
       const float *src = P + (int64_t)(kok ? k0 + kk : k0) * ld + (r < nrows ? r : r0);
-      if (VEC == 4) {
-        const float4 v = *reinterpret_cast<const float4 *>(src);
-        reg[i * 4 + 0] = v.x; reg[i * 4 + 1] = v.y; reg[i * 4 + 2] = v.z; reg[i * 4 + 3] = v.w;
-      } else if (VEC == 2) {
-        const float2 v = *reinterpret_cast<const float2 *>(src);
-        reg[i * 2 + 0] = v.x; reg[i * 2 + 1] = v.y;
-      } else {
-        reg[i] = *src;
-      }
+      load_floats<VEC>(src, reg + i * VEC);
     }
   }
 }
@@ -104,9 +108,7 @@ __device__ __forceinline__ void store_tile(float *lds, const float *reg, int r0,
 #pragma unroll
       for (int e = 0; e < VEC; ++e) m[e] = (rok && k0 + kl + e < kend) ? reg[i * VEC + e] : 0.f;
       float *dst = lds + row * STRIDE + kl;
-      if (VEC == 4) *reinterpret_cast<float4 *>(dst) = make_float4(m[0], m[1], m[2], m[3]);
-      else if (VEC == 2) *reinterpret_cast<float2 *>(dst) = make_float2(m[0], m[1]);
-      else *dst = m[0];
+      store_floats<VEC>(dst, m);
     }
   } else {
     constexpr int VPR = ROWS / VEC;
@@ -119,9 +121,7 @@ __device__ __forceinline__ void store_tile(float *lds, const float *reg, int r0,
 #pragma unroll
       for (int e = 0; e < VEC; ++e) m[e] = (kok && r0 + rl + e < nrows) ? reg[i * VEC + e] : 0.f;
       float *dst = lds + kk * STRIDE + rl;
-      if (VEC == 4) *reinterpret_cast<float4 *>(dst) = make_float4(m[0], m[1], m[2], m[3]);
-      else if (VEC == 2) *reinterpret_cast<float2 *>(dst) = make_float2(m[0], m[1]);
-      else *dst = m[0];
+      store_floats<VEC>(dst, m);
     }
   }
 }
@@ -138,11 +138,6 @@ __device__ __forceinline__ void read_frag(const float *lds, int row, int s, int 
 #pragma unroll
     for (int e = 0; e < 4; ++e) f[e] = lds[(8 * s + 4 * h + e) * STRIDE + r];
   }
-}
-
-// workgroup barrier that orders LDS traffic only: __syncthreads() also drains every global access in flight
-__device__ __forceinline__ void gemm_lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
 template <int BM, int BN, bool A_KM, bool B_KM, int VA, int VB, int DEPTH = 1>
@@ -195,13 +190,13 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, int bx, int by
     for (int k0 = kbeg; k0 < kend; k0 += BK) {
       store_tile<BM, A_KM, VA>(As, ra, m0, g.M, k0, kend);
       store_tile<BN, B_KM, VB>(Bs, rb, n0, g.N, k0, kend);
-      gemm_lds_barrier();
+      lds_barrier();
       if (k0 + BK < kend) {
         load_tile<BM, A_KM, VA>(g.A, g.lda, m0, g.M, k0 + BK, kend, ra);
         load_tile<BN, B_KM, VB>(g.B, g.ldb, n0, g.N, k0 + BK, kend, rb);
       }
       mfma_step();
-      gemm_lds_barrier();
+      lds_barrier();
     }
   } else if (kbeg < kend) {
     // DEPTH K steps of operands in flight (ring of register stages, the step loop unrolled over the ring): a short
@@ -221,12 +216,12 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, int bx, int by
         if (k >= kend) break;
         store_tile<BM, A_KM, VA>(As, ra[d], m0, g.M, k, kend);
         store_tile<BN, B_KM, VB>(Bs, rb[d], n0, g.N, k, kend);
-        gemm_lds_barrier();
+        lds_barrier();
         const int kn = k + DEPTH * BK, kc = kn < kend ? kn : kbeg;
         load_tile<BM, A_KM, VA>(g.A, g.lda, m0, g.M, kc, kend, ra[d]);
         load_tile<BN, B_KM, VB>(g.B, g.ldb, n0, g.N, kc, kend, rb[d]);
         mfma_step();
-        gemm_lds_barrier();
+        lds_barrier();
       }
     }
   }
@@ -269,19 +264,12 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, int bx, int by
 // Stride 96 (192 B = 48 banks): the four k-rows of the two blocks a 32-lane half reads fall on eight disjoint
 // 8-bank runs -- conflict-free.
 // ---------------------------------------------------------------------------------------------
-typedef unsigned short hu16;
 typedef short hs16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 hbf16x8 __attribute__((ext_vector_type(8)));
 constexpr int BKH = 64;            // k per stage
 constexpr int HSTRIDE = 96;        // bf16 elements per k-row of an LDS image
 constexpr int GROUP_LDS_FLOATS = (2 * BKH * HSTRIDE * 2) / 4 > TileGeom<64, true>::SIZE * 2 ? (2 * BKH * HSTRIDE * 2) / 4
                                                                                              : TileGeom<64, true>::SIZE * 2;
-
-__device__ __forceinline__ uint32_t h_pack(float a, float b) {
-  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-  const bf2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
 
 // rows r0.. of k-rows k0.. of a K-major fp32 operand into registers: 4 float4 per thread, unconditional RAW loads from
 // clamped addresses; the masks (rows / k beyond the operand) are applied when the values are rounded and written to
@@ -298,7 +286,7 @@ __device__ __forceinline__ void h_load(const float *__restrict__ P, int64_t ld, 
     reg[i] = *reinterpret_cast<const float4 *>(P + (int64_t)(k < kend ? k : k0) * ld + rc);
   }
 }
-__device__ __forceinline__ void h_store(hu16 *lds, const float4 *reg, int r0, int nrows, int k0, int kend) {
+__device__ __forceinline__ void h_store(u16 *lds, const float4 *reg, int r0, int nrows, int k0, int kend) {
   const int tid = threadIdx.x;
   const int r = r0 + (tid & 15) * 4;
 #pragma unroll
@@ -307,13 +295,13 @@ __device__ __forceinline__ void h_store(hu16 *lds, const float4 *reg, int r0, in
     const bool kok = k0 + kk < kend;
     const float x = (kok && r + 0 < nrows) ? reg[i].x : 0.f, y = (kok && r + 1 < nrows) ? reg[i].y : 0.f;
     const float z = (kok && r + 2 < nrows) ? reg[i].z : 0.f, w = (kok && r + 3 < nrows) ? reg[i].w : 0.f;
-    *reinterpret_cast<uint2 *>(lds + kk * HSTRIDE + (tid & 15) * 4) = make_uint2(h_pack(x, y), h_pack(z, w));
+    *reinterpret_cast<uint2 *>(lds + kk * HSTRIDE + (tid & 15) * 4) = make_uint2(pack_bf16(x, y), pack_bf16(z, w));
   }
 }
 // fragment of the 16-deep k-step s for the 32 rows starting at `row`: two transposing reads (k = 8h + 0..3, + 4..7)
-__device__ __forceinline__ hbf16x8 h_frag(const hu16 *lds, int row, int s, int lane) {
+__device__ __forceinline__ hbf16x8 h_frag(const u16 *lds, int row, int s, int lane) {
   const int i = lane & 15, g = lane >> 4;
-  const hu16 *p = lds + (16 * s + 8 * (g >> 1) + (i >> 2)) * HSTRIDE + row + 16 * (g & 1) + 4 * (i & 3);
+  const u16 *p = lds + (16 * s + 8 * (g >> 1) + (i >> 2)) * HSTRIDE + row + 16 * (g & 1) + 4 * (i & 3);
   typedef __attribute__((address_space(3))) hs16x4 lds_s16x4;
   const hs16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)p);
   const hs16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p + 4 * HSTRIDE));
@@ -323,7 +311,7 @@ __device__ __forceinline__ hbf16x8 h_frag(const hu16 *lds, int row, int s, int l
 }
 
 __device__ __forceinline__ void gemm_tn_tile_body_h(const GemmArgs &g, int bx, int by, int bz, float *lds_f) {
-  hu16 *As = reinterpret_cast<hu16 *>(lds_f), *Bs = As + BKH * HSTRIDE;
+  u16 *As = reinterpret_cast<u16 *>(lds_f), *Bs = As + BKH * HSTRIDE;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m0 = by * 64, n0 = bx * 64;
   const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
@@ -343,7 +331,7 @@ __device__ __forceinline__ void gemm_tn_tile_body_h(const GemmArgs &g, int bx, i
   for (int k0 = kbeg; k0 < kend; k0 += BKH) {
     h_store(As, ra, m0, g.M, k0, kend);
     h_store(Bs, rb, n0, g.N, k0, kend);
-    gemm_lds_barrier();
+    lds_barrier();
     if (k0 + BKH < kend) {
       h_load(g.A, g.lda, m0, g.M, k0 + BKH, kend, ra);
       h_load(g.B, g.ldb, n0, g.N, k0 + BKH, kend, rb);
@@ -351,7 +339,7 @@ __device__ __forceinline__ void gemm_tn_tile_body_h(const GemmArgs &g, int bx, i
 #pragma unroll
     for (int s = 0; s < BKH / 16; ++s)
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(h_frag(As, wm, s, lane), h_frag(Bs, wn, s, lane), acc, 0, 0, 0);
-    gemm_lds_barrier();
+    lds_barrier();
   }
   // epilogue as the fp32 tiles: always a slab (grouped jobs)
   float *Cbase = g.slab + (int64_t)bz * g.slab_stride;

@@ -69,12 +69,6 @@ struct AdamArgs {
   ShadowArgs sh;
 };
 
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-  const bf2 v = {(__bf16)a, (__bf16)b};          // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
-  return __builtin_bit_cast(uint32_t, v);
-}
-
 // the four values p of flat elements e .. e+3 into whichever region holds them (regions start and end on
 // multiples of 4 elements and have cols % 4 == 0, so the four share a region and a row)
 __device__ __forceinline__ void shadow_store(const ShadowArgs &sh, int64_t e, float4 p) {

@@ -18,41 +18,17 @@ constexpr int TAIL_WAVES = 16;                // waves per workgroup: one per 16
 constexpr int TAIL_THREADS = 64 * TAIL_WAVES; // threads per workgroup (1024)
 static_assert(16 * TAIL_WAVES == TAIL_MAX_W, "one N tile per wave");
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding
-// GLOBAL store (vmcnt(0)); nothing in these kernels reads global data written by another wave.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-struct BFrag { float4 v[2]; };          // [j]: chunk fragment of this lane (the wave's N tile), 16-deep half j
-
-// ---------------------------------------------------------------------------------------------
-// bf16 operands (STDADK_FLAG_BF16): v_mfma_f32_16x16x32_bf16, fp32 accumulate
-// ---------------------------------------------------------------------------------------------
-// Lane l = 16 q + c16 holds A[row c16][k = 8q + j] and B[k = 8q + j][col c16], j = 0..7 (one 16-byte piece
-// each); D as for the fp32 form.  A 64-deep chunk is TWO MFMAs: lane group q owns the 16 consecutive k
-// 64c + 16q .. +15 of its row (A: the bf16 activation image in LDS; B: row n of the [N][K] bf16 weights), the
-// first MFMA takes its low 8, the second its high 8 -- any assignment of k to (MFMA, q, j) sums the same
-// products as long as A and B agree on it, and this one makes each weight row's four pieces one full 128-byte line.
-typedef unsigned short u16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int ABF_LD = TAIL_MAX_W + 8;        // bf16 activation row stride in LDS (elements; 528 B, 16-byte aligned)
 
 __device__ __forceinline__ f32x4 mfma16h(uint4 a, uint4 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-  const bf2 v = {(__bf16)a, (__bf16)b};       // v_cvt_pk_bf16_f32 (round to nearest even)
-  return __builtin_bit_cast(uint32_t, v);
-}
 __device__ __forceinline__ u16 to_bf16(float a) { return (u16)(pack_bf16(a, 0.f) & 0xffffu); }
-
-struct BFragH { uint4 v[2]; };          // [half]: this lane's 16 k of weight row n in chunk c
 
 #ifdef STDADK_DIAG   // diagnostic build only: in-kernel wall-clock stamps of the phases
 #define STAMP(i) do { if (a.stamps && tid == 0) a.stamps[tile * 16 + (i)] = wall_clock64(); } while (0)
@@ -65,56 +41,105 @@ struct BFragH { uint4 v[2]; };          // [half]: this lane's 16 k of weight ro
 #define WSTAMP(i) do { } while (0)
 #endif
 
+// ---------------------------------------------------------------------------------------------
+// operands of a phase's GEMM: what the shared loops below (preload_w, gemm16_*) need to know about them
+// ---------------------------------------------------------------------------------------------
+// Frag: this lane's weights of one K chunk of the wave's N tile; Elem: element of A (LDS) and W (global);
+// CHUNK = 1 << SHIFT: k per chunk; load: the fragment of chunk c; mma<MT, FULL>: acc[mt] += A[rows 16 mt.., chunk c]
+// . fragment, FULL = the chunk lies entirely below K.  KN = false: W is [N][K] (the forward); KN = true: the product
+// is dA = dZ . W, with nn.Linear's own (out,in) weight as its [K][N] operand.
+//
 // Loads are UNCONDITIONAL from clamped (always valid) addresses and never masked in registers: a
 // conditional load gets its own branch + vmcnt(0), and a select on the loaded value drags the wait
 // in front of the MFMAs of the previous chunk.  The K-half test is scalar, so the MFMA stream has no
 // exec-masked branches.
-// KN = false: W is [N][K] (K contiguous): one dwordx4 per 16-deep half.
-// KN = true:  W is [K][N] row-major (N contiguous): nn.Linear's own (out,in) weight read as the B operand of
-//             dA = dZ . W -- four dword loads (64-byte pieces per 16 lanes) instead of one dwordx4, and no
-//             transposed copy of the weights is needed.  Component e of v[..] is k = 32c + 16j + 4q + e in both
-//             forms, the same k order as the A fragments.
+struct BFrag { float4 v[2]; };          // [j]: chunk fragment of this lane (the wave's N tile), 16-deep half j
+struct BFragH { uint4 v[2]; };          // [half]: this lane's 16 k of weight row n in chunk c
+
+// fp32 operands: v_mfma_f32_16x16x4f32, 32-deep chunks
 template <bool KN>
-__device__ __forceinline__ void load_bfrag(BFrag &f, const float *__restrict__ W, int N, int K, int c, int wave,
-                                           int c16, int q) {
+struct OpF32 {
+  using Frag = BFrag;
+  using Elem = float;
+  static constexpr int SHIFT = 5, CHUNK = 1 << SHIFT;
+  // KN = false: W is [N][K] (K contiguous): one dwordx4 per 16-deep half.
+  // KN = true:  W is [K][N] row-major (N contiguous) -- four dword loads (64-byte pieces per 16 lanes) instead of one
+  //             dwordx4, and no transposed copy of the weights is needed.  Component e of v[..] is
+  //             k = 32c + 16j + 4q + e in both forms, the same k order as the A fragments.
+  static __device__ __forceinline__ void load(BFrag &f, const float *__restrict__ W, int N, int K, int c, int wave,
+                                              int c16, int q) {
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int k = 32 * c + 16 * j + 4 * q;
-    const int kc = k < K ? k : 0;
-    const int n = min(16 * wave, N - 16) + c16;
-    if constexpr (KN) {
-      const float *b = W + (size_t)kc * N + n;
-      f.v[j] = make_float4(b[0], b[N], b[2 * (size_t)N], b[3 * (size_t)N]);
-    } else {
-      f.v[j] = *reinterpret_cast<const float4 *>(W + (size_t)n * K + kc);
+    for (int j = 0; j < 2; ++j) {
+      const int k = 32 * c + 16 * j + 4 * q;
+      const int kc = k < K ? k : 0;
+      const int n = min(16 * wave, N - 16) + c16;
+      if constexpr (KN) {
+        const float *b = W + (size_t)kc * N + n;
+        f.v[j] = make_float4(b[0], b[N], b[2 * (size_t)N], b[3 * (size_t)N]);
+      } else {
+        f.v[j] = *reinterpret_cast<const float4 *>(W + (size_t)n * K + kc);
+      }
     }
   }
-}
-
-template <int MT>
-__device__ __forceinline__ void mma_chunk(f32x4 *acc, const BFrag &f, const float *__restrict__ A, int K, int c,
-                                          int c16, int q) {
+  // A: fp32 activations, row stride ACT_LD (the same for either form of W: KN plays no part here).  Without FULL one
+  // scalar test per 16-deep half (K is a multiple of 16, a half is all in or out); with it straight-line code.
+  template <int MT, bool FULL>
+  static __device__ __forceinline__ void mma(f32x4 *acc, const BFrag &f, const float *__restrict__ A, int K, int c,
+                                             int c16, int q) {
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    if (32 * c + 16 * j < K) {          // scalar: K is a multiple of 16, a 16-deep half is all in or out
-      float af[MT][4];
+    for (int j = 0; j < 2; ++j) {
+      if (FULL || 32 * c + 16 * j < K) {
+        float af[MT][4];
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const float4 av = *reinterpret_cast<const float4 *>(A + (16 * mt + c16) * ACT_LD + 32 * c + 16 * j + 4 * q);
-        af[mt][0] = av.x; af[mt][1] = av.y; af[mt][2] = av.z; af[mt][3] = av.w;
-      }
+        for (int mt = 0; mt < MT; ++mt) {
+          const float4 av = *reinterpret_cast<const float4 *>(A + (16 * mt + c16) * ACT_LD + 32 * c + 16 * j + 4 * q);
+          af[mt][0] = av.x; af[mt][1] = av.y; af[mt][2] = av.z; af[mt][3] = av.w;
+        }
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float4 bv = f.v[j];
-        const float bf[4] = {bv.x, bv.y, bv.z, bv.w};
+        for (int e = 0; e < 4; ++e) {
+          const float4 bv = f.v[j];
+          const float bf[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {    // every weight fragment feeds all row tiles
-          acc[mt] = mfma16(af[mt][e], bf[e], acc[mt]);
+          for (int mt = 0; mt < MT; ++mt) {    // every weight fragment feeds all row tiles
+            acc[mt] = mfma16(af[mt][e], bf[e], acc[mt]);
+          }
         }
       }
     }
   }
-}
+};
+
+// bf16 operands (STDADK_FLAG_BF16): v_mfma_f32_16x16x32_bf16, fp32 accumulate, 64-deep chunks.
+// Lane l = 16 q + c16 holds A[row c16][k = 8q + j] and B[k = 8q + j][col c16], j = 0..7 (one 16-byte piece
+// each); D as for the fp32 form.  A 64-deep chunk is TWO MFMAs: lane group q owns the 16 consecutive k
+// 64c + 16q .. +15 of its row (A: the bf16 activation image in LDS, row stride ABF_LD, columns K .. 64 ceil(K/64)
+// zero; B: row n of the [N][K] bf16 weights -- Wbf, or the transposed copy WTbf for dA = dZ W), the first MFMA takes
+// its low 8, the second its high 8 -- any assignment of k to (MFMA, q, j) sums the same products as long as A and B
+// agree on it, and this one makes each weight row's four pieces one full 128-byte line.
+struct OpBF16 {
+  using Frag = BFragH;
+  using Elem = u16;
+  static constexpr int SHIFT = 6, CHUNK = 1 << SHIFT;
+  // a piece beyond K meets zeros in the A image
+  static __device__ __forceinline__ void load(BFragH &f, const u16 *__restrict__ Wn, int N, int K, int c, int wave,
+                                              int c16, int q) {
+    const int k = 64 * c + 16 * q;
+    const int n = min(16 * wave, N - 16) + c16;
+    const uint4 *src = reinterpret_cast<const uint4 *>(Wn + (size_t)n * K + (k < K ? k : 0));
+    f.v[0] = src[0]; f.v[1] = src[1];
+  }
+  template <int MT, bool FULL>           // FULL makes no difference: the image is zero beyond K
+  static __device__ __forceinline__ void mma(f32x4 *acc, const BFragH &f, const u16 *__restrict__ A, int K, int c,
+                                             int c16, int q) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      const uint4 *ap = reinterpret_cast<const uint4 *>(A + (16 * mt + c16) * ABF_LD + 64 * c + 16 * q);
+      const uint4 a0 = ap[0], a1 = ap[1];
+      acc[mt] = mfma16h(a0, f.v[0], acc[mt]);
+      acc[mt] = mfma16h(a1, f.v[1], acc[mt]);
+    }
+  }
+};
 
 // Every workgroup of a launch multiplies by the SAME weights; walking the K chunks in the same order, the 32 CUs of an
 // XCD ask its L2 for the same 128-byte lines at the same moment.  With STDADK_KROT=1 a workgroup starts its walk at
@@ -123,60 +148,39 @@ __device__ __forceinline__ void mma_chunk(f32x4 *acc, const BFrag &f, const floa
 // r2 item 3): no gain -- off by default (rot = 0 is the natural order), kept as a switch for that measurement.
 __device__ __forceinline__ int chunk_start(int rot, int nchunk) { return rot % nchunk; }
 
-// mma_chunk for a chunk that lies entirely below K (no scalar test per 16-deep half: straight-line code)
-template <int MT>
-__device__ __forceinline__ void mma_chunk_full(f32x4 *acc, const BFrag &f, const float *__restrict__ A, int c, int c16,
-                                               int q) {
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    float af[MT][4];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const float4 av = *reinterpret_cast<const float4 *>(A + (16 * mt + c16) * ACT_LD + 32 * c + 16 * j + 4 * q);
-      af[mt][0] = av.x; af[mt][1] = av.y; af[mt][2] = av.z; af[mt][3] = av.w;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float4 bv = f.v[j];
-      const float bf[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) acc[mt] = mfma16(af[mt][e], bf[e], acc[mt]);
-    }
-  }
-}
-
-// The first 32-deep weight chunk of a GEMM phase, requested one phase EARLY (before the row-local
+// The first weight chunk of a GEMM phase, requested one phase EARLY (before the row-local
 // LayerNorm / input phase that precedes the GEMM) so that its L2 round trip is hidden behind that phase.
 // `rot`: this workgroup's rotation of the K-chunk order (chunk_start above), 0 = natural order.
-template <bool KN = false>
-__device__ __forceinline__ void preload_w(BFrag &f, const float *__restrict__ W, int N, int K, int wave, int c16,
-                                          int q, int rot = 0) {
-  if (wave < (N >> 4)) load_bfrag<KN>(f, W, N, K, chunk_start(rot, (K + 31) >> 5), wave, c16, q);
+template <class Op>
+__device__ __forceinline__ void preload_w(typename Op::Frag &f, const typename Op::Elem *__restrict__ W, int N, int K,
+                                          int wave, int c16, int q, int rot = 0) {
+  if (wave < (N >> 4)) Op::load(f, W, N, K, chunk_start(rot, (K + Op::CHUNK - 1) >> Op::SHIFT), wave, c16, q);
 }
 
-// GEMM of a phase: acc[mt] (rows 16 mt.., N tile `wave`) += A[R x K] (LDS, row stride ACT_LD) * W.
+// GEMM of a phase: acc[mt] (rows 16 mt.., N tile `wave`) += A[R x K] (LDS image of the operand kind) * W.
 // M = 16..64 rows is the GEMV-like regime: every wave streams ITS OWN slice of W straight into VGPRs (no
-// LDS staging, no workgroup barrier in the K loop), two 32-deep chunks in flight; chunk 0 is already in
+// LDS staging, no workgroup barrier in the K loop), two chunks in flight; chunk 0 is already in
 // registers (preload_w).
-template <int MT, bool KN>
-__device__ __forceinline__ void gemm16_loop(f32x4 *acc, const float *__restrict__ A, const float *__restrict__ W,
-                                            int N, int K, int wave, int c16, int q, BFrag &f0, int rot) {
-  const int nchunk = (K + 31) >> 5;
-  BFrag f1;
+template <int MT, class Op>
+__device__ __forceinline__ void gemm16_loop(f32x4 *acc, const typename Op::Elem *__restrict__ A,
+                                            const typename Op::Elem *__restrict__ W, int N, int K, int wave, int c16,
+                                            int q, typename Op::Frag &f0, int rot) {
+  const int nchunk = (K + Op::CHUNK - 1) >> Op::SHIFT;
+  typename Op::Frag f1;
   int c = chunk_start(rot, nchunk);             // f0 holds this chunk (preload_w)
   for (int i = 0; i < nchunk; i += 2) {
     const int c1 = c + 1 == nchunk ? 0 : c + 1;
-    if (i + 1 < nchunk) load_bfrag<KN>(f1, W, N, K, c1, wave, c16, q);
-    mma_chunk<MT>(acc, f0, A, K, c, c16, q);
+    if (i + 1 < nchunk) Op::load(f1, W, N, K, c1, wave, c16, q);
+    Op::template mma<MT, false>(acc, f0, A, K, c, c16, q);
     if (i + 1 < nchunk) {
       const int c2 = c1 + 1 == nchunk ? 0 : c1 + 1;
-      if (i + 2 < nchunk) load_bfrag<KN>(f0, W, N, K, c2, wave, c16, q);
-      mma_chunk<MT>(acc, f1, A, K, c1, c16, q);
+      if (i + 2 < nchunk) Op::load(f0, W, N, K, c2, wave, c16, q);
+      Op::template mma<MT, false>(acc, f1, A, K, c1, c16, q);
       c = c2;
     }
   }
 }
-// K = 32 NCH exactly (the widths 256 and 128 of every shipped configuration), natural chunk order: the chunk loop
+// K = CHUNK * NCH exactly (the widths 256 and 128 of every shipped configuration), natural chunk order: the chunk loop
 // fully unrolled over a ring of three fragment buffers, chunks c + 1 and c + 2 in flight while chunk c is multiplied.
 // Straight-line code matters here: in the rolled loop above the loads of the next chunk sit behind a scalar branch
 // (the last chunk has no successor), and where the two paths meet the compiler can only wait for the larger of their
@@ -184,102 +188,33 @@ __device__ __forceinline__ void gemm16_loop(f32x4 *acc, const float *__restrict_
 // every chunk's MFMAs waited for the NEXT chunk's fragments: no weight chunk was ever in flight under the MFMAs, and
 // the phase ran at ~60-70 % of the matrix pipe with four waves per SIMD covering for each other (round-3 per-wave
 // stamps, tools/diag/wave_stamps.py).  Unrolled, every wait is an exact count.
-template <int MT, bool KN, int NCH>
-__device__ __forceinline__ void gemm16_unrolled(f32x4 *acc, const float *__restrict__ A, const float *__restrict__ W,
-                                                int N, int K, int wave, int c16, int q, const BFrag &f0) {
+template <int MT, class Op, int NCH>
+__device__ __forceinline__ void gemm16_unrolled(f32x4 *acc, const typename Op::Elem *__restrict__ A,
+                                                const typename Op::Elem *__restrict__ W, int N, int K, int wave,
+                                                int c16, int q, const typename Op::Frag &f0) {
   // (also measured: the A fragments of the next 16-deep step read from LDS ahead of the current step's MFMAs, two
   //  register sets -- 56.8 vs 57.3 us for the 16-row fused kernel, 403 vs 388 us at 64 rows; and that order pinned
   //  with sched_group_barrier -- 59.8 / 407 us: the compiler's own placement of the LDS reads stays)
-  BFrag f[3];
+  typename Op::Frag f[3];
   f[0] = f0;
-  if (NCH > 1) load_bfrag<KN>(f[1], W, N, K, 1, wave, c16, q);
-  if (NCH > 2) load_bfrag<KN>(f[2], W, N, K, 2, wave, c16, q);
+  if (NCH > 1) Op::load(f[1], W, N, K, 1, wave, c16, q);
+  if (NCH > 2) Op::load(f[2], W, N, K, 2, wave, c16, q);
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
-    mma_chunk_full<MT>(acc, f[c % 3], A, c, c16, q);
-    if (c + 3 < NCH) load_bfrag<KN>(f[c % 3], W, N, K, c + 3, wave, c16, q);
+    Op::template mma<MT, true>(acc, f[c % 3], A, K, c, c16, q);
+    if (c + 3 < NCH) Op::load(f[c % 3], W, N, K, c + 3, wave, c16, q);
   }
 }
 
-template <int MT, bool KN = false>
-__device__ __forceinline__ void gemm16_pre(f32x4 *acc, const float *__restrict__ A, const float *__restrict__ W, int N,
-                                           int K, int wave, int c16, int q, BFrag &f0, int rot = 0) {
+template <int MT, class Op>
+__device__ __forceinline__ void gemm16_pre(f32x4 *acc, const typename Op::Elem *__restrict__ A,
+                                           const typename Op::Elem *__restrict__ W, int N, int K, int wave, int c16,
+                                           int q, typename Op::Frag &f0, int rot = 0) {
   if (wave >= (N >> 4)) return;                 // scalar: this wave has no N tile in a narrow layer
 
-  if (rot == 0 && K == 256) gemm16_unrolled<MT, KN, 8>(acc, A, W, N, K, wave, c16, q, f0);
-  else if (rot == 0 && K == 128) gemm16_unrolled<MT, KN, 4>(acc, A, W, N, K, wave, c16, q, f0);
-  else gemm16_loop<MT, KN>(acc, A, W, N, K, wave, c16, q, f0, rot);
-}
-
-// ---- bf16 operands
-// unconditional loads from clamped addresses like load_bfrag; a piece beyond K meets zeros in the A image
-__device__ __forceinline__ void load_bfrag_h(BFragH &f, const u16 *__restrict__ Wn, int N, int K, int c, int wave,
-                                             int c16, int q) {
-  const int k = 64 * c + 16 * q;
-  const int n = min(16 * wave, N - 16) + c16;
-  const uint4 *src = reinterpret_cast<const uint4 *>(Wn + (size_t)n * K + (k < K ? k : 0));
-  f.v[0] = src[0]; f.v[1] = src[1];
-}
-
-template <int MT>
-__device__ __forceinline__ void mma_chunk_h(f32x4 *acc, const BFragH &f, const u16 *__restrict__ A, int c, int c16,
-                                            int q) {
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const uint4 *ap = reinterpret_cast<const uint4 *>(A + (16 * mt + c16) * ABF_LD + 64 * c + 16 * q);
-    const uint4 a0 = ap[0], a1 = ap[1];
-    acc[mt] = mfma16h(a0, f.v[0], acc[mt]);
-    acc[mt] = mfma16h(a1, f.v[1], acc[mt]);
-  }
-}
-
-__device__ __forceinline__ void preload_wh(BFragH &f, const u16 *__restrict__ Wn, int N, int K, int wave, int c16,
-                                           int q, int rot = 0) {
-  if (wave < (N >> 4)) load_bfrag_h(f, Wn, N, K, chunk_start(rot, (K + 63) >> 6), wave, c16, q);
-}
-
-// acc[mt] += A[R x K] (bf16 image in LDS, columns K .. 64 ceil(K/64) zero) * W^T, W = [N][K] bf16 in global
-// memory, chunk 0 already in registers (preload_wh), two chunks in flight
-template <int MT>
-__device__ __forceinline__ void gemm16_loop_h(f32x4 *acc, const u16 *__restrict__ A, const u16 *__restrict__ Wn, int N,
-                                              int K, int wave, int c16, int q, BFragH &f0, int rot) {
-  const int nchunk = (K + 63) >> 6;
-  BFragH f1;
-  int c = chunk_start(rot, nchunk);
-  for (int i = 0; i < nchunk; i += 2) {
-    const int c1 = c + 1 == nchunk ? 0 : c + 1;
-    if (i + 1 < nchunk) load_bfrag_h(f1, Wn, N, K, c1, wave, c16, q);
-    mma_chunk_h<MT>(acc, f0, A, c, c16, q);
-    if (i + 1 < nchunk) {
-      const int c2 = c1 + 1 == nchunk ? 0 : c1 + 1;
-      if (i + 2 < nchunk) load_bfrag_h(f0, Wn, N, K, c2, wave, c16, q);
-      mma_chunk_h<MT>(acc, f1, A, c1, c16, q);
-      c = c2;
-    }
-  }
-}
-// the unrolled ring of gemm16_unrolled for the bf16 operands: K = 64 NCH exactly (256 -> 4 chunks, 128 -> 2)
-template <int MT, int NCH>
-__device__ __forceinline__ void gemm16_unrolled_h(f32x4 *acc, const u16 *__restrict__ A, const u16 *__restrict__ Wn,
-                                                  int N, int K, int wave, int c16, int q, const BFragH &f0) {
-  BFragH f[3];
-  f[0] = f0;
-  if (NCH > 1) load_bfrag_h(f[1], Wn, N, K, 1, wave, c16, q);
-  if (NCH > 2) load_bfrag_h(f[2], Wn, N, K, 2, wave, c16, q);
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    mma_chunk_h<MT>(acc, f[c % 3], A, c, c16, q);
-    if (c + 3 < NCH) load_bfrag_h(f[c % 3], Wn, N, K, c + 3, wave, c16, q);
-  }
-}
-
-template <int MT>
-__device__ __forceinline__ void gemm16_pre_h(f32x4 *acc, const u16 *__restrict__ A, const u16 *__restrict__ Wn, int N,
-                                             int K, int wave, int c16, int q, BFragH &f0, int rot = 0) {
-  if (wave >= (N >> 4)) return;
-  if (rot == 0 && K == 256) gemm16_unrolled_h<MT, 4>(acc, A, Wn, N, K, wave, c16, q, f0);
-  else if (rot == 0 && K == 128) gemm16_unrolled_h<MT, 2>(acc, A, Wn, N, K, wave, c16, q, f0);
-  else gemm16_loop_h<MT>(acc, A, Wn, N, K, wave, c16, q, f0, rot);
+  if (rot == 0 && K == 256) gemm16_unrolled<MT, Op, (256 >> Op::SHIFT)>(acc, A, W, N, K, wave, c16, q, f0);
+  else if (rot == 0 && K == 128) gemm16_unrolled<MT, Op, (128 >> Op::SHIFT)>(acc, A, W, N, K, wave, c16, q, f0);
+  else gemm16_loop<MT, Op>(acc, A, W, N, K, wave, c16, q, f0, rot);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -331,21 +266,23 @@ __device__ __forceinline__ void d0_load_bfrag(BFrag &f, const float *__restrict_
   }
 }
 
-// acc += features (LDS, two 256-column halves) . W0^T, 32-deep chunks, two in flight like gemm16_pre
+// acc += features (LDS, two 256-column halves) . W0^T, 32-deep chunks, two in flight like gemm16_loop.  Written out:
+// as a third operand description of gemm16_loop (rot = 0) the compiler keeps the loop's wrap-around selects, and every
+// dense-0 kernel compiles to other code (profiles/tail_gemm_refactor.md).  W0^T is a [K][N] operand: OpF32<true>.
 template <int MT>
 __device__ __forceinline__ void d0_gemm(f32x4 *acc, const float *act0, const float *act1, const float *__restrict__ W0T,
                                         int N, int D, int wave, int c16, int q, BFrag &f0) {
   if (wave >= (N >> 4)) return;
-  const int Kp = (D + 15) & ~15;                 // mma_chunk works in 16-deep halves
+  const int Kp = (D + 15) & ~15;                 // mma works in 16-deep halves
   const int nchunk = (D + 31) >> 5;
   constexpr int HC = TAIL_MAX_W / 32;            // chunks per LDS half
   BFrag f1;
   for (int c = 0; c < nchunk; c += 2) {
     if (c + 1 < nchunk) d0_load_bfrag(f1, W0T, N, D, c + 1, wave, c16, q);
-    mma_chunk<MT>(acc, f0, c < HC ? act0 : act1 - TAIL_MAX_W, Kp, c, c16, q);
+    OpF32<true>::mma<MT, false>(acc, f0, c < HC ? act0 : act1 - TAIL_MAX_W, Kp, c, c16, q);
     if (c + 1 < nchunk) {
       if (c + 2 < nchunk) d0_load_bfrag(f0, W0T, N, D, c + 2, wave, c16, q);
-      mma_chunk<MT>(acc, f1, c + 1 < HC ? act0 : act1 - TAIL_MAX_W, Kp, c + 1, c16, q);
+      OpF32<true>::mma<MT, false>(acc, f1, c + 1 < HC ? act0 : act1 - TAIL_MAX_W, Kp, c + 1, c16, q);
     }
   }
 }
@@ -358,6 +295,14 @@ __device__ __forceinline__ void d0_gemm(f32x4 *acc, const float *act0, const flo
 // compiler turns `if (column < h) store` into a save-exec / branch / restore block per store: twelve per row in the
 // forward phase).  A 128-wide layer walks two groups instead of four masked ones.  The generic instantiation
 // (CC = 4, masks) keeps every other width working.  Same arithmetic, in the same order, in all of them.
+
+// okc[cc]: column lane + 64 cc lies inside the width h
+template <int CC, bool FULL>
+__device__ __forceinline__ void col_mask(bool (&okc)[CC], int lane, int h) {
+#pragma unroll
+  for (int cc = 0; cc < CC; ++cc) okc[cc] = FULL || lane + 64 * cc < h;
+}
+
 struct LnFwdCtx {
   float *xhat, *act, *rstd;      // NULL in eval mode
   int layer_id, h, B;
@@ -373,8 +318,7 @@ __device__ __forceinline__ void ln_fwd_rows(const LnFwdCtx &c, float *nxt, u16 *
                                             const float (&gv)[4], const float (&bev)[4]) {
   const int h = c.h;
   bool okc[CC];
-#pragma unroll
-  for (int cc = 0; cc < CC; ++cc) okc[cc] = FULL || lane + 64 * cc < h;
+  col_mask<CC, FULL>(okc, lane, h);
   const float inv_h = 1.0f / (float)h;
   float z[RPW][CC], mean[RPW], rs[RPW];
 #pragma unroll
@@ -465,8 +409,7 @@ __device__ __forceinline__ void ln_bwd_rows(const LnBwdCtx &c, float *cur, u16 *
                                             const float (&rsv)[RPW], float (&pg)[4], float (&pb)[4], float (&pz)[4]) {
   const int h = c.h;
   bool okc[CC];
-#pragma unroll
-  for (int cc = 0; cc < CC; ++cc) okc[cc] = FULL || lane + 64 * cc < h;
+  col_mask<CC, FULL>(okc, lane, h);
   const float inv_h = 1.0f / (float)h;
   float dxh[RPW][CC], m1[RPW], m2[RPW];
 #pragma unroll
@@ -558,6 +501,10 @@ __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float *smem,
   // workgroups b, b + 8, ... share an XCD: consecutive ones of them start their K walks one chunk apart
   const int rot = a.krot ? (int)(blockIdx.x >> 3) : 0;
   STAMP(0);
+  // z = a W^T, W = [N][K]: OpF32<false> on `cur` and W, or OpBF16 on the image and Wbf.  The kind is chosen at each
+  // preload and GEMM call, with its own fragment variable, image and weight pointer: chosen behind the operand
+  // description, the 64-row bf16 kernels compile to other code (profiles/tail_gemm_refactor.md).  The dense layer 0
+  // multiplies fp32 features whatever BF says: `wpre`.
   BFrag wpre;
   BFragH wpre_h;
   if constexpr (D0) {
@@ -567,8 +514,8 @@ __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float *smem,
     }
   } else {
     if (a.n_layers > 0) {
-      if constexpr (BF) preload_wh(wpre_h, a.L[0].Wbf, a.L[0].h, a.L[0].hp, wave, c16, q, rot);
-      else preload_w(wpre, a.L[0].W, a.L[0].h, a.L[0].hp, wave, c16, q, rot);
+      if constexpr (BF) preload_w<OpBF16>(wpre_h, a.L[0].Wbf, a.L[0].h, a.L[0].hp, wave, c16, q, rot);
+      else preload_w<OpF32<false>>(wpre, a.L[0].W, a.L[0].h, a.L[0].hp, wave, c16, q, rot);
     }
   }
   if constexpr (!D0) {
@@ -656,13 +603,13 @@ __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float *smem,
       }
     } else {
       if (li == 0) WSTAMP(0);
-      if constexpr (BF) gemm16_pre_h<MT>(acc, abf, L.Wbf, h, hp, wave, c16, q, wpre_h, rot);
-      else gemm16_pre<MT>(acc, cur, L.W, h, hp, wave, c16, q, wpre, rot);
+      if constexpr (BF) gemm16_pre<MT, OpBF16>(acc, abf, L.Wbf, h, hp, wave, c16, q, wpre_h, rot);
+      else gemm16_pre<MT, OpF32<false>>(acc, cur, L.W, h, hp, wave, c16, q, wpre, rot);
       if (li == 0) WSTAMP(1);
     }
     if (li + 1 < a.n_layers) {
-      if constexpr (BF) preload_wh(wpre_h, a.L[li + 1].Wbf, a.L[li + 1].h, a.L[li + 1].hp, wave, c16, q, rot);
-      else preload_w(wpre, a.L[li + 1].W, a.L[li + 1].h, a.L[li + 1].hp, wave, c16, q, rot);
+      if constexpr (BF) preload_w<OpBF16>(wpre_h, a.L[li + 1].Wbf, a.L[li + 1].h, a.L[li + 1].hp, wave, c16, q, rot);
+      else preload_w<OpF32<false>>(wpre, a.L[li + 1].W, a.L[li + 1].h, a.L[li + 1].hp, wave, c16, q, rot);
     }
     STAMP(2 + 4 * (li < 0 ? 0 : li));
     // z = acc + bias into the other activation buffer
@@ -927,9 +874,11 @@ __device__ __forceinline__ void tail_bwd_body(const TailBwdArgs &a, float *smem,
     const int h = L.h;
     BFrag wpre;
     BFragH wpre_h;
-    if (li > 0) {                                                      // for the dA GEMM at the end of this pass
-      if constexpr (BF) preload_wh(wpre_h, L.WTbf, L.hp, h, wave, c16, q, rot);
-      else preload_w<true>(wpre, L.W, L.hp, h, wave, c16, q, rot);
+    // dA = dZ W, W = [K][N]: OpF32<true> on `cur` and W, or OpBF16 on the image and the transposed copy WTbf (the
+    // kind chosen at each call, as in the forward body)
+    if (li > 0) {                  // for the dA GEMM at the end of this pass
+      if constexpr (BF) preload_w<OpBF16>(wpre_h, L.WTbf, L.hp, h, wave, c16, q, rot);
+      else preload_w<OpF32<true>>(wpre, L.W, L.hp, h, wave, c16, q, rot);
     }
     // ---- (a) Dropout -> ReLU -> LayerNorm backward of the wave's rows, specialised on the layer's width
     // (ln_bwd_rows below).  Its global inputs (xhat rows, gamma, beta, rstd) were requested one phase early (ln_inputs).
@@ -971,8 +920,8 @@ __device__ __forceinline__ void tail_bwd_body(const TailBwdArgs &a, float *smem,
     for (int mt = 0; mt < MT; ++mt) acc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     ln_inputs(a.L[li - 1]);        // consumed after the GEMM, in the next pass
     lds_barrier();                 // every wave's dZ rows are in `cur`
-    if constexpr (BF) gemm16_pre_h<MT>(acc, abf, L.WTbf, hp, h, wave, c16, q, wpre_h, rot);
-    else gemm16_pre<MT, true>(acc, cur, L.W, hp, h, wave, c16, q, wpre, rot);
+    if constexpr (BF) gemm16_pre<MT, OpBF16>(acc, abf, L.WTbf, hp, h, wave, c16, q, wpre_h, rot);
+    else gemm16_pre<MT, OpF32<true>>(acc, cur, L.W, hp, h, wave, c16, q, wpre, rot);
     STAMP(3 + 3 * (a.n_layers - 1 - li));      // dA GEMM of this pass
     if (wave < NT) {
 #pragma unroll

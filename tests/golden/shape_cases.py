@@ -22,6 +22,12 @@ chunks, the bf16 one 64-deep chunks):
   d_gauss_q2         the same with the Gaussian basis, K = 112 / 144, Q = 2
   g_*                widths the tail refuses (not a multiple of 16, wider than 256): the per-layer LayerNorm /
                      ReLU / GEMM / head kernels of mlp.hip
+
+Rows per workgroup: tail_rows() (csrc/tail.hip) gives 64-row tiles once ceil(B / 64) >= 256, else 32-row tiles once
+ceil(B / 32) >= 256, else 16.  At 300 and 4 097 rows that is 16: only the MT = 1 instantiations meet the rolled K
+loop with its ragged last chunk.  ROWS32_B = 255 * 32 + 1 = 8 161 is the smallest batch with 32-row tiles (MT = 2:
+255 full tiles and one of a single row), ROWS64_B = 255 * 64 + 1 = 16 321 the smallest with 64-row tiles (MT = 4,
+likewise); BIG_CASES run at both.
 """
 import numpy as np
 
@@ -69,6 +75,8 @@ FEATURE_WIDTH = {"d_D256": 256, "d_D257_depth1": 257, "d_D512": 512, "d_D513": 5
 # last tile of one row
 BIG_B = 4097
 BIG_CASES = ["w_k80_k176_noln", "w_depth8_q8"]
+ROWS32_B = 255 * 32 + 1      # smallest batch with 32-row tail tiles
+ROWS64_B = 255 * 64 + 1      # smallest batch with 64-row tail tiles
 
 
 def config(name, B=None):

@@ -92,7 +92,8 @@ def test_module_forward_backward_against_float64(name, path):
 
 # ------------------------------------------------------------------ b. one TrainStep.step
 B_PARAMS = [(n, 300) for n in SC.WINDOW_CASES] + [(n, SC.BIG_B) for n in SC.BIG_CASES] \
-    + [("d_D256", 300), ("d_D512", 300), ("g_h320_72_q3", 300)]
+    + [("d_D256", 300), ("d_D512", 300), ("g_h320_72_q3", 300)] \
+    + [(n, B) for B in (SC.ROWS32_B, SC.ROWS64_B) for n in SC.BIG_CASES]
 
 
 @pytest.mark.parametrize("name,B", B_PARAMS)
@@ -101,7 +102,8 @@ def test_train_step_against_float64(name, B):
     the reference norm) against the float64 optimiser on the kink-adjusted gradients.  Window cases at 300 rows run the
     one-launch step kernel (fused_step.hip); at 4 097 rows, the first size past it, the separate window and tail
     kernels with a ragged last tile of one row (no bound on the number of near-kink units there: fourteen times the
-    rows)."""
+    rows); at 8 161 and 16 321 rows the same kernels with 32- and 64-row tiles (shape_cases.ROWS32_B / ROWS64_B), whose
+    rolled K loop with a ragged last chunk no other test reaches."""
     from stnf.engine import TrainStep
     cfg, inp, yo, lo, go, alts = _reference(name, B)
     ref_norm = float(np.sqrt(sum(float((g * g).sum()) for g in go.values())))
@@ -245,12 +247,17 @@ def test_predict_grid_against_float64(name):
 
 
 # ------------------------------------------------------------------ e. bf16 operands
-@pytest.mark.parametrize("name", ["w_k48_q2", "w_k80_k176_noln", "w_narrow_wide_q4", "d_D256"])
-def test_bf16_operands_against_emulation(name):
+E_PARAMS = [pytest.param(n, None, id=n) for n in ["w_k48_q2", "w_k80_k176_noln", "w_narrow_wide_q4", "d_D256"]] \
+    + [pytest.param("w_k80_k176_noln", B, id=f"w_k80_k176_noln-{B}") for B in (SC.ROWS32_B, SC.ROWS64_B)]
+
+
+@pytest.mark.parametrize("name,B", E_PARAMS)
+def test_bf16_operands_against_emulation(name, B):
     """K % 64 in {16, 32, 48} under bf16 operands (64-deep chunks: a piece beyond K meets zeros in the A image) against
     the float64 emulation of exactly that arithmetic (test_gpu_bf16.emulate), with that module's bounds: rounding flips
-    stay below them, a wrong k mapping or a missing product shows at O(1)."""
-    cfg, inp = _reference(name)[:2]
+    stay below them, a wrong k mapping or a missing product shows at O(1).  The two large batches run the 32- and
+    64-row tiles."""
+    cfg, inp = _reference(name, B)[:2]
     m = T.build_model(cfg)
     m.compute_dtype = "bf16"
     m.train()
@@ -263,7 +270,7 @@ def test_bf16_operands_against_emulation(name):
     emu_l = abs(loss.item() - le) / le
     emu_g = {k: T.rel_l2(p.grad.cpu().numpy(), ge[k]) for k, p in m.named_parameters()}
     worst = max(emu_g, key=emu_g.get)
-    print(f"{name} bf16 vs emulation: y {emu_y:.2e}, loss {emu_l:.2e}, gradients worst rel-L2 {emu_g[worst]:.2e} ({worst})")
+    print(f"{name} B={cfg['B']} bf16 vs emulation: y {emu_y:.2e}, loss {emu_l:.2e}, gradients worst rel-L2 {emu_g[worst]:.2e} ({worst})")
     assert emu_y <= BF.EMU_Y and emu_l <= BF.EMU_LOSS
     for k, e in emu_g.items():
         assert e <= BF.EMU_GRAD, (k, e)
