@@ -96,6 +96,28 @@ typedef struct stdadk_mlp_tensors {
  * split-K slabs).  The same workspace must be passed to backward untouched. */
 size_t stdadk_mlp_workspace_bytes(const stdadk_mlp_desc *desc, int64_t B);
 
+/* Dropout keep-masks: "the counter-based generator keyed by drop_seed", everywhere below.  Stateless:
+ * the keep decision of element (row, col) of hidden layer `layer` (0-based) is a pure function of
+ * (drop_seed, step, layer, row, col), so a backward regenerates the mask of its forward.
+ *   step seed  s = drop_seed + step_dev[0] * 0x9E3779B97F4A7C15  mod 2^64   (step_dev NULL: s = drop_seed)
+ *   row key    k = mix32(s ^ (0x9E3779B97F4A7C15 * (layer + 1) mod 2^64) ^ (row * 0xD1B54A32D192ED03 mod 2^64))
+ *              mix32(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53;
+ *                        x ^= x >> 33 (64-bit, wrapping); the low 32 bits
+ *   hash       h = fin32(k ^ (pair * 0x9E3779B1 mod 2^32)),  pair = (col & 63) | ((col >> 7) << 6): the columns
+ *              c and c + 64 of a 128-column block share one hash
+ *              fin32(h): h ^= h >> 16; h *= 0x21f0aaad; h ^= h >> 15; h *= 0x735a2d97; h ^= h >> 15 (32-bit)
+ *   bits       v = bit 6 of col set ? h >> 16 : h & 0xffff
+ *   keep       v >= ceilf(p * 65536) with p = dropout_p as float32; kept values are scaled by 1 / (1 - p)
+ * `row` is the caller's row wherever the features are materialised (stdadk_mlp_*_f32, and the step entry
+ * points on the materialising path).  On the window path it is the row's SORTED position: the batch is
+ * sorted by binning-cell key (stable: ascending caller row inside a cell) on the grid of
+ * pick_cell_grid(B) cells a side, the smallest power of two in [8, 256] whose square is >= B.
+ * step_dev[0]: forward and backward of one step read the value the counter has BEFORE that step's own
+ * advance, which rides behind the backward (with the clip-norm partial sums, or stdadk_step_advance);
+ * the optimiser launch reads the advanced value.  The n-th step since the counter was zeroed (n from 0)
+ * therefore draws the masks of step n, in eager launches and in a replayed graph alike.
+ * oracle/dropout.py restates this on the CPU for the tests. */
+
 /* y_pred[B,Q] = mlp(features[B, ldf]).  `training` != 0 applies dropout (keep-mask from the
  * counter-based generator keyed by drop_seed, or from drop_mask[l] (uint8 [B,h_l], 1 = keep) when
  * that host array of device pointers is non-NULL) and saves what backward needs in `workspace`. */

@@ -41,9 +41,10 @@ def _features(X, coords, t, cfg, knots, device):
     return torch.cat([phi, psi], dim=1)
 
 
-def _forward(a, layers, head, layernorm):
+def _forward(a, layers, head, layernorm, masks=None):
+    """`masks`: per hidden layer the keep-mask of these rows already scaled by 1 / (1 - p), or None."""
     cache = []
-    for W, b, g, be in layers:
+    for li, (W, b, g, be) in enumerate(layers):
         z = a @ W.T + b
         if layernorm:
             mu = z.mean(-1, keepdim=True)
@@ -55,16 +56,21 @@ def _forward(a, layers, head, layernorm):
             xhat, rstd, u = None, None, z
         cache.append((a, xhat, rstd, u))
         a = torch.clamp(u, min=0.0)
+        if masks is not None:
+            a = a * masks[li]
     Wo, bo = head
     return a @ Wo.T + bo, cache, a
 
 
-def train_step_grads(X, coords, t, y, params, cfg, device="cpu", chunk=4096, kink_tol=None):
+def train_step_grads(X, coords, t, y, params, cfg, device="cpu", chunk=4096, kink_tol=None, drop_masks=None,
+                     drop_p=0.0):
     """(y_pred, loss, grads[, alts]) as `stdadk_oracle.train_step_grads`, as numpy float64.  `alts` (with kink_tol):
     the units within kink_tol of a ReLU kink in THIS forward, each with the change of every gradient when its ReLU
     derivative is taken from the other side -- taken from the numpy oracle on that single row (row-local), so
-    `stdadk_oracle.fit_kink_sides` applies unchanged."""
+    `stdadk_oracle.fit_kink_sides` applies unchanged.  `drop_masks` / `drop_p` as `stdadk_oracle.mlp_forward`: keep-masks
+    (B, h_l) per hidden layer, sliced per row chunk."""
     device = torch.device(device)
+    dropping = drop_masks is not None and drop_p > 0
     B = np.asarray(coords).shape[0]
     nh, ln = len(cfg["hidden_dims"]), cfg["layernorm"]
     layers_np, head_np, keys = orc.split_params(params, nh, ln)
@@ -82,7 +88,8 @@ def train_step_grads(X, coords, t, y, params, cfg, device="cpu", chunk=4096, kin
         r1 = min(B, r0 + chunk)
         Xc = None if X is None else np.asarray(X)[r0:r1]
         a0 = _features(Xc, np.asarray(coords)[r0:r1], np.asarray(t)[r0:r1], cfg, knots, device)
-        yp, cache, a_last = _forward(a0, layers, head, ln)
+        mk = [_t(m[r0:r1], device) / (1.0 - drop_p) for m in drop_masks] if dropping else None
+        yp, cache, a_last = _forward(a0, layers, head, ln, mk)
         d = yp - _t(np.asarray(y)[r0:r1], device).reshape(yp.shape)
         loss += (d * d).sum()
         ys.append(yp.cpu())
@@ -95,6 +102,8 @@ def train_step_grads(X, coords, t, y, params, cfg, device="cpu", chunk=4096, kin
         for li in range(nh - 1, -1, -1):
             W, b, g, be = layers[li]
             a_in, xhat, rstd, u = cache[li]
+            if mk is not None:
+                da = da * mk[li]
             if kink_tol is not None:
                 rr, cc = torch.nonzero(u.abs() < kink_tol, as_tuple=True)
                 near += [(li, r0 + int(i), int(j)) for i, j in zip(rr.tolist(), cc.tolist())]
@@ -119,7 +128,9 @@ def train_step_grads(X, coords, t, y, params, cfg, device="cpu", chunk=4096, kin
     alts = []
     for (li, r, c) in sorted(near):
         Xr = None if X is None else np.asarray(X)[r:r + 1]
-        yr, cache_r, _, _, _ = orc.model_forward(Xr, np.asarray(coords)[r:r + 1], np.asarray(t)[r:r + 1], params, cfg)
+        mr = [np.asarray(m)[r:r + 1] for m in drop_masks] if dropping else None
+        yr, cache_r, _, _, _ = orc.model_forward(Xr, np.asarray(coords)[r:r + 1], np.asarray(t)[r:r + 1], params, cfg,
+                                                 drop_masks=mr, drop_p=drop_p)
         yt = np.asarray(y)[r:r + 1]
         g0 = orc.mlp_mse_backward(yr, yt, cache_r, params, nh, ln, grad_scale=scale)
         g1 = orc.mlp_mse_backward(yr, yt, cache_r, params, nh, ln, grad_scale=scale, flip=((li, 0, c),))
