@@ -361,6 +361,8 @@ int stdadk_backward_f32(const stdadk_basis_desc *basis, const stdadk_mlp_desc *m
  *   G = dZ0 . W0[:, p:p+Ks]                                  (what autograd sends into phi)
  *   r = |x - c_k| / (exp(log_bw_k) cal);   d_c_k = sum_b G phi'(r) (-(x-c_k)/(|x-c_k| s_k)) (0 at zero
  *   distance, as cdist's backward has it);   d_log_bw_k = sum_b G phi'(r) (-r)
+ * The triangular basis at exactly r == 1: the materialising route counts the pair with slope -1, as autograd
+ * differentiates clamp(1 - r, min = 0); the window route skips it, because phi == 0 never enters a knot's list.
  * then, when `kt` is given, what the training driver adds on top (all per knot, fixed order):
  *   + penalty_grad_scale * d/dc [ domain_weight  * sum (max(0,-c) + max(0,c-1))^2      (:493-526)
  *                               + movement_weight * sum |c - centers_init|^2 ]         (:528-546)
