@@ -5,7 +5,7 @@ Same arithmetic definition as the numpy oracle -- direct-difference distances (n
 Wendland / Gaussian / triangular basis, Linear -> LayerNorm (biased variance) -> ReLU, MSE over B*Q -- evaluated in
 float64 on any torch device, in row chunks: every row's forward and backward is row-local once the MSE scale
 1/(B*Q) is passed in, so the gradients are float64 sums of per-chunk contributions.  Pinned against the numpy
-oracle in tests/test_torch_f64_oracle.py.
+oracle in tests/test_torch_f64_oracle.py.  `forward` is the forward half alone (the validation passes).
 """
 import numpy as np
 import torch
@@ -60,6 +60,27 @@ def _forward(a, layers, head, layernorm, masks=None):
             a = a * masks[li]
     Wo, bo = head
     return a @ Wo.T + bo, cache, a
+
+
+def forward(X, coords, t, params, cfg, device="cpu", chunk=4096):
+    """y_pred (B, Q) as `stdadk_oracle.model_forward(...)[0]` in eval mode, as numpy float64: the forward half of
+    train_step_grads alone, for the validation passes (nothing is kept for a backward, any output width)."""
+    device = torch.device(device)
+    B = np.asarray(coords).shape[0]
+    nh, ln = len(cfg["hidden_dims"]), cfg["layernorm"]
+    layers_np, head_np, _ = orc.split_params(params, nh, ln)
+    layers = [tuple(None if a is None else _t(a, device) for a in lay) for lay in layers_np]
+    head = tuple(_t(a, device) for a in head_np)
+    centers, bw, _ = orc.uniform_knots(cfg["k_spatial_centers"])
+    tc, tb = orc.temporal_knots(cfg["k_temporal_centers"])
+    knots = tuple(_t(a, device) for a in (centers, bw, tc, tb))
+    ys = []
+    for r0 in range(0, B, chunk):
+        r1 = min(B, r0 + chunk)
+        Xc = None if X is None else np.asarray(X)[r0:r1]
+        a0 = _features(Xc, np.asarray(coords)[r0:r1], np.asarray(t)[r0:r1], cfg, knots, device)
+        ys.append(_forward(a0, layers, head, ln)[0].cpu())
+    return torch.cat(ys).numpy() if ys else np.zeros((0, head_np[0].shape[0]))
 
 
 def train_step_grads(X, coords, t, y, params, cfg, device="cpu", chunk=4096, kink_tol=None, drop_masks=None,

@@ -21,7 +21,8 @@ class Evaluator:
     `mse, mae, rmse` (of the median level `Q // 2` for several outputs), `check_loss` (quantile), `mean_check_loss`,
     `check_loss`, `crps` (multi-quantile), plus `loss`: the mean over batches of the batch objective, the
     reference's `val_loss` (with the delta head and `non_crossing_lambda > 0` the parameter-level P_nc(delta) is part
-    of every batch's objective, as scripts/train_st_interp.py:770-777 has it)."""
+    of every batch's objective, as scripts/train_st_interp.py:770-777 has it).  `batch_size` is one size (last batch
+    ragged) or a list of sizes summing to len(dataset), the data-parallel schedule of `DeviceDataset.epoch_batches`."""
 
     def __init__(self, model, loss="mse", quantile_levels=None, non_crossing_weight=0.0, non_crossing_power=1,
                  non_crossing_lambda=0.0, max_batch=65536, force_dense=False, process_group=None):
@@ -122,7 +123,9 @@ class Evaluator:
                 engine.swap_in_ema()
                 swapped = True
         try:
-            return self._evaluate(dataset, int(batch_size), engine, ema_views=(params == "ema" and not swapped))
+            # (a list of sizes summing to len(dataset): the data-parallel schedule, DeviceDataset.epoch_batches)
+            sizes = [int(b) for b in batch_size] if isinstance(batch_size, (list, tuple)) else int(batch_size)
+            return self._evaluate(dataset, sizes, engine, ema_views=(params == "ema" and not swapped))
         finally:
             if swapped:
                 engine.swap_in_ema()

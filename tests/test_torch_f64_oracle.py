@@ -33,6 +33,20 @@ def test_chunked_float64_step_equals_numpy_oracle(name, chunk):
     assert np.array_equal(np.abs(gt["mlp.0.weight"]).sum(0) == 0, z)
 
 
+@pytest.mark.parametrize("name,chunk", [("tiny9", 3), ("tiny9_ln_p3", 4), ("default227", 64), ("default227_tri", 16),
+                                        ("c2_b257", 100), ("tiny9_mq5_nc2", 2), ("c2_b257_mq3", 4096)])
+def test_chunked_float64_forward_equals_numpy_oracle(name, chunk):
+    """The forward-only entry point (the reference of the production validation calls), quantile heads included."""
+    cfg = cases.MODEL_CASES[name] if name in cases.MODEL_CASES else cases.quantile_cfg(name)[0]
+    X, coords, t, _ = cases.make_inputs(cfg)
+    params = {k: v.astype(np.float64) for k, v in cases.make_state(cfg).items()}
+    yo = orc.model_forward(X, coords, t, params, cfg)[0]
+    yt = torch_f64.forward(X, coords, t, params, cfg, device="cpu", chunk=chunk)
+    assert yt.shape == yo.shape == (cfg["B"], cfg["output_dim"]) and yt.dtype == np.float64
+    assert _rel(yt, yo) <= 1e-12, _rel(yt, yo)
+    assert np.abs(yt - yo).max() <= 1e-12 * max(1.0, np.abs(yo).max())
+
+
 def test_chunked_float64_near_kink_units_equal_numpy_oracle():
     """With a kink tolerance wide enough to catch units, the restatement lists the same units, with the same
     per-unit gradient changes, as the numpy oracle (chunk boundaries falling inside the batch)."""
