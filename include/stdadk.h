@@ -82,7 +82,9 @@ typedef struct stdadk_mlp_desc {
  * W_bf16 / WT_bf16 (parameters only, read with STDADK_FLAG_BF16; NULL otherwise): bfloat16 copies of the
  * hidden layers l >= 1 -- W_bf16[l] is W[l] rounded to nearest-even, (out,in) row-major; WT_bf16[l] its
  * transpose (in,out) row-major (the K-contiguous operand of dA = dZ W).  stdadk_bf16_shadow_refresh makes
- * them, the optimiser entry points keep them current (stdadk_bf16_shadow). */
+ * them, the optimiser entry points keep them current (stdadk_bf16_shadow).
+ * With STDADK_FLAG_PACK_F32 the same slots are read as `float *`: W_bf16[l] is the packed forward copy PF
+ * and WT_bf16[l] the packed backward copy PB of W[l], l = 1 .. L-1 (layout below, at stdadk_f32_pack_refresh). */
 typedef struct stdadk_mlp_tensors {
   float *W[STDADK_MAX_HIDDEN + 1];
   float *b[STDADK_MAX_HIDDEN + 1];
@@ -226,6 +228,25 @@ typedef struct stdadk_bf16_shadow {
 } stdadk_bf16_shadow;
 int stdadk_bf16_shadow_refresh(const float *p, const stdadk_bf16_shadow *shadow, stdadk_stream_t stream);
 
+/* Fragment-order fp32 copies of the hidden weights (STDADK_FLAG_PACK_F32; an addition within ABI 10:
+ * one new entry point and one new flag bit, no struct, signature or default behaviour changed).  The fused tail kernels give every
+ * lane of a wave, per 32-deep K chunk c of its 16-column N tile nt, two float4 of weights (halves j = 0, 1); a packed
+ * copy stores those float4 in the order they are loaded, so that a wave's load is one contiguous KiB.  For a hidden
+ * layer l >= 1 (not the output head) with W = W[l] (rows = out, cols = in) row-major, lane = 16 q + c16 (q = 0..3,
+ * c16 = 0..15) and e = 0..3, chunk-major over all N tiles, entries with k beyond K zero:
+ *   forward copy PF (z = a W^T):  N = rows, K = cols, NT = N/16, NCH = ceil(K/32)
+ *     PF[(((c NT + nt) 2 + j) 64 + lane) 4 + e] = W[16 nt + c16][32 c + 16 j + 4 q + e]
+ *   backward copy PB (dA = dZ W): K = rows, N = cols, NT = cols/16, NCH = ceil(rows/32)
+ *     PB[(((c NT + nt) 2 + j) 64 + lane) 4 + e] = W[32 c + 16 j + 4 q + e][16 nt + c16]
+ * Each copy holds NCH * NT * 512 floats (PF: 32 rows ceil(cols/32), PB: 32 cols ceil(rows/32)), is owned by the caller
+ * and must be 16-byte aligned (STDADK_E_ALIGN); rows and cols are multiples of 16 (STDADK_E_SHAPE).  The table is a
+ * stdadk_bf16_shadow whose `dst` / `dst_t` are reinterpreted: `dst` = (float *) PF, `dst_t` = (float *) PB (either may
+ * be NULL).  stdadk_f32_pack_refresh rebuilds every region's copies, zeros included, from the flat buffer p; a
+ * one-call step with STDADK_FLAG_PACK_F32 reads opt->shadow as such a table and its optimiser launch rewrites the
+ * copies from the values it has just stepped (the other optimiser entry points always take bf16 tables).  Same
+ * products, same summation order: results are bit-identical with and without the copies. */
+int stdadk_f32_pack_refresh(const float *p, const stdadk_bf16_shadow *table, stdadk_stream_t stream);
+
 int stdadk_step_advance(int32_t *step_dev, stdadk_stream_t stream);
 
 /* Non-finite guard (ABI 7; scripts/train_st_interp.py:724-733 leaves the epoch at the first batch whose loss is NaN).
@@ -306,6 +327,12 @@ typedef struct stdadk_basis_desc {
                               * fp32 loss, fp32 master weights / gradients / optimiser state.  phi and psi are
                               * evaluated in fp32 and layer 0 stays fp32 on both paths.  Needs the fused tail
                               * kernels (hidden widths multiples of 16 up to 256); STDADK_E_ARG otherwise */
+#define STDADK_FLAG_PACK_F32 128 /* fp32 operands only (with STDADK_FLAG_BF16: STDADK_E_ARG): the fused tail kernels
+                              * stream the hidden weights l >= 1 from the fragment-order copies PF / PB that
+                              * params->W_bf16[l] / WT_bf16[l] then carry as float * (stdadk_f32_pack_refresh;
+                              * every one of them given, 16-byte aligned: STDADK_E_ARG / STDADK_E_ALIGN), and the
+                              * one-call step keeps them current through opt->shadow.  Selects no other kernel and
+                              * changes no result; needs hidden widths the fused tail kernels take              */
 #define STDADK_FLAG_SCATTERED 64 /* the spatial knots are NOT a uniform grid (gmm / random_site initialisers,
                               * st_interp.py:187-343; learnable or fixed): basis->n_levels levels whose SIZES are
                               * basis->side[l] (knot COUNT of level l, any positions; sum = Ks).  The window path

@@ -28,6 +28,16 @@ __global__ __launch_bounds__(TAIL_THREADS) void l1_tail_kernel(L1FwdArgs l, Tail
   l1_window_fwd_body<CPL, LN, BASIS, FREE>(l, smem, r0, min(r0 + 16, l.B));
   PSTAMP(11);
   __syncthreads();
+  if constexpr (!BF) {
+    if (f.pack) {      // scalar (kernel argument; f.pack == b.pack): the same chain on the packed weight copies
+      tail_fwd_body<1, false, false, true>(f, smem, red, tile);
+      PSTAMP(12);
+      __syncthreads();
+      tail_bwd_body<1, false, true>(b, smem, tile);
+      PSTAMP(13);
+      return;
+    }
+  }
   tail_fwd_body<1, false, BF>(f, smem, red, tile);
   PSTAMP(12);
   __syncthreads();
@@ -71,6 +81,9 @@ int l1_tail_launch(const L1FwdArgs &l_in, int basis, bool ln, const TailFwdArgs 
   STDADK_REQUIRE((f.bf16 != 0) == (b.bf16 != 0), STDADK_E_ARG, "l1_tail: forward and backward disagree on bf16 operands");
   if (int rc = tail_check_bf16(f.bf16, f.n_layers, f.L, true, 0)) return rc;
   if (int rc = tail_check_bf16(b.bf16, b.n_layers, b.L, false, 1)) return rc;
+  if (int rc = tail_check_pack(f.bf16, f.n_layers, f.L, true, 0)) return rc;
+  if (int rc = tail_check_pack(b.bf16, b.n_layers, b.L, false, 1)) return rc;
+  f.pack = b.pack = tail_pack(f.bf16, f.n_layers, f.L, true, 0) && tail_pack(b.bf16, b.n_layers, b.L, false, 1);
 #define GO2(CPL_, BF_)                                                                                        \
   (basis == STDADK_BASIS_WENDLAND                                                                             \
        ? (ln ? ((l.halo || l.kperm) ? launch<CPL_, true, 0, true, BF_>(l, f, b, st) : launch<CPL_, true, 0, false, BF_>(l, f, b, st)) \

@@ -542,6 +542,8 @@ struct Ctx {
   const float *d0_coords = nullptr, *d0_t = nullptr, *d0_X = nullptr, *d0_bw = nullptr;
   bool scattered = false;       // STDADK_FLAG_SCATTERED: the knots of a level sit anywhere (window path through knot cell lists)
   bool bf16 = false;            // STDADK_FLAG_BF16: bf16 operands in the fused tail kernels (P->W_bf16 / WT_bf16)
+  bool pack = false;            // STDADK_FLAG_PACK_F32: fragment-order fp32 weight copies in the fused tail kernels (the
+                                // P->W_bf16 / WT_bf16 slots read as float *PF / *PB)
   bool cap32 = false;           // this batch's tail launches use <= 32-row tiles (bf16 + dense layer 0 in the launch)
   bool save = true;             // false in eval mode: the forward keeps nothing for a backward (xhat, rstd, act, psi)
   bool log_bw = false;          // basis->s_bw holds log-bandwidths (learnable knots)
@@ -626,10 +628,12 @@ static bool tail_enabled() {
 }
 
 // layer l of the model as the tail kernels take it: saving nothing (xhat, rstd, act NULL), or into the workspace of `c`
-static TailLayer tail_layer(const stdadk_mlp_desc *d, const stdadk_mlp_tensors *P, bool bf16, int l) {
+static TailLayer tail_layer(const stdadk_mlp_desc *d, const stdadk_mlp_tensors *P, bool bf16, int l, bool pack = false) {
   TailLayer t;
   t.W = P->W[l]; t.b = P->b[l];
   t.Wbf = bf16 ? P->W_bf16[l] : nullptr; t.WTbf = bf16 ? P->WT_bf16[l] : nullptr;
+  t.PF = pack ? reinterpret_cast<const float *>(P->W_bf16[l]) : nullptr;
+  t.PB = pack ? reinterpret_cast<const float *>(P->WT_bf16[l]) : nullptr;
   t.g = d->layernorm ? P->ln_g[l] : nullptr; t.be = d->layernorm ? P->ln_b[l] : nullptr;
   t.h = d->hidden[l]; t.hp = l > 0 ? d->hidden[l - 1] : d->in_dim;
   t.xhat = t.rstd = t.act = nullptr;
@@ -637,7 +641,7 @@ static TailLayer tail_layer(const stdadk_mlp_desc *d, const stdadk_mlp_tensors *
   return t;
 }
 static TailLayer tail_layer(const Ctx &c, int l) {
-  TailLayer t = tail_layer(c.d, c.P, c.bf16, l);
+  TailLayer t = tail_layer(c.d, c.P, c.bf16, l, c.pack);
   t.xhat = c.ws + c.pl.xhat[l]; t.rstd = c.ws + c.pl.rstd[l]; t.act = c.ws + c.pl.act[l];
   return t;
 }
@@ -1256,6 +1260,20 @@ static int open_step(Ctx &c, const stdadk_basis_desc *b, const stdadk_mlp_desc *
   STDADK_REQUIRE(!c.bf16 || (tail_enabled() && d->n_hidden >= 1 && tail_supported(d, 1)), STDADK_E_ARG,
                  "step: STDADK_FLAG_BF16 needs the fused tail kernels (hidden widths multiples of 16 up to %d, out_dim <= %d)",
                  TAIL_MAX_W, TAIL_MAXQ);
+  c.pack = (flags & STDADK_FLAG_PACK_F32) != 0;
+  if (c.pack) {
+    STDADK_REQUIRE(!c.bf16, STDADK_E_ARG, "step: STDADK_FLAG_PACK_F32 and STDADK_FLAG_BF16 exclude each other");
+    STDADK_REQUIRE(tail_enabled() && d->n_hidden >= 1 && tail_supported(d, 1), STDADK_E_ARG,
+                   "step: STDADK_FLAG_PACK_F32 needs the fused tail kernels (hidden widths multiples of 16 up to %d, "
+                   "out_dim <= %d)", TAIL_MAX_W, TAIL_MAXQ);
+    for (int l = 1; P && l < d->n_hidden; ++l) {
+      STDADK_REQUIRE(P->W_bf16[l] && P->WT_bf16[l], STDADK_E_ARG,
+                     "step: STDADK_FLAG_PACK_F32 needs the packed copies of layer %d (params->W_bf16 / WT_bf16 as "
+                     "float *; stdadk_f32_pack_refresh)", l);
+      STDADK_REQUIRE(aligned16(P->W_bf16[l]) && aligned16(P->WT_bf16[l]), STDADK_E_ALIGN,
+                     "step: the packed copies of layer %d must be 16-byte aligned", l);
+    }
+  }
   STDADK_REQUIRE(workspace_bytes >= c.pl.total_floats * sizeof(float), STDADK_E_WORKSPACE,
                  "step: workspace %zu < %zu bytes", workspace_bytes, c.pl.total_floats * sizeof(float));
   c.d = d; c.P = P; c.G = G; c.ws = (float *)workspace; c.st = (hipStream_t)stream; c.B = B;
@@ -1752,7 +1770,7 @@ static int train_step_impl(StepCall s, const stdadk_sparsity_desc *sparsity, con
   stdadk_adam_group gr;
   AdamHyper h;
   optim_group(o, clip ? parts : nullptr, n_parts, s.loss_sum, &gr, &h);
-  rc = adamw_launch("adamw", 1, &gr, nullptr, h, bin, s.stream);
+  rc = adamw_launch("adamw", 1, &gr, nullptr, h, bin, s.stream, (s.flags & STDADK_FLAG_PACK_F32) != 0);
   if (rc == 0 && (bin || out.binned_next)) *nb.binned = 1;
   return rc;
 }

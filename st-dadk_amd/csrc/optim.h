@@ -25,6 +25,7 @@ static inline void optim_group(const stdadk_optim_desc *o, const float *parts, i
 // Validates `ng` (1 or 2) groups -- errors are reported under the prefix `what` -- and steps them in ONE launch:
 // adamw_ema_kernel, adamw_ema2_kernel or, with `bin` (one group only), adamw_bin_kernel, whose extra workgroups bin
 // the next batch.  A single group may be empty (nothing is launched); the first group's workgroups keep the guard.
+// `pack_f32` (STDADK_FLAG_PACK_F32 of a one-call step): the groups' shadow tables name fragment-order fp32 copies.
 int adamw_launch(const char *what, int ng, const stdadk_adam_group *g0, const stdadk_adam_group *g1, const AdamHyper &h,
-                 const BinSmallArgs *bin, stdadk_stream_t stream);
+                 const BinSmallArgs *bin, stdadk_stream_t stream, bool pack_f32 = false);
 }  // namespace stdadk

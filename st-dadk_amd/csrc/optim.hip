@@ -54,6 +54,7 @@ __global__ __launch_bounds__(256) void sumsq2_kernel(const float *__restrict__ g
 // bf16 operand copies of some matrices of the flat buffer (stdadk_bf16_shadow), by value in the kernel arguments
 struct ShadowArgs {
   int n;
+  int pack;                             // the regions' copies are the fragment-order fp32 copies PF / PB (stdadk.h)
   int64_t lo, hi;                       // union of the regions' element ranges: one compare rejects the rest
   stdadk_bf16_region r[STDADK_MAX_HIDDEN];
 };
@@ -77,6 +78,24 @@ __device__ __forceinline__ void shadow_store(const ShadowArgs &sh, int64_t e, fl
     const stdadk_bf16_region &r = sh.r[i];
     const int64_t idx = e - r.off;
     if (idx < 0 || idx >= (int64_t)r.rows * r.cols) continue;
+    if (sh.pack) {
+      // W[row][col .. col + 3], col a multiple of 4: in PF (N = rows, K = cols) the four are the components e of ONE
+      // lane's float4 (k = col + e); in PB (K = rows, N = cols) they are component e = row & 3 of four neighbouring
+      // lanes (n = col + i), 16 bytes apart
+      const int row = (int)(idx / r.cols), col = (int)(idx - (int64_t)row * r.cols);
+      if (r.dst) {
+        const size_t v = ((size_t)((col >> 5) * (r.rows >> 4) + (row >> 4)) * 2 + ((col >> 4) & 1)) * 64 +
+                         16 * ((col >> 2) & 3) + (row & 15);
+        reinterpret_cast<float4 *>(r.dst)[v] = p;
+      }
+      if (r.dst_t) {
+        const size_t v = ((size_t)((row >> 5) * (r.cols >> 4) + (col >> 4)) * 2 + ((row >> 4) & 1)) * 64 +
+                         16 * ((row >> 2) & 3) + (col & 15);
+        float *t = reinterpret_cast<float *>(r.dst_t) + 4 * v + (row & 3);
+        t[0] = p.x; t[4] = p.y; t[8] = p.z; t[12] = p.w;
+      }
+      return;
+    }
     const uint32_t lo = pack_bf16(p.x, p.y), hi = pack_bf16(p.z, p.w);
     if (r.dst) *reinterpret_cast<uint2 *>(r.dst + idx) = make_uint2(lo, hi);
     if (r.dst_t) {
@@ -97,8 +116,25 @@ __global__ __launch_bounds__(256) void shadow_refresh_kernel(const float *__rest
   }
 }
 
-static int fill_shadow(ShadowArgs &o, const stdadk_bf16_shadow *sh, const float *p, int64_t n) {
-  o.n = 0; o.lo = 0; o.hi = 0;
+// The entries of PF / PB beyond K (the second half of the last chunk when K is an odd multiple of 16): no element of W
+// lands there, the refresh writes their zeros once.
+__global__ __launch_bounds__(256) void pack_pad_kernel(ShadowArgs sh) {
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int i = 0; i < sh.n; ++i) {
+    const stdadk_bf16_region &r = sh.r[i];
+    for (int t = 0; t < 2; ++t) {
+      float *dst = reinterpret_cast<float *>(t ? r.dst_t : r.dst);
+      const int K = t ? r.rows : r.cols, N = t ? r.cols : r.rows;
+      if (!dst || (K & 31) == 0) continue;
+      const int NT = N >> 4, c = K >> 5;
+      for (int j = (int)(blockIdx.x * blockDim.x + threadIdx.x); j < NT * 64; j += (int)(gridDim.x * blockDim.x))
+        reinterpret_cast<float4 *>(dst)[((size_t)(c * NT + (j >> 6)) * 2 + 1) * 64 + (j & 63)] = zero;
+    }
+  }
+}
+
+static int fill_shadow(ShadowArgs &o, const stdadk_bf16_shadow *sh, const float *p, int64_t n, bool pack = false) {
+  o.n = 0; o.lo = 0; o.hi = 0; o.pack = pack ? 1 : 0;
   if (!sh || sh->n == 0) return 0;
   STDADK_REQUIRE(sh->n > 0 && sh->n <= STDADK_MAX_HIDDEN, STDADK_E_ARG, "bf16 shadow: %d regions (1..%d)", sh->n,
                  STDADK_MAX_HIDDEN);
@@ -110,8 +146,15 @@ static int fill_shadow(ShadowArgs &o, const stdadk_bf16_shadow *sh, const float 
                        (n < 0 || r.off + cnt <= n),
                    STDADK_E_SHAPE, "bf16 shadow: region %d (off %lld, %d x %d) outside the buffer or not 4-aligned", i,
                    (long long)r.off, r.rows, r.cols);
-    STDADK_REQUIRE((!r.dst || (reinterpret_cast<uintptr_t>(r.dst) & 7) == 0) && (r.dst || r.dst_t), STDADK_E_ALIGN,
-                   "bf16 shadow: region %d copies NULL or not 8-byte aligned", i);
+    if (pack) {
+      STDADK_REQUIRE((r.rows & 15) == 0 && (r.cols & 15) == 0, STDADK_E_SHAPE,
+                     "packed fp32 copies: region %d (%d x %d) is not made of 16 x 16 tiles", i, r.rows, r.cols);
+      STDADK_REQUIRE((r.dst || r.dst_t) && aligned16(r.dst) && aligned16(r.dst_t), STDADK_E_ALIGN,
+                     "packed fp32 copies: region %d copies NULL or not 16-byte aligned", i);
+    } else {
+      STDADK_REQUIRE((!r.dst || (reinterpret_cast<uintptr_t>(r.dst) & 7) == 0) && (r.dst || r.dst_t), STDADK_E_ALIGN,
+                     "bf16 shadow: region %d copies NULL or not 8-byte aligned", i);
+    }
     o.r[i] = r;
     if (i == 0 || r.off < o.lo) o.lo = r.off;
     if (i == 0 || r.off + cnt > o.hi) o.hi = r.off + cnt;
@@ -295,7 +338,7 @@ extern "C" int stdadk_sumsq_f32(const float *g, int64_t n, float *parts, int32_t
 // The one place that validates a parameter group against the hyper-parameters and fills the kernel's arguments.
 // `guard`: this group's launch keeps the non-finite guard; `may_be_empty`: n == 0 is accepted and leaves a.n == 0.
 static int fill_adam(AdamArgs &a, const char *what, const stdadk_adam_group *gr, const AdamHyper &h, bool guard,
-                     bool may_be_empty) {
+                     bool may_be_empty, bool pack) {
   STDADK_REQUIRE((h.loss_watch != nullptr) == (h.nonfinite_step != nullptr), STDADK_E_ARG,
                  "%s: loss_watch and nonfinite_step go together (both or neither)", what);
   a.n = 0;
@@ -310,7 +353,7 @@ static int fill_adam(AdamArgs &a, const char *what, const stdadk_adam_group *gr,
   a.max_norm = gr->max_norm; a.sumsq = gr->sumsq_parts; a.n_parts = gr->n_parts; a.grad_mul = h.grad_mul;
   a.ema_decay = h.ema_decay;
   a.watch = guard ? h.loss_watch : nullptr; a.bad_step = guard ? h.nonfinite_step : nullptr;
-  if (int rc = fill_shadow(a.sh, gr->shadow, gr->p, gr->n)) return rc;
+  if (int rc = fill_shadow(a.sh, gr->shadow, gr->p, gr->n, pack)) return rc;
   STDADK_REQUIRE(a.sh.n == 0 || ((reinterpret_cast<uintptr_t>(gr->g) | reinterpret_cast<uintptr_t>(gr->m) |
                                   reinterpret_cast<uintptr_t>(gr->v) | reinterpret_cast<uintptr_t>(gr->ema)) & 15) == 0,
                  STDADK_E_ALIGN, "%s: bf16 shadows need 16-byte aligned buffers", what);
@@ -358,11 +401,11 @@ static int launch_adam(const AdamArgs *a, int ng, const BinSmallArgs *bin, hipSt
 }
 
 int stdadk::adamw_launch(const char *what, int ng, const stdadk_adam_group *g0, const stdadk_adam_group *g1,
-                         const AdamHyper &h, const BinSmallArgs *bin, stdadk_stream_t stream) {
+                         const AdamHyper &h, const BinSmallArgs *bin, stdadk_stream_t stream, bool pack_f32) {
   const stdadk_adam_group *gr[2] = {g0, g1};
   AdamArgs a[2];
   for (int i = 0; i < ng; ++i)
-    if (int rc = fill_adam(a[i], what, gr[i], h, i == 0, ng == 1)) return rc;
+    if (int rc = fill_adam(a[i], what, gr[i], h, i == 0, ng == 1, pack_f32)) return rc;
   if (a[0].n == 0) return 0;                      // (one empty group)
   return launch_adam(a, ng, bin, (hipStream_t)stream);
 }
@@ -388,6 +431,20 @@ extern "C" int stdadk_bf16_shadow_refresh(const float *p, const stdadk_bf16_shad
   if (blocks > 1024) blocks = 1024;
   STDADK_LAUNCH(shadow_refresh_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, sh);
   STDADK_CHECK_LAUNCH("bf16_shadow_refresh");
+  return 0;
+}
+
+extern "C" int stdadk_f32_pack_refresh(const float *p, const stdadk_bf16_shadow *table, stdadk_stream_t stream) {
+  STDADK_REQUIRE(p && table, STDADK_E_ARG, "f32_pack_refresh: NULL pointer");
+  ShadowArgs sh;
+  if (int rc = fill_shadow(sh, table, p, -1, true)) return rc;
+  if (sh.n == 0) return 0;
+  int64_t blocks = ceil_div((sh.hi - sh.lo) / 4, 256);
+  if (blocks > 1024) blocks = 1024;
+  STDADK_LAUNCH(shadow_refresh_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, sh);
+  STDADK_CHECK_LAUNCH("f32_pack_refresh");
+  STDADK_LAUNCH(pack_pad_kernel, dim3(4), dim3(256), 0, (hipStream_t)stream, sh);
+  STDADK_CHECK_LAUNCH("f32_pack_refresh (padding)");
   return 0;
 }
 

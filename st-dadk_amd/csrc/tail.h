@@ -18,6 +18,8 @@ struct TailLayer {
   const uint16_t *Wbf;   // STDADK_FLAG_BF16: bf16 copy of W [h][hp], and of its transpose [hp][h] (the operand of
   const uint16_t *WTbf;  // dA = dZ W); NULL otherwise
   const float *W;      // [h][hp]  (nn.Linear layout)
+  const float *PF = nullptr;   // STDADK_FLAG_PACK_F32: fragment-order fp32 copies of W (stdadk.h) for z = a W^T (PF) and
+  const float *PB = nullptr;   // dA = dZ W (PB): the fp32 GEMM phases stream them when non-NULL, else W itself
   const float *b;      // [h]
   const float *g;      // LayerNorm gamma / beta or NULL
   const float *be;
@@ -72,6 +74,8 @@ struct TailFwdArgs {
   const int *step_dev;
   int bf16;                     // STDADK_FLAG_BF16: the layers' GEMMs take bf16 operands (L[i].Wbf)
   int krot;                     // per-workgroup rotation of the K-chunk order (set by the launch code, tail_krot())
+  int pack;                     // every layer carries its packed copy PF: the fp32 GEMM phases stream it (set by the
+                                // launch code, tail_pack())
   unsigned long long *stamps;   // -DSTDADK_DIAG builds only: [blocks][16] wall-clock stamps (100 MHz), else NULL
 };
 
@@ -93,6 +97,7 @@ struct TailBwdArgs {
   const int *step_dev;
   int bf16;                     // STDADK_FLAG_BF16: dA = dZ W with bf16 operands (L[i].WTbf)
   int krot;                     // as in TailFwdArgs
+  int pack;                     // as in TailFwdArgs, with the copies PB of the layers above the first
   int *zero_ints = nullptr;     // n_zero ints the workgroup of tile 0 clears (arrival counters of the weight-gradient
   int n_zero = 0;               // launch behind this one, FinArgs), or NULL
   unsigned long long *stamps;   // -DSTDADK_DIAG builds only (see TailFwdArgs), else NULL
@@ -110,6 +115,11 @@ int tail_rows(int64_t B, bool cap32 = false);
 // STDADK_FLAG_BF16 (`bf16` != 0): layers first .. n - 1 must carry their 16-byte aligned bf16 weight copies, Wbf for
 // the forward (`fwd`) and WTbf for the backward; 0 or an error code (set_error)
 int tail_check_bf16(int bf16, int n, const TailLayer *L, bool fwd, int first);
+// STDADK_FLAG_PACK_F32: a packed copy that is given (PF for the forward, PB for the backward) must be 16-byte aligned
+// and stands for fp32 operands only (STDADK_E_ALIGN / STDADK_E_ARG)
+int tail_check_pack(int bf16, int n, const TailLayer *L, bool fwd, int first);
+// 1 when fp32 layers first .. n - 1 (at least one) all carry that copy: the launch then runs the packed bodies
+int tail_pack(int bf16, int n, const TailLayer *L, bool fwd, int first);
 int tail_forward(const TailFwdArgs &a, hipStream_t st);
 int tail_backward(const TailBwdArgs &a, hipStream_t st, bool cap32 = false);
 // training: forward (with the loss) and backward of every row tile in one launch

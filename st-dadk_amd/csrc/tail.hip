@@ -19,12 +19,18 @@ template <int MT, bool D0, bool BF>
 __global__ TAIL_BOUNDS void tail_fwd_kernel(TailFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ float red[TAIL_WAVES];
+  if constexpr (!BF) {
+    if (a.pack) { tail_fwd_body<MT, D0, false, true>(a, smem, red, blockIdx.x); return; }   // scalar: kernel argument
+  }
   tail_fwd_body<MT, D0, BF>(a, smem, red, blockIdx.x);
 }
 
 template <int MT, bool BF>
 __global__ TAIL_BOUNDS void tail_bwd_kernel(TailBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  if constexpr (!BF) {
+    if (a.pack) { tail_bwd_body<MT, false, true>(a, smem, blockIdx.x); return; }
+  }
   tail_bwd_body<MT, BF>(a, smem, blockIdx.x);
 }
 
@@ -37,6 +43,14 @@ template <int MT, bool D0, bool BF>
 __global__ TAIL_BOUNDS void tail_fwd_bwd_kernel(TailFwdArgs f, TailBwdArgs b) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ float red[TAIL_WAVES];
+  if constexpr (!BF) {
+    if (f.pack) {      // scalar (kernel argument; f.pack == b.pack): the same chain on the packed copies
+      tail_fwd_body<MT, D0, false, true>(f, smem, red, blockIdx.x);
+      __syncthreads();
+      tail_bwd_body<MT, false, true>(b, smem, blockIdx.x);
+      return;
+    }
+  }
   tail_fwd_body<MT, D0, BF>(f, smem, red, blockIdx.x);
   __syncthreads();
   tail_bwd_body<MT, BF>(b, smem, blockIdx.x);
@@ -70,6 +84,23 @@ int tail_check_bf16(int bf16, int n, const TailLayer *L, bool fwd, int first) {
                    STDADK_E_ARG, "tail: STDADK_FLAG_BF16 needs the 16-byte aligned bf16 weight copies of every layer after "
                    "the first (params->W_bf16 / WT_bf16; stdadk_bf16_shadow_refresh)");
   return 0;
+}
+
+int tail_check_pack(int bf16, int n, const TailLayer *L, bool fwd, int first) {
+  for (int i = first; i < n; ++i) {
+    const float *pk = fwd ? L[i].PF : L[i].PB;
+    if (!pk) continue;
+    STDADK_REQUIRE(!bf16, STDADK_E_ARG, "tail: packed fp32 weight copies together with bf16 operands");
+    STDADK_REQUIRE(aligned16(pk), STDADK_E_ALIGN, "tail: the packed fp32 weight copies must be 16-byte aligned");
+  }
+  return 0;
+}
+
+int tail_pack(int bf16, int n, const TailLayer *L, bool fwd, int first) {
+  if (bf16 || n <= first) return 0;
+  for (int i = first; i < n; ++i)
+    if (!(fwd ? L[i].PF : L[i].PB)) return 0;
+  return 1;
 }
 
 static int check_d0(const TailFwdArgs &a) {
@@ -128,6 +159,8 @@ int tail_forward(const TailFwdArgs &a_in, hipStream_t st) {
   const int r = tail_rows(a.B, bf && d0);
   if (int rc = check_d0(a)) return rc;
   if (int rc = tail_check_bf16(a.bf16, a.n_layers, a.L, true, 0)) return rc;
+  if (int rc = tail_check_pack(a.bf16, a.n_layers, a.L, true, 0)) return rc;
+  a.pack = tail_pack(a.bf16, a.n_layers, a.L, true, 0);
   return TAIL_DISPATCH(launch_fwd, r, d0, bf, a, st);
 }
 
@@ -173,6 +206,10 @@ int tail_forward_backward(const TailFwdArgs &f_in, const TailBwdArgs &b_in, hipS
   if (int rc = check_d0(f)) return rc;
   if (int rc = tail_check_bf16(f.bf16, f.n_layers, f.L, true, 0)) return rc;
   if (int rc = tail_check_bf16(b.bf16, b.n_layers, b.L, false, 1)) return rc;
+  if (int rc = tail_check_pack(f.bf16, f.n_layers, f.L, true, 0)) return rc;
+  if (int rc = tail_check_pack(b.bf16, b.n_layers, b.L, false, 1)) return rc;
+  // one choice for the launch: the packed bodies when both chains have their copies
+  f.pack = b.pack = tail_pack(f.bf16, f.n_layers, f.L, true, 0) && tail_pack(b.bf16, b.n_layers, b.L, false, 1);
   return TAIL_DISPATCH(launch_fwd_bwd, r, d0, bf, f, b, st);
 }
 
@@ -183,6 +220,8 @@ int tail_backward(const TailBwdArgs &a_in, hipStream_t st, bool cap32) {
   a.krot = tail_krot();
   const int r = tail_rows(a.B, cap32);
   if (int rc = tail_check_bf16(a.bf16, a.n_layers, a.L, false, 1)) return rc;
+  if (int rc = tail_check_pack(a.bf16, a.n_layers, a.L, false, 1)) return rc;
+  a.pack = tail_pack(a.bf16, a.n_layers, a.L, false, 1);
   if (a.bf16) return r == 64 ? launch_bwd<4, true>(a, st) : (r == 32 ? launch_bwd<2, true>(a, st) : launch_bwd<1, true>(a, st));
   return r == 64 ? launch_bwd<4, false>(a, st) : (r == 32 ? launch_bwd<2, false>(a, st) : launch_bwd<1, false>(a, st));
 }

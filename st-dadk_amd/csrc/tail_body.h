@@ -8,6 +8,7 @@
 #pragma once
 #include "tail.h"
 #include "basis.h"
+#include <type_traits>
 
 namespace stdadk {
 
@@ -106,6 +107,23 @@ struct OpF32 {
         }
       }
     }
+  }
+};
+
+// fp32 operands from a fragment-order copy of the weights (STDADK_FLAG_PACK_F32; PF / PB of stdadk.h, kept current by
+// the optimiser launch): the float4 of (chunk c, N tile nt, half j, lane) sits at float4 index
+// ((c NT + nt) 2 + j) 64 + lane and holds exactly the four (k, n) that OpF32<KN>::load gives that lane, zeros beyond
+// K.  A wave's fragment load is then one contiguous KiB -- eight full 128-byte lines, each asked for once -- where
+// OpF32<false> takes 64 B of each of 16 rows 1 KiB apart (every line requested by two instructions) and OpF32<true>
+// four dwords per half.  Same mma, same k order, same sums: the results are bit-identical.  One layout serves both
+// products (W is the [N][K] operand of PF and the [K][N] operand of PB), so there is no KN here; every address is
+// inside the copy for every chunk below ceil(K / 32), so nothing is clamped.
+struct OpF32P : OpF32<false> {
+  static __device__ __forceinline__ void load(BFrag &f, const float *__restrict__ P, int N, int K, int c, int wave,
+                                              int c16, int q) {
+    const float4 *src = reinterpret_cast<const float4 *>(P) + ((size_t)(c * (N >> 4) + wave) * 2) * 64 + 16 * q + c16;
+    f.v[0] = src[0];
+    f.v[1] = src[64];
   }
 };
 
@@ -489,8 +507,13 @@ __device__ __forceinline__ void ln_bwd_rows(const LnBwdCtx &c, float *cur, u16 *
 // stay fp32).  LDS then holds ONE fp32 tile (z / LayerNorm in place; the head reads it) and the bf16 image of the
 // current activations in the place of the second fp32 tile -- with D0 the fp32 pair stays (the features of layer 0
 // use both halves) and the image follows them.
-template <int MT, bool D0 = false, bool BF = false>
+// PK (fp32 operands only): every layer carries its packed copy PF and the GEMM phases stream it (OpF32P).  A template
+// parameter, chosen once per kernel by a scalar test of the arguments: a choice per phase would let the two preloads
+// meet in front of the GEMM, where the compiler can only wait for the larger of their outstanding-load counts.
+template <int MT, bool D0 = false, bool BF = false, bool PK = false>
 __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float *smem, float *red, const int tile) {
+  static_assert(!(BF && PK), "packed copies are fp32 operands");
+  using OpW = std::conditional_t<PK, OpF32P, OpF32<false>>;
   constexpr int R = 16 * MT, RPW = (R + TAIL_WAVES - 1) / TAIL_WAVES;
   float *act0 = smem, *act1 = (BF && !D0) ? smem : smem + R * ACT_LD;
   u16 *abf = reinterpret_cast<u16 *>(smem + (D0 ? 2 : 1) * R * ACT_LD);
@@ -501,7 +524,7 @@ __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float *smem,
   // workgroups b, b + 8, ... share an XCD: consecutive ones of them start their K walks one chunk apart
   const int rot = a.krot ? (int)(blockIdx.x >> 3) : 0;
   STAMP(0);
-  // z = a W^T, W = [N][K]: OpF32<false> on `cur` and W, or OpBF16 on the image and Wbf.  The kind is chosen at each
+  // z = a W^T, W = [N][K]: OpF32<false> on `cur` and W (PK: OpF32P on the packed copy PF), or OpBF16 on the image and Wbf.  The kind is chosen at each
   // preload and GEMM call, with its own fragment variable, image and weight pointer: chosen behind the operand
   // description, the 64-row bf16 kernels compile to other code (profiles/tail_gemm_refactor.md).  The dense layer 0
   // multiplies fp32 features whatever BF says: `wpre`.
@@ -515,7 +538,7 @@ __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float *smem,
   } else {
     if (a.n_layers > 0) {
       if constexpr (BF) preload_w<OpBF16>(wpre_h, a.L[0].Wbf, a.L[0].h, a.L[0].hp, wave, c16, q, rot);
-      else preload_w<OpF32<false>>(wpre, a.L[0].W, a.L[0].h, a.L[0].hp, wave, c16, q, rot);
+      else preload_w<OpW>(wpre, PK ? a.L[0].PF : a.L[0].W, a.L[0].h, a.L[0].hp, wave, c16, q, rot);
     }
   }
   if constexpr (!D0) {
@@ -604,12 +627,12 @@ __device__ __forceinline__ void tail_fwd_body(const TailFwdArgs &a, float *smem,
     } else {
       if (li == 0) WSTAMP(0);
       if constexpr (BF) gemm16_pre<MT, OpBF16>(acc, abf, L.Wbf, h, hp, wave, c16, q, wpre_h, rot);
-      else gemm16_pre<MT, OpF32<false>>(acc, cur, L.W, h, hp, wave, c16, q, wpre, rot);
+      else gemm16_pre<MT, OpW>(acc, cur, PK ? L.PF : L.W, h, hp, wave, c16, q, wpre, rot);
       if (li == 0) WSTAMP(1);
     }
     if (li + 1 < a.n_layers) {
       if constexpr (BF) preload_w<OpBF16>(wpre_h, a.L[li + 1].Wbf, a.L[li + 1].h, a.L[li + 1].hp, wave, c16, q, rot);
-      else preload_w<OpF32<false>>(wpre, a.L[li + 1].W, a.L[li + 1].h, a.L[li + 1].hp, wave, c16, q, rot);
+      else preload_w<OpW>(wpre, PK ? a.L[li + 1].PF : a.L[li + 1].W, a.L[li + 1].h, a.L[li + 1].hp, wave, c16, q, rot);
     }
     STAMP(2 + 4 * (li < 0 ? 0 : li));
     // z = acc + bias into the other activation buffer
@@ -814,8 +837,10 @@ __device__ __forceinline__ void bwd_head(const TailBwdArgs &a, float *d0, float 
 
 // BF: dA = dZ W with bf16 operands (the transposed weight copies WTbf as the K-contiguous operand): ONE fp32
 // gradient tile (LayerNorm backward in place, the GEMM's output lands in it again) + the bf16 image of dZ.
-template <int MT, bool BF = false>
+template <int MT, bool BF = false, bool PK = false>     // PK: as in the forward body, with the copies PB
 __device__ __forceinline__ void tail_bwd_body(const TailBwdArgs &a, float *smem, const int tile) {
+  static_assert(!(BF && PK), "packed copies are fp32 operands");
+  using OpW = std::conditional_t<PK, OpF32P, OpF32<true>>;
   constexpr int R = 16 * MT, RPW = (R + TAIL_WAVES - 1) / TAIL_WAVES;
   float *d0 = smem, *d1 = BF ? smem : smem + R * ACT_LD;
   u16 *abf = reinterpret_cast<u16 *>(smem + R * ACT_LD);
@@ -874,11 +899,11 @@ __device__ __forceinline__ void tail_bwd_body(const TailBwdArgs &a, float *smem,
     const int h = L.h;
     BFrag wpre;
     BFragH wpre_h;
-    // dA = dZ W, W = [K][N]: OpF32<true> on `cur` and W, or OpBF16 on the image and the transposed copy WTbf (the
+    // dA = dZ W, W = [K][N]: OpF32<true> on `cur` and W (PK: OpF32P on the packed copy PB), or OpBF16 on the image and the transposed copy WTbf (the
     // kind chosen at each call, as in the forward body)
     if (li > 0) {                  // for the dA GEMM at the end of this pass
       if constexpr (BF) preload_w<OpBF16>(wpre_h, L.WTbf, L.hp, h, wave, c16, q, rot);
-      else preload_w<OpF32<true>>(wpre, L.W, L.hp, h, wave, c16, q, rot);
+      else preload_w<OpW>(wpre, PK ? L.PB : L.W, L.hp, h, wave, c16, q, rot);
     }
     // ---- (a) Dropout -> ReLU -> LayerNorm backward of the wave's rows, specialised on the layer's width
     // (ln_bwd_rows below).  Its global inputs (xhat rows, gamma, beta, rstd) were requested one phase early (ln_inputs).
@@ -921,7 +946,7 @@ __device__ __forceinline__ void tail_bwd_body(const TailBwdArgs &a, float *smem,
     ln_inputs(a.L[li - 1]);        // consumed after the GEMM, in the next pass
     lds_barrier();                 // every wave's dZ rows are in `cur`
     if constexpr (BF) gemm16_pre<MT, OpBF16>(acc, abf, L.WTbf, hp, h, wave, c16, q, wpre_h, rot);
-    else gemm16_pre<MT, OpF32<true>>(acc, cur, L.W, hp, h, wave, c16, q, wpre, rot);
+    else gemm16_pre<MT, OpW>(acc, cur, PK ? L.PB : L.W, hp, h, wave, c16, q, wpre, rot);
     STAMP(3 + 3 * (a.n_layers - 1 - li));      // dA GEMM of this pass
     if (wave < NT) {
 #pragma unroll

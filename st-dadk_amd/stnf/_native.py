@@ -97,6 +97,7 @@ FLAG_WINDOW = 8
 FLAG_PREBINNED = 16
 FLAG_BF16 = 32
 FLAG_SCATTERED = 64
+FLAG_PACK_F32 = 128        # fragment-order fp32 copies of the hidden weights in the W_bf16 / WT_bf16 slots
 KNOT_CELLS = 32          # cells per axis of the knot cell lists (csrc/window.h)
 
 _lib = None
@@ -215,6 +216,7 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_int32, C.c_float, C.c_float, C.POINTER(BF16Shadow),
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "stdadk_bf16_shadow_refresh": (C.c_int, [C.c_void_p, C.POINTER(BF16Shadow), C.c_void_p]),
+    "stdadk_f32_pack_refresh": (C.c_int, [C.c_void_p, C.POINTER(BF16Shadow), C.c_void_p]),
 }
 
 
@@ -342,9 +344,11 @@ def make_desc(in_dim, hidden, out_dim, layernorm, dropout_p, ln_eps=1e-5):
     return d
 
 
-def make_tensors(Ws, bs, gs, betas, bf16=None):
+def make_tensors(Ws, bs, gs, betas, bf16=None, packed=None):
     """Pack per-layer tensors (lists; gs/betas may be None) into the ABI struct.  `bf16`: per Linear index
-    None or the pair (W_bf16 (out,in), WT_bf16 (in,out)) of torch.bfloat16 operand copies (FLAG_BF16)."""
+    None or the pair (W_bf16 (out,in), WT_bf16 (in,out)) of torch.bfloat16 operand copies (FLAG_BF16).  `packed`
+    (instead): per Linear index None or the pair (PF, PB) of float32 fragment-order copies (FLAG_PACK_F32), which
+    travel in the same slots."""
     s = MlpTensors()
     for i, (w, b) in enumerate(zip(Ws, bs)):
         s.W[i], s.b[i] = _dev(w, f"W[{i}]"), _dev(b, f"b[{i}]")
@@ -357,6 +361,14 @@ def make_tensors(Ws, bs, gs, betas, bf16=None):
                 if pair[0].dtype != torch.bfloat16 or pair[1].dtype != torch.bfloat16:
                     raise RuntimeError("make_tensors: the operand copies must be torch.bfloat16")
                 s.W_bf16[i], s.WT_bf16[i] = _dev(pair[0], f"W_bf16[{i}]"), _dev(pair[1], f"WT_bf16[{i}]")
+    if packed is not None:
+        if bf16 is not None:
+            raise RuntimeError("make_tensors: bf16 operand copies and packed fp32 copies share their slots")
+        for i, pair in enumerate(packed):
+            if pair is not None:
+                if pair[0].dtype != torch.float32 or pair[1].dtype != torch.float32:
+                    raise RuntimeError("make_tensors: the packed copies must be torch.float32")
+                s.W_bf16[i], s.WT_bf16[i] = _dev(pair[0], f"PF[{i}]"), _dev(pair[1], f"PB[{i}]")
     return s
 
 
@@ -376,6 +388,18 @@ def bf16_shadow_refresh(p, shadow):
     """Rewrite every region's bf16 copies from the fp32 buffer `p` (stdadk_bf16_shadow_refresh)."""
     rc = lib().stdadk_bf16_shadow_refresh(_dev(p, "p"), C.byref(shadow), _stream())
     _check(rc, "stdadk_bf16_shadow_refresh")
+
+
+def pack_f32_sizes(rows, cols):
+    """Floats of the packed forward / backward copy (PF, PB of stdadk.h) of a (rows, cols) weight."""
+    return 32 * rows * ((cols + 31) // 32), 32 * cols * ((rows + 31) // 32)
+
+
+def f32_pack_refresh(p, table):
+    """Rebuild every region's packed fp32 copies (dst = PF, dst_t = PB, float32 tensors in a make_bf16_shadow table)
+    from the fp32 buffer `p` (stdadk_f32_pack_refresh)."""
+    rc = lib().stdadk_f32_pack_refresh(_dev(p, "p"), C.byref(table), _stream())
+    _check(rc, "stdadk_f32_pack_refresh")
 
 
 def mlp_workspace_bytes(desc, B):

@@ -182,6 +182,11 @@ class TrainStep:
         replicated mode (scripts/train_st_interp.py:696-712: global-norm clip, step, EMA) up to the order of the
         clip norm's partial sums.
 
+    Packed weights (`pack_weights`, default on; `STNF_NO_PACK_WEIGHTS=1` turns it off): fp32 one-call steps with hidden
+    widths of 128 / 256 stream the hidden weights after the first from fragment-order copies (N.FLAG_PACK_F32) that
+    the step's optimiser launch keeps current and `refresh_bf16` rebuilds after any other write of the parameters.
+    Bit-identical results either way.
+
     Non-finite guard (`nonfinite_guard`): the optimiser launch of every step checks the objective accumulator on the
     device; `first_nonfinite_step()` / `run_epoch(check_every=k)` report or stop at the first batch whose objective
     was NaN/inf, as scripts/train_st_interp.py:724-733 does, without a host sync per step."""
@@ -194,7 +199,7 @@ class TrainStep:
                  domain_penalty_weight=0.0, movement_penalty_weight=0.0, sparsity_penalty_type="none",
                  sparsity_lambda_l1=0.001, sparsity_lambda_group=0.01, sparsity_apply_to_spatial=True,
                  sparsity_apply_to_temporal=True, seed=None, world_size=None, dtype="f32", shard_optimizer=False,
-                 sync_init=True, nonfinite_guard=True, inline_prep=True):
+                 sync_init=True, nonfinite_guard=True, inline_prep=True, pack_weights=True):
         self.model = model
         if dtype not in ("f32", "bf16"):
             raise ValueError(f"unknown dtype '{dtype}'; use 'f32' or 'bf16'")
@@ -260,6 +265,10 @@ class TrainStep:
         self._shadow_buf = None
         self._shadow_regions = []
         self._shadow_tables = {}
+        self._pack_buf = None           # fragment-order fp32 copies of the same weights (_install_packed_copies)
+        self._pack_regions = []
+        self._pack_table = None
+        self._pack_params = None
         model.compute_dtype = dtype
         model._bf16_engine = None
         if dtype == "bf16":
@@ -352,6 +361,10 @@ class TrainStep:
                             and not model._has_delta and self.aux_stream is None)
         self._optim = None
         self._sumsq512 = torch.zeros(N.GRADSQ_PARTS, device=self.dev)
+        # fp32 one-call steps stream the hidden weights after the first from fragment-order copies that the step's
+        # optimiser launch keeps current (N.FLAG_PACK_F32; False or STNF_NO_PACK_WEIGHTS=1: the weights themselves)
+        if pack_weights and os.environ.get("STNF_NO_PACK_WEIGHTS", "") != "1" and self._pack_qualifies():
+            self._install_packed_copies()
         self._pipe = None          # two workspaces + side stream of the pipelined batch preparation
         self._prepared = None      # the announced batch (_Announced)
         # small batches of the one-call step: the next batch is binned inside this step's optimiser launch
@@ -391,6 +404,35 @@ class TrainStep:
         m._bf16_refresh = weakref.WeakMethod(self.refresh_bf16)
         self.refresh_bf16()
 
+    def _pack_qualifies(self):
+        """fp32 one-call steps whose hidden layers after the first run in the fused tail kernels with in / out widths
+        128 or 256 -- the widths whose weight chunks travel through the unrolled fragment ring, where the packed loads
+        were measured (profiles/tail_packed_weights.md).  The library takes the copies at every width of the tail
+        kernels; split-path steps, eval and Predictor read the weights themselves."""
+        m = self.model
+        return (self.dtype == "f32" and self._whole_step and len(m.hidden_dims) >= 2
+                and all(h in (128, 256) for h in m.hidden_dims) and m.output_dim <= 8
+                and os.environ.get("STDADK_NO_FUSED_TAIL", "") != "1")
+
+    def _install_packed_copies(self):
+        m = self.model
+        lins = m._linears()
+        by_name = {n: (o, k) for n, o, k in self.offsets}
+        names = {id(p): n for n, p in m.named_parameters()}
+        shapes = [tuple(lins[l].weight.shape) for l in range(1, len(m.hidden_dims))]
+        self._pack_buf = torch.zeros(sum(sum(N.pack_f32_sizes(h, hp)) for h, hp in shapes), device=self.dev)
+        regions, pos = [], 0
+        self._pack_params = N.MlpTensors.from_buffer_copy(self.state.params)
+        for l, (h, hp) in enumerate(shapes, start=1):
+            nf, nb = N.pack_f32_sizes(h, hp)
+            pf, pb = self._pack_buf[pos:pos + nf], self._pack_buf[pos + nf:pos + nf + nb]
+            pos += nf + nb
+            regions.append((by_name[names[id(lins[l].weight)]][0], h, hp, pf, pb))
+            self._pack_params.W_bf16[l], self._pack_params.WT_bf16[l] = pf.data_ptr(), pb.data_ptr()
+        self._pack_regions = regions
+        self._pack_table = N.make_bf16_shadow(regions)
+        self.refresh_bf16()
+
     def _shadow(self, base=0):
         """stdadk_bf16_shadow table with offsets relative to flat[base:] (None in fp32 mode or without layers
         after the first)."""
@@ -408,12 +450,15 @@ class TrainStep:
         sh = self._shadow(0)
         if sh is not None:
             N.bf16_shadow_refresh(self.flat, sh)
+        if self._pack_table is not None:              # the packed fp32 copies follow the same events
+            N.f32_pack_refresh(self.flat, self._pack_table)
+        if sh is not None or self._pack_table is not None:
             self.model._bf16_key = self.model._bf16_master_key()
 
     def _check_bf16_current(self):
         """The operand copies follow this engine's own optimiser; anything else that rewrote the master weights
         (load_state_dict, ModelEMA.apply_shadow / restore, an in-place edit under no_grad) moves the key."""
-        if self._shadow_regions and self.model._bf16_key != self.model._bf16_master_key():
+        if (self._shadow_regions or self._pack_regions) and self.model._bf16_key != self.model._bf16_master_key():
             self.refresh_bf16()
 
     def set_lr(self, lr):
@@ -445,13 +490,17 @@ class TrainStep:
                 self._optim = N.make_optim(self.flat, self.grad, self.m, self.v, self.ema, self.lr, self.lr_dev,
                                            self.betas, self.eps, self.wd, self.step_dev, self.grad_clip,
                                            self._sumsq512 if self.grad_clip > 0 else None, self.ema_decay,
-                                           shadow=self._shadow(0), nonfinite_step=self.nonfinite)
+                                           shadow=self._shadow(0) if self._pack_table is None else self._pack_table,
+                                           nonfinite_step=self.nonfinite)
+            params = st.params
+            if self._pack_params is not None:
+                params, flags = self._pack_params, flags | N.FLAG_PACK_F32
             if nxt is not None:
-                return N.train_step_next(st.basis, st.desc, st.params, self.grads_t, coords, t, X, y, idx,
+                return N.train_step_next(st.basis, st.desc, params, self.grads_t, coords, t, X, y, idx,
                                          D.grad_scale(global_rows, Q), self.loss_sum, ws, flags, self._optim, nxt[0],
                                          nxt[1], seed=self.seed, loss_desc=self._loss_desc(y.shape[1]),
                                          sparsity_desc=self._sparsity)
-            N.train_step(st.basis, st.desc, st.params, self.grads_t, coords, t, X, y,
+            N.train_step(st.basis, st.desc, params, self.grads_t, coords, t, X, y,
                          idx if not prebinned else None, B, D.grad_scale(global_rows, Q), self.loss_sum, ws, flags,
                          self._optim, seed=self.seed, loss_desc=self._loss_desc(y.shape[1]),
                          sparsity_desc=self._sparsity)
@@ -675,8 +724,8 @@ class TrainStep:
         # the kernels update the parameters through raw pointers (no autograd version bump): Predictors that
         # cache derived tensors (the delta head's output layer) watch this counter
         self.model._engine_version = getattr(self.model, "_engine_version", 0) + 1
-        if self._shadow_regions:
-            self.model._bf16_key = self.model._bf16_master_key()      # the optimiser kernel has just re-rounded them
+        if self._shadow_regions or self._pack_regions:
+            self.model._bf16_key = self.model._bf16_master_key()      # the optimiser kernel has just rewritten them
 
     def step_indexed(self, coords_all, t_all, y_all, idx, X_all=None, global_rows=None, next_idx=None):
         """One optimisation step on rows `idx` (int64 device tensor) of device-RESIDENT observation
