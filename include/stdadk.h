@@ -599,6 +599,31 @@ int stdadk_grid_score_f32(const float *y_pred, const float *z, const uint8_t *sp
                           double *split_acc, double *site_acc, double *time_acc, void *workspace,
                           size_t workspace_bytes, stdadk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Knot initialiser (added under ABI 10: new entry points only, nothing existing changes, so STDADK_ABI_VERSION stays
+ * 10): ONE EM iteration of the spherical Gaussian mixture in two dimensions behind `spatial_init_method: gmm`
+ * (stnf/models/st_interp.py:187-266 fits sklearn.mixture.GaussianMixture(covariance_type='spherical') on the host),
+ * entirely in float64.  All pointers are device pointers:
+ *   X [n][2] samples; w [k], mu [k][2], var [k] the current parameters; *_out the next ones; lower_bound [1].
+ * E-step on the parameters given (d = 2, the direct squared distance):
+ *   lp_ij = log w_j - 0.5 (d log 2pi + |x_i - mu_j|^2 / var_j) - 0.5 d log var_j,   lpn_i = logsumexp_j lp_ij,
+ *   lower_bound = (1/n) sum_i lpn_i
+ * M-step with r_ij = exp(lp_ij - lpn_i), eps = 2^-52:
+ *   nk_j = sum_i r_ij + 10 eps,  mu_out_j = sum_i r_ij x_i / nk_j,
+ *   var_out_j = sum_i r_ij |x_i - mu_out_j|^2 / (d nk_j) + reg_covar   (about the NEW mean, non-negative terms),
+ *   w_out_j = nk_j / sum_j nk_j
+ * A component no sample reaches (every r_ij == 0) gives mu_out_j = 0, var_out_j = reg_covar and a finite w_out_j.
+ * The responsibilities are never stored (each pass recomputes lp_ij; lpn lives in the workspace).  Outputs must not
+ * alias inputs, each other or the workspace (STDADK_E_ARG): the caller ping-pongs two parameter sets.
+ * 1 <= n < 2^31, 1 <= k <= 65536, reg_covar > 0.  Deterministic (no atomics, fixed orders).  Workspace:
+ * stdadk_gmm_workspace_bytes(n, k) (0 = bad sizes), 8-byte aligned.  No host read of device memory, no allocation,
+ * capturable.
+ * ------------------------------------------------------------------------------------------ */
+size_t stdadk_gmm_workspace_bytes(int64_t n, int32_t k);
+int stdadk_gmm_em_f64(const double *X, int64_t n, int32_t k, const double *w, const double *mu, const double *var,
+                      double reg_covar, double *w_out, double *mu_out, double *var_out, double *lower_bound,
+                      void *workspace, size_t workspace_bytes, stdadk_stream_t stream);
+
 /* A10 on a site x time prediction grid (the dense inference callers loop over time slices with the SAME S
  * sites in each, scripts/train_st_interp.py:1091-1107,1232-1248,1378-1409).  Layer 0's pre-activation of row
  * (ti, s) is  sum_k phi_k(s) W0^T[p+k,:]  +  sum_j psi_j(t_ti) W0^T[p+Ks+j,:]  +  b0 : a per-site row plus a per-time

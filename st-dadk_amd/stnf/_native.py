@@ -191,6 +191,10 @@ _SIGNATURES = {
     "stdadk_grid_score_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                         C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
+    "stdadk_gmm_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "stdadk_gmm_em_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                    C.c_void_p]),
     "stdadk_bin_batch_f32": (C.c_int, [C.POINTER(BasisDesc), C.POINTER(MlpDesc), C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                        C.c_size_t, C.c_int32, C.c_void_p]),
@@ -727,6 +731,39 @@ def grid_score(y_pred, z, split, metric_col, taus, lo_col, hi_col, split_acc, si
         int(hi_col), _f64_acc(split_acc, "split_acc", (4, GRID_SLOTS)), _f64_acc(site_acc, "site_acc", (4, S, 3)),
         _f64_acc(time_acc, "time_acc", (4, nT, 3)), workspace.data_ptr(), workspace.numel() * 8, _stream())
     _check(rc, "stdadk_grid_score_f32")
+
+
+def gmm_workspace_bytes(n, k):
+    nbytes = lib().stdadk_gmm_workspace_bytes(n, k)
+    if nbytes == 0:
+        raise RuntimeError(f"stdadk_gmm_workspace_bytes: bad sizes n={n}, k={k} (1 <= n < 2^31, 1 <= k <= 65536)")
+    return nbytes
+
+
+def _f64(tensor, name, shape):
+    """Address of a contiguous float64 tensor of `shape` on the current HIP device."""
+    if tensor.dtype != torch.float64 or not _on_device(tensor) or not tensor.is_contiguous() \
+            or (shape is not None and tuple(tensor.shape) != shape):
+        raise RuntimeError(f"gmm_em: {name} must be a contiguous float64 tensor{'' if shape is None else f' of shape {shape}'}"
+                           f" on the device, got {tensor.dtype} {tuple(tensor.shape)} on {tensor.device}")
+    if tensor.is_cuda and tensor.device.index != _current_device():
+        raise RuntimeError(f"gmm_em: {name} lives on {tensor.device} but the current device is cuda:"
+                           f"{torch.cuda.current_device()}; call under torch.cuda.device({tensor.device.index})")
+    return tensor.data_ptr()
+
+
+def gmm_em(X, w, mu, var, reg_covar, w_out, mu_out, var_out, lower_bound, workspace):
+    """stdadk_gmm_em_f64: one EM iteration of the spherical two-dimensional mixture in float64 -- the E-step on
+    (w (k,), mu (k, 2), var (k,)) over the samples X (n, 2), the M-step into (w_out, mu_out, var_out), the mean
+    log-likelihood of the E-step into lower_bound (1,).  Outputs must not alias inputs (ping-pong two sets)."""
+    if X.dim() != 2 or X.shape[1] != 2:
+        raise RuntimeError(f"gmm_em: X must be (n, 2), got {tuple(X.shape)}")
+    n, k = X.shape[0], w.shape[0] if w.dim() == 1 else -1
+    rc = lib().stdadk_gmm_em_f64(
+        _f64(X, "X", (n, 2)), n, k, _f64(w, "w", (k,)), _f64(mu, "mu", (k, 2)), _f64(var, "var", (k,)),
+        float(reg_covar), _f64(w_out, "w_out", (k,)), _f64(mu_out, "mu_out", (k, 2)), _f64(var_out, "var_out", (k,)),
+        _f64(lower_bound, "lower_bound", (1,)), _f64(workspace, "workspace", None), workspace.numel() * 8, _stream())
+    _check(rc, "stdadk_gmm_em_f64")
 
 
 def make_knot_train(centers_init, gradient_damping=False, damping_threshold=0.3, damping_strength=1.0,

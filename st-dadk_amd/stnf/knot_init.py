@@ -1,0 +1,128 @@
+"""Data-adaptive knot initialisation on the device: the spherical Gaussian mixture behind `spatial_init_method: gmm`
+(reference stnf/models/st_interp.py:187-266), fitted by stdadk_gmm_em_f64 -- one float64 EM iteration per call -- where
+the host path calls sklearn.mixture.GaussianMixture(...).fit three times.
+
+What stays on the host: the draw of the subsample (the same global-numpy-RNG call as the host path), the k-means++
+seeding (sklearn's own public sklearn.cluster.kmeans_plusplus on one RandomState(42), three calls in sequence: exactly
+what GaussianMixture(random_state=42, n_init=3, init_params='k-means++') does), the first M-step from the one-hot
+responsibilities of the seeds (k rows), and the convergence test: one 8-byte read of the lower bound per iteration.
+"""
+import collections
+import math
+
+import numpy as np
+import torch
+
+from . import _native as N
+
+EPS = float(np.finfo(np.float64).eps)
+MAX_SAMPLES = 10000            # the reference's max_samples_for_gmm
+N_INIT = 3
+RANDOM_STATE = 42
+
+GmmFit = collections.namedtuple("GmmFit", "weights means variances lower_bound n_iter best lower_bounds")
+
+
+def seed_parameters(points, idx, reg_covar):
+    """The M-step from one-hot responsibilities on the seed rows, float64 numpy: nk = 1 + 10 eps, mu = x / nk,
+    var = |x - mu|^2 / (d nk) + reg_covar, w = nk / n.  points (n, 2) float64, idx (k,) rows."""
+    x = np.asarray(points, np.float64)[np.asarray(idx, np.int64)]
+    nk = 1.0 + 10.0 * EPS
+    mu = x / nk
+    var = ((x - mu) ** 2).sum(axis=1) / (2.0 * nk) + reg_covar
+    w = np.full(len(x), nk / len(points))
+    return w, mu, var
+
+
+def fit_spherical_gmm(points64, n_components, seed_indices, max_iter=100, tol=1e-3, reg_covar=1e-6):
+    """EM for a spherical mixture of `n_components` Gaussians on points64 ((n, 2) float64 on a HIP device), one restart
+    per index array of `seed_indices` (the k rows whose one-hot responsibilities start it), as GaussianMixture.fit
+    with warm_start=False: from lb = -inf, each iteration is one stdadk_gmm_em_f64 call (E on the current parameters,
+    then M) and stops when |lb - prev| < tol; the restart with the largest lower bound is kept, the first on a tie.
+    Returns GmmFit(weights (k,), means (k, 2), variances (k,) float64 device tensors, lower_bound, per-restart n_iter,
+    the chosen restart, per-restart lower bounds)."""
+    if points64.dtype != torch.float64 or points64.dim() != 2 or points64.shape[1] != 2:
+        raise RuntimeError(f"fit_spherical_gmm: points must be (n, 2) float64, got {points64.dtype} {tuple(points64.shape)}")
+    if not points64.is_cuda:
+        raise RuntimeError(f"fit_spherical_gmm: points must live on a HIP device (cuda:N), got {points64.device}; the "
+                           f"host path is sklearn's (init_device=None)")
+    if len(seed_indices) == 0:
+        raise ValueError("fit_spherical_gmm: no restart given")
+    points64 = points64.contiguous()
+    dev, n, k = points64.device, points64.shape[0], int(n_components)
+    host = points64.cpu().numpy()
+    ws = torch.empty(N.gmm_workspace_bytes(n, k) // 8, device=dev, dtype=torch.float64)
+    lb_dev = torch.empty(1, device=dev, dtype=torch.float64)
+    new = lambda: (torch.empty(k, device=dev, dtype=torch.float64), torch.empty(k, 2, device=dev, dtype=torch.float64),
+                   torch.empty(k, device=dev, dtype=torch.float64))                        # noqa: E731
+    best, best_lb, best_params, n_iters, lbs = -1, -math.inf, None, [], []
+    with torch.cuda.device(dev):
+        for r, idx in enumerate(seed_indices):
+            idx = np.asarray(idx, np.int64)
+            if idx.shape != (k,):
+                raise ValueError(f"fit_spherical_gmm: restart {r} has {idx.shape} seeds, {k} components expected")
+            cur = tuple(torch.from_numpy(a).to(dev) for a in seed_parameters(host, idx, reg_covar))
+            nxt = new()
+            lb, it = -math.inf, 0
+            for it in range(1, max_iter + 1):
+                prev = lb
+                N.gmm_em(points64, cur[0], cur[1], cur[2], reg_covar, nxt[0], nxt[1], nxt[2], lb_dev, ws)
+                cur, nxt = nxt, cur
+                lb = float(lb_dev.item())
+                if abs(lb - prev) < tol:
+                    break
+            n_iters.append(it)
+            lbs.append(lb)
+            if lb > best_lb or best < 0:
+                best, best_lb, best_params = r, lb, cur
+    return GmmFit(best_params[0], best_params[1], best_params[2], best_lb, n_iters, best, lbs)
+
+
+def grid_bandwidth(k):
+    """Bandwidth of the uniform grid with k knots: 2.5 x spacing (the reference's clipping yardstick)."""
+    side = int(math.sqrt(k))
+    return 2.5 * (1.0 / (side - 1) if side > 1 else 1.0)
+
+
+def knots_from_fit(means64, variances64, k):
+    """(centres (k, 2), bandwidths (k,)) float32 from a level's float64 fit: bandwidth = 4.23 * 2.5 * sigma, floored at a
+    quarter of the same-size grid's bandwidth (numpy, as the host path)."""
+    bw = np.clip(4.23 * 2.5 * np.sqrt(np.asarray(variances64, np.float64)), 0.25 * grid_bandwidth(k), float('inf'))
+    return torch.from_numpy(np.asarray(means64, np.float64)).float(), torch.from_numpy(bw).float()
+
+
+def subsample(train_coords):
+    """At most MAX_SAMPLES rows, drawn with the global numpy RNG exactly as the host path draws them, as float64."""
+    pts = np.asarray(train_coords)
+    if len(pts) > MAX_SAMPLES:
+        pts = pts[np.random.choice(len(pts), MAX_SAMPLES, replace=False)]
+    return pts.astype(np.float64)
+
+
+def kmeanspp_seeds(points, n_centers):
+    """Per level the N_INIT k-means++ index arrays of GaussianMixture(random_state=42, n_init=3,
+    init_params='k-means++'): every level starts a fresh RandomState(42), its restarts draw from it in sequence."""
+    from sklearn.cluster import kmeans_plusplus
+    out = []
+    for k in n_centers:
+        rs = np.random.RandomState(RANDOM_STATE)
+        out.append([kmeans_plusplus(points, k, random_state=rs)[1] for _ in range(N_INIT)])
+    return out
+
+
+def gmm_knots(train_coords, n_centers, device):
+    """The reference's _init_gmm with the mixture fitted on `device`: (centres (sum k, 2), bandwidths (sum k,)) float32
+    host tensors, levels concatenated in list order."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"gmm_knots: a HIP device (cuda:N) is required, got {device}; init_device=None is the host path")
+    pts = subsample(train_coords)
+    seeds = kmeanspp_seeds(pts, n_centers)
+    pts_dev = torch.from_numpy(pts).to(device)
+    cs, bs = [], []
+    for k, level_seeds in zip(n_centers, seeds):
+        fit = fit_spherical_gmm(pts_dev, k, level_seeds, max_iter=100, tol=1e-3, reg_covar=1e-6)
+        c, b = knots_from_fit(fit.means.cpu().numpy(), fit.variances.cpu().numpy(), k)
+        cs.append(c)
+        bs.append(b)
+    return torch.cat(cs, dim=0), torch.cat(bs, dim=0)

@@ -85,7 +85,7 @@ class SpatialBasisEmbedding(nn.Module):
     def __init__(self, n_centers: list = [25, 81, 121], learnable: bool = False,
                  init_method: str = 'uniform', train_coords: np.ndarray = None,
                  basis_function: str = 'wendland', gradient_damping: bool = False,
-                 damping_threshold: float = 0.3, damping_strength: float = 1.0):
+                 damping_threshold: float = 0.3, damping_strength: float = 1.0, init_device=None):
         super().__init__()
         self.n_centers = n_centers
         self.learnable = learnable
@@ -101,7 +101,12 @@ class SpatialBasisEmbedding(nn.Module):
             centers, bandwidths = self._init_uniform()
         elif init_method == 'gmm':
             assert train_coords is not None, "train_coords required for GMM initialization"
-            centers, bandwidths = self._init_gmm(train_coords)
+            # init_device: None = the host sklearn fit; a HIP device = the same mixture fitted there (stnf.knot_init)
+            if init_device is None:
+                centers, bandwidths = self._init_gmm(train_coords)
+            else:
+                from ..knot_init import gmm_knots
+                centers, bandwidths = gmm_knots(train_coords, n_centers, init_device)
         elif init_method == 'random_site':
             assert train_coords is not None, "train_coords required for random_site initialization"
             centers, bandwidths = self._init_random_site(train_coords)
@@ -344,7 +349,7 @@ class STInterpMLP(nn.Module):
                  spatial_init_method: str = 'uniform', spatial_basis_function: str = 'wendland',
                  train_coords: np.ndarray = None, gradient_damping: bool = False,
                  damping_threshold: float = 0.3, damping_strength: float = 1.0,
-                 output_dim: int = 1, use_delta_reparameterization: bool = False):
+                 output_dim: int = 1, use_delta_reparameterization: bool = False, spatial_init_device=None):
         super().__init__()
         self.p = p
         self.k_spatial_centers = k_spatial_centers
@@ -356,7 +361,8 @@ class STInterpMLP(nn.Module):
             n_centers=k_spatial_centers, learnable=spatial_learnable,
             init_method=spatial_init_method, train_coords=train_coords,
             basis_function=spatial_basis_function, gradient_damping=gradient_damping,
-            damping_threshold=damping_threshold, damping_strength=damping_strength)
+            damping_threshold=damping_threshold, damping_strength=damping_strength,
+            init_device=spatial_init_device)
         self.temporal_basis = TemporalBasisEmbedding(n_centers=k_temporal_centers)
         self.k_spatial = self.spatial_basis.k
         self.k_temporal = self.temporal_basis.k_time
@@ -702,4 +708,5 @@ def create_model(config: dict, train_coords: np.ndarray = None) -> STInterpMLP:
         damping_threshold=config.get('damping_threshold', 0.3),
         damping_strength=config.get('damping_strength', 1.0),
         output_dim=output_dim,
-        use_delta_reparameterization=config.get('use_delta_reparameterization', False))
+        use_delta_reparameterization=config.get('use_delta_reparameterization', False),
+        spatial_init_device=config.get('spatial_init_device'))
