@@ -633,7 +633,11 @@ int stdadk_gmm_em_f64(const double *X, int64_t n, int32_t k, const double *w, co
  *   stdadk_forward_parts_f32     y_pred[T*S][Q], rows time-major: z0 = sp[row % S] + tp[row / S] + b0, then
  *                                LayerNorm/ReLU of layer 0, the remaining layers and the output layer (eval mode)
  * Same sums as stdadk_forward_f32 in another order of addition (agreement to fp32 rounding, tested).
- * All three need the first weight stored (in,out) (STDADK_FLAG_W0_T). */
+ * All three need the first weight stored (in,out) (STDADK_FLAG_W0_T).
+ * stdadk_forward_parts_supported (added under ABI 10: a new entry point only): 1 when stdadk_forward_parts_f32 runs
+ * this MLP (at least one hidden layer, every hidden width a multiple of 16 up to 256, out_dim <= 8), else 0; a
+ * caller that gets 0 expands the rows and calls stdadk_forward_f32. */
+int32_t stdadk_forward_parts_supported(const stdadk_mlp_desc *mlp);
 int stdadk_spatial_partial_f32(const stdadk_basis_desc *basis, const stdadk_mlp_desc *mlp,
                                const stdadk_mlp_tensors *params, const float *coords, int64_t S, float *out,
                                void *workspace, size_t workspace_bytes, int32_t flags, stdadk_stream_t stream);

@@ -1548,6 +1548,14 @@ extern "C" int stdadk_temporal_partial_f32(const stdadk_basis_desc *b, const std
   return 0;
 }
 
+// the shapes stdadk_forward_parts_f32 runs: the fused tail from layer 0 on (the query and the door share this)
+static bool forward_parts_shape_ok(const stdadk_mlp_desc *d) { return d->n_hidden >= 1 && tail_supported(d, 1); }
+
+extern "C" int32_t stdadk_forward_parts_supported(const stdadk_mlp_desc *d) {
+  if (check_desc(d) != 0) return 0;
+  return forward_parts_shape_ok(d) ? 1 : 0;
+}
+
 extern "C" int stdadk_forward_parts_f32(const stdadk_mlp_desc *d, const stdadk_mlp_tensors *P, const float *sp,
                                         int64_t S, const float *tp, int64_t T, float *y_pred,
                                         stdadk_stream_t stream) {
@@ -1556,7 +1564,7 @@ extern "C" int stdadk_forward_parts_f32(const stdadk_mlp_desc *d, const stdadk_m
   if (rc) return rc;
   const int L = d->n_hidden;
   STDADK_REQUIRE(P && sp && tp && y_pred && S * T < (1ll << 31), STDADK_E_ARG, "forward_parts: bad argument");
-  STDADK_REQUIRE(L >= 1 && tail_supported(d, 1) && P->W[L] && P->b[L], STDADK_E_ARG,
+  STDADK_REQUIRE(forward_parts_shape_ok(d) && P->W[L] && P->b[L], STDADK_E_ARG,
                  "forward_parts: hidden widths must be multiples of 16 up to %d, out_dim <= %d", TAIL_MAX_W, TAIL_MAXQ);
   TailFwdArgs a;
   a.n_layers = L - 1;

@@ -136,6 +136,7 @@ _SIGNATURES = {
                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
     "stdadk_forward_parts_f32": (C.c_int, [C.POINTER(MlpDesc), C.POINTER(MlpTensors), C.c_void_p, C.c_int64,
                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "stdadk_forward_parts_supported": (C.c_int32, [C.POINTER(MlpDesc)]),
     "stdadk_train_step_f32": (C.c_int, [C.POINTER(BasisDesc), C.POINTER(MlpDesc), C.POINTER(MlpTensors),
                                         C.POINTER(MlpTensors), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_int64, C.c_float, C.POINTER(LossDesc),
@@ -579,6 +580,11 @@ def temporal_partial(basis, desc, params, t_values, out, flags):
     rc = lib().stdadk_temporal_partial_f32(C.byref(basis), C.byref(desc), C.byref(params), _dev(t_values, "t_values"),
                                            T, _dev(out, "out"), flags, _stream())
     _check(rc, "stdadk_temporal_partial_f32")
+
+
+def forward_parts_supported(desc):
+    """stdadk_forward_parts_supported: whether forward_parts runs this MLP (the fused tail's widths and head)."""
+    return bool(lib().stdadk_forward_parts_supported(C.byref(desc)))
 
 
 def forward_parts(desc, params, sp, tp, y_pred):

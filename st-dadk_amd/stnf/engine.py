@@ -1037,13 +1037,15 @@ class Predictor:
         filled with the chunk's predictions, (n*S, Q) time-major.  `alloc(name, shape)` hands out the scratch tensors
         (fresh ones for predict_grid, the predictor's reused ones for score_grid).  Layer 0's pre-activation is a
         per-site row plus a per-time row, so the basis evaluation and the gather of first-layer weights happen once per
-        site; that needs the first weight stored (in,out) and p = 0, otherwise every chunk's rows are expanded and
-        go through predict()."""
+        site; that needs the first weight stored (in,out), p = 0 and an MLP that stdadk_forward_parts_f32 runs (the
+        library answers that: the fused tail's widths and head), otherwise every chunk's rows are expanded and go
+        through predict()."""
         st = self.state
         S, T = coords.shape[0], t_values.numel()
         m = self.model
         per = self._slices_per_call(S, max_rows)
-        parts = m.p == 0 and bool(st.flags & N.FLAG_W0_T) and len(m.hidden_dims) >= 1 and S > 0 and T > 0
+        parts = m.p == 0 and bool(st.flags & N.FLAG_W0_T) and len(m.hidden_dims) >= 1 and S > 0 and T > 0 \
+            and N.forward_parts_supported(st.desc)
         window = parts and not m.spatial_basis.learnable and N.step_uses_window(st.basis, st.desc, st.flags)
         if not parts:
             for t0 in range(0, T, per):
@@ -1094,8 +1096,15 @@ class Predictor:
         """The same S sites at every one of T times (what the reference's dense-grid callers loop over, one
         model call per time slice): coords (S,2), t_values (T,) -> (T, S, Q).  Layer 0's pre-activation is a
         per-site row plus a per-time row, so the basis evaluation and the gather of first-layer weights
-        happen once per site; the rest of the network runs on the T*S rows.  Needs the window path (fixed
-        grid knots, compact-support basis) and p = 0; otherwise falls back to predict() on the expanded rows."""
+        happen once per site; the rest of the network runs on the T*S rows.  Three routes (p = 0 on all):
+          window         fixed knots on the window path: stdadk_spatial_partial_f32 per `chunk` sites
+          materialising  any other model whose first weight is stored (in,out) (learnable knots, Gaussian basis,
+                         small tables, engine-owned storage): the sites' phi, then one GEMM with the spatial rows
+                         of W0^T
+          expanded       first weight stored (out,in), or an MLP stdadk_forward_parts_f32 refuses (a hidden width
+                         that is no multiple of 16 or above 256, more than 8 outputs): predict() on the T*S rows
+        The first two finish with stdadk_temporal_partial_f32 and one stdadk_forward_parts_f32 per chunk of time
+        slices (at most `max_rows` rows)."""
         self._refresh()
         S, T = coords.shape[0], t_values.numel()
         coords = coords.contiguous().float()
