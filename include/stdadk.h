@@ -527,6 +527,53 @@ int stdadk_train_step_next_f32(const stdadk_basis_desc *basis, const stdadk_mlp_
                                const int64_t *next_idx, int64_t next_B, int32_t next_y_cols, void *next_workspace,
                                size_t next_workspace_bytes, int32_t *next_binned, stdadk_stream_t stream);
 
+/* The one-call step with TWO parameter groups: learnable knots (DA-STDK).  Added under ABI 10 as a new entry point
+ * only: no struct, signature or default changes, so STDADK_ABI_VERSION stays 10.
+ * = stdadk_train_fwd_bwd(_indexed)_f32 + stdadk_knot_backward_f32 + stdadk_sumsq2_f32 + stdadk_adamw_ema2_f32 of a
+ * learnable-knot step, as one call.  The arguments of stdadk_train_step_next_f32, with idx optional (NULL: rows
+ * 0..B-1 of the given arrays) and the next batch optional (next_idx, next_B, next_workspace all NULL / 0: none;
+ * next_binned may then be NULL), plus
+ *   kt                     the knot penalties and the damping hook; NULL = the plain data gradient, as in
+ *                          stdadk_knot_backward_f32, whose checks of `kt` apply unchanged
+ *   d_centers, d_log_bw    [Ks,2] / [Ks], overwritten.  Both must lie inside [knots->g, knots->g + knots->n);
+ *                          elements of that range covered by neither are padding and the caller keeps them zero
+ *   knots                  the knot group: p / g / m / v / ema / n, lr / lr_dev and max_norm.  sumsq_parts is a caller
+ *                          buffer of STDADK_SUMSQ_PARTS floats (every entry is written), required when max_norm > 0
+ *                          and written through although the field is const; n_parts is ignored on input; shadow must be
+ *                          NULL
+ * `opt` describes the MLP group exactly as for stdadk_train_step_f32 -- [opt->g, opt->g + opt->n) contains every
+ * tensor of `grads`, gaps zero, and none of the knot gradients -- and carries what both groups share: betas, eps,
+ * weight decay, step_dev, ema_decay and the guard.  The MLP group keeps the guard and, under STDADK_FLAG_BF16,
+ * opt->shadow as the table of its bf16 copies.
+ * The door needs STDADK_FLAG_LOG_BW, Ks > 0 and at least one hidden layer, and runs on both routes (window,
+ * materialising) with every basis and loss that stdadk_train_fwd_bwd_f32 + stdadk_knot_backward_f32 accept.  It refuses
+ * STDADK_FLAG_PACK_F32 (STDADK_E_ARG: packed copies are not kept on this path), d_centers / d_log_bw outside the knot
+ * group's range, a shadow on the knot group and max_norm > 0 without partials, each with STDADK_E_ARG.  Everything,
+ * the next batch included, is validated and planned before the first launch is enqueued: a refused call leaves
+ * parameters, moments, EMA, step counter and loss sum untouched.
+ * One finishing launch (step_finish_kernel) closes both gradients: its first workgroups run the step's fixed-order
+ * sums and leave the squared-norm partials of what they write, where those sums are still pending behind the weight
+ * gradients (window route below 49 152 rows); the workgroups behind them finish the knots -- per knot, fixed order,
+ * penalty value x penalty_loss_scale into loss_sum -- and each leaves ONE partial, the squares of the d_centers /
+ * d_log_bw entries it wrote: at most STDADK_SUMSQ_PARTS knot workgroups stride over the 64-knot tiles, so the knot
+ * group's norm is a fixed-order sum of at most 256 partials whatever Ks is.  Where the step's launches do not
+ * deliver the MLP group's partials (a sparsity penalty, products outside the grouped launch) its norm is a
+ * stdadk_sumsq_f32 over opt->g.  opt->step_dev advances exactly once per call, after the backward and before the
+ * optimiser launch (the finishing launch carries the advance).  Then ONE two-group AdamW launch, MLP group first.
+ * Next batch: binned by the merged weight-gradient launch when that launch can carry it (window route, the
+ * workspaces apart, at most 64 x 64 cells) and *next_binned = 1; in every other case *next_binned = 0 and nothing was
+ * prepared (bin it with stdadk_bin_batch_f32).  Under STDADK_DRY_RUN=1 the door validates and plans like every other. */
+int stdadk_train_step_knots_f32(const stdadk_basis_desc *basis, const stdadk_mlp_desc *mlp,
+                                const stdadk_mlp_tensors *params, const stdadk_mlp_tensors *grads,
+                                const float *coords_all, const float *t_all, const float *X_all, const float *y_all,
+                                const int64_t *idx, int64_t B, float grad_scale, const stdadk_loss_desc *loss,
+                                const stdadk_sparsity_desc *sparsity, float *loss_sum, void *workspace,
+                                size_t workspace_bytes, uint64_t drop_seed, int32_t flags, const stdadk_optim_desc *opt,
+                                const int64_t *next_idx, int64_t next_B, int32_t next_y_cols, void *next_workspace,
+                                size_t next_workspace_bytes, int32_t *next_binned, const stdadk_knot_train *kt,
+                                float *d_centers, float *d_log_bw, const stdadk_adam_group *knots,
+                                stdadk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Validation (ABI 9): evaluate_model and the validation half of train_model's epoch
  * (scripts/train_st_interp.py:737-806,884-961) on rows idx[b] (int64, device) of the RESIDENT arrays, forward only.

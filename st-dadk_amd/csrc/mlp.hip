@@ -15,6 +15,7 @@
 #include "optim.h"
 #include "bin_body.h"
 #include "knots.h"
+#include "step_finish.h"
 #include "basis.h"
 #include "loss.h"
 
@@ -562,6 +563,13 @@ struct Ctx {
   // fused-tail backward: the temporal / covariate rows of dW0^T on the window path
   int n_extra = 0;
   struct { const float *A; int64_t lda; int M; float *C; } extra[2] = {};
+  // one-call learnable step (stdadk_train_step_knots_f32): the finishing launch (step_finish.hip) closes the knot
+  // group's gradient, leaves its clip-norm partials and advances the step counter; where the step's reductions
+  // launch is still pending behind the merged dW launch it takes that launch's place and carries its jobs
+  bool knot_ride = false, knot_done = false;
+  const stdadk_knot_train *knot_kt = nullptr;
+  float *knot_dc = nullptr, *knot_dlb = nullptr, *knot_sq = nullptr;
+  int *knot_inc = nullptr;
 };
 
 // One description of a training step call: what the public doors take positionally, by name
@@ -585,7 +593,15 @@ struct StepCall {
 // StepRide: what the one-call step lets ride along with its launches -- squared-norm partials of the gradient with the step
 // counter their launch advances, the next batch for the merged dW launch to bin; StepOut: where the partials went (NULL:
 // no launch left them) and whether that batch is binned
-struct StepRide { float *gradsq_parts = nullptr; int32_t *step_inc = nullptr; const BinSmallArgs *bin_next = nullptr; };
+struct StepRide {
+  float *gradsq_parts = nullptr; int32_t *step_inc = nullptr; const BinSmallArgs *bin_next = nullptr;
+  // two parameter groups (stdadk_train_step_knots_f32): the knot finish rides in the step's finishing launch, which
+  // leaves the knot group's partials in knot_sq (NULL: unclipped) and advances finish_inc (step_inc stays NULL then)
+  bool knots = false;
+  const stdadk_knot_train *kt = nullptr;
+  float *d_centers = nullptr, *d_log_bw = nullptr, *knot_sq = nullptr;
+  int32_t *finish_inc = nullptr;
+};
 struct StepOut { const float *sq_parts = nullptr; int sq_n = 0; bool binned_next = false; };
 struct NextBatch {   // the batch a one-call step announces (stdadk_train_step_next_f32)
   const int64_t *idx = nullptr;
@@ -1363,6 +1379,70 @@ static int step_forward(Ctx &c, const stdadk_basis_desc *b, bool window, const f
   return run_forward(c, 0, ws + c.pl.feats, c.pl.ldf, d->in_dim, y_pred);
 }
 
+// the knot penalties' checks, shared by the doors that take them
+static int check_knot_train(const char *what, const stdadk_knot_train *kt) {
+  if (!kt) return 0;
+  STDADK_REQUIRE(kt->centers_init || (!kt->gradient_damping && !(kt->movement_weight > 0.f)), STDADK_E_ARG,
+                 "%s: centers_init is NULL but damping / movement penalty is on", what);
+  STDADK_REQUIRE(kt->domain_weight >= 0.f && kt->movement_weight >= 0.f, STDADK_E_ARG, "%s: negative penalty weight", what);
+  return 0;
+}
+
+// the knot finish of the batch whose raw per-knot sums sit in the workspace of `c` (kt NULL: the plain data gradient)
+static KnotFinishArgs knot_finish_args(const Ctx &c, const stdadk_basis_desc *b, const stdadk_knot_train *kt,
+                                       float *d_centers, float *d_log_bw, float *loss_sum) {
+  KnotFinishArgs fa;
+  fa.part = c.ws + c.pl.kpart; fa.slabs = c.pl.kslabs; fa.Ks = (int)b->Ks; fa.centers = b->s_centers;
+  fa.centers_init = kt ? kt->centers_init : nullptr;
+  fa.damping = kt ? kt->gradient_damping : 0;
+  fa.thr = kt ? kt->damping_threshold : 0.f; fa.strength = kt ? kt->damping_strength : 0.f;
+  fa.dom_w = kt ? kt->domain_weight : 0.f; fa.mov_w = kt ? kt->movement_weight : 0.f;
+  fa.pen_grad_scale = kt ? kt->penalty_grad_scale : 0.f; fa.pen_loss_scale = kt ? kt->penalty_loss_scale : 0.f;
+  fa.d_centers = d_centers; fa.d_log_bw = d_log_bw; fa.loss_sum = loss_sum;
+  return fa;
+}
+
+// materialising path: the raw per-slab knot sums from dZ of layer 0, which run_backward left in the workspace
+static int knot_dense_sums(const Ctx &c, const stdadk_basis_desc *b, const stdadk_mlp_tensors *P, const float *coords) {
+  const stdadk_mlp_desc *d = c.d;
+  float *ws = c.ws;
+  const int H = d->hidden[0];
+  // where run_backward left dZ of layer 0 (fused tail: its per-layer buffer; generic: the shared one)
+  const float *dz0 = (tail_enabled() && tail_supported(d, 1)) ? ws + c.pl.dZl[0] : ws + c.pl.dZ;
+  // dFeat = dZ0 . W0 over ALL feature columns, into the (now free) feature buffer
+  float *dfeat = ws + c.pl.feats;
+  int rc;
+  if (c.w0t)
+    rc = gemm_run(dz0, H, false, P->W[0], H, false, (int)c.B, d->in_dim, H, nullptr, dfeat, c.pl.ldf,
+                  ws + c.pl.slab, false, nullptr, c.st);
+  else
+    rc = gemm_run(dz0, H, false, P->W[0], d->in_dim, true, (int)c.B, d->in_dim, H, nullptr, dfeat, c.pl.ldf,
+                  ws + c.pl.slab, false, nullptr, c.st);
+  if (rc) return rc;
+  KnotGradArgs ka;
+  ka.coords = coords; ka.B = (int)c.B; ka.dFeat = dfeat; ka.ld = c.pl.ldf; ka.p = b->p;
+  ka.centers = b->s_centers; ka.bw = ws + c.pl.bw_exp; ka.Ks = (int)b->Ks; ka.basis = b->basis;
+  ka.part = ws + c.pl.kpart; ka.slabs = c.pl.kslabs;
+  return launch_knot_grad(ka, c.st);
+}
+
+// The reductions launch that is pending behind the merged dW launch of a window-path step -- or, in a one-call
+// learnable step, the finishing launch that takes its place and carries its jobs (the per-knot sums are final once
+// the dW launch is).  Mode 0's 256 region workgroups stay in a launch of their own there.
+static int launch_step_reductions(Ctx &c, const stdadk_basis_desc *b, ReduceGroup &rg) {
+  if (!c.knot_ride) return launch_reduce_jobs(rg, c.st);
+  if (rg.sq_region_parts) {
+    ReduceGroup region;
+    region.sq_region_parts = rg.sq_region_parts; region.sq_src = rg.sq_src; region.sq_n = rg.sq_n;
+    rg.sq_region_parts = nullptr; rg.sq_src = nullptr; rg.sq_n = 0;
+    const int rc = launch_reduce_jobs(region, c.st);
+    if (rc) return rc;
+  }
+  const KnotFinishArgs fa = knot_finish_args(c, b, c.knot_kt, c.knot_dc, c.knot_dlb, c.mse_loss);
+  c.knot_done = true;
+  return launch_step_finish(rg, fa, c.knot_sq, c.knot_inc, c.st);
+}
+
 // backward of the batch whose training forward left its state in the workspace; dY in caller order
 // (`dY_sorted`: window path only — dY is already the plan's dY buffer in sorted order)
 static int step_backward(Ctx &c, const stdadk_basis_desc *b, bool window, const float *dY, bool dY_sorted) {
@@ -1435,7 +1515,7 @@ static int step_backward(Ctx &c, const stdadk_basis_desc *b, bool window, const 
       c.rg_pend.sq_parts = fin.slots + n_knot;
       c.rg_pend.step_inc = c.step_inc;
       c.gradsq_done = true; c.gradsq_out = fin.slots; c.gradsq_n = n_knot + nrb;
-      return launch_reduce_jobs(c.rg_pend, c.st);
+      return launch_step_reductions(c, b, c.rg_pend);
     }
     rc = window_dw0(c, c.st, &c.gg_pend);
     if (rc) return rc;
@@ -1449,7 +1529,7 @@ static int step_backward(Ctx &c, const stdadk_basis_desc *b, bool window, const 
       c.rg_pend.step_inc = c.step_inc;
       c.gradsq_done = true; c.gradsq_out = c.gradsq; c.gradsq_n = 256 + nrb;
     }
-    return launch_reduce_jobs(c.rg_pend, c.st);
+    return launch_step_reductions(c, b, c.rg_pend);
   }
   for (int e = 0; e < c.n_extra; ++e) {     // not consumed by a grouped launch
     rc = gemm_run(c.extra[e].A, c.extra[e].lda, true, c.dz0, H, true, c.extra[e].M, H, (int)c.B, nullptr,
@@ -1617,43 +1697,15 @@ extern "C" int stdadk_knot_backward_f32(const stdadk_basis_desc *b, const stdadk
   STDADK_REQUIRE(P && P->W[0] && (coords || window) && d_centers && d_log_bw, STDADK_E_ARG,
                  "knot_backward: NULL pointer");
   STDADK_REQUIRE(b->Ks > 0 && d->n_hidden >= 1, STDADK_E_ARG, "knot_backward: no spatial knots / no hidden layer");
-  if (kt) {
-    STDADK_REQUIRE(kt->centers_init || (!kt->gradient_damping && !(kt->movement_weight > 0.f)), STDADK_E_ARG,
-                   "knot_backward: centers_init is NULL but damping / movement penalty is on");
-    STDADK_REQUIRE(kt->domain_weight >= 0.f && kt->movement_weight >= 0.f, STDADK_E_ARG,
-                   "knot_backward: negative penalty weight");
-  }
-  hipStream_t st = c.st;
-  float *ws = c.ws;
-  const int H = d->hidden[0];
-  KnotFinishArgs fa;
-  fa.part = ws + c.pl.kpart; fa.slabs = c.pl.kslabs; fa.Ks = (int)b->Ks; fa.centers = b->s_centers;
-  fa.centers_init = kt ? kt->centers_init : nullptr;
-  fa.damping = kt ? kt->gradient_damping : 0;
-  fa.thr = kt ? kt->damping_threshold : 0.f; fa.strength = kt ? kt->damping_strength : 0.f;
-  fa.dom_w = kt ? kt->domain_weight : 0.f; fa.mov_w = kt ? kt->movement_weight : 0.f;
-  fa.pen_grad_scale = kt ? kt->penalty_grad_scale : 0.f; fa.pen_loss_scale = kt ? kt->penalty_loss_scale : 0.f;
-  fa.d_centers = d_centers; fa.d_log_bw = d_log_bw; fa.loss_sum = loss_sum;
+  rc = check_knot_train("knot_backward", kt);
+  if (rc) return rc;
+  const KnotFinishArgs fa = knot_finish_args(c, b, kt, d_centers, d_log_bw, loss_sum);
   // window path: the per-knot gather of the backward already left the raw sums in the workspace
-  if (window) return launch_knot_finish(fa, st);
-  // where run_backward left dZ of layer 0 (fused tail: its per-layer buffer; generic: the shared one)
-  const float *dz0 = (tail_enabled() && tail_supported(d, 1)) ? ws + c.pl.dZl[0] : ws + c.pl.dZ;
-  // dFeat = dZ0 . W0 over ALL feature columns, into the (now free) feature buffer
-  float *dfeat = ws + c.pl.feats;
-  if (c.w0t)
-    rc = gemm_run(dz0, H, false, P->W[0], H, false, (int)B, d->in_dim, H, nullptr, dfeat, c.pl.ldf,
-                  ws + c.pl.slab, false, nullptr, st);
-  else
-    rc = gemm_run(dz0, H, false, P->W[0], d->in_dim, true, (int)B, d->in_dim, H, nullptr, dfeat, c.pl.ldf,
-                  ws + c.pl.slab, false, nullptr, st);
-  if (rc) return rc;
-  KnotGradArgs ka;
-  ka.coords = coords; ka.B = (int)B; ka.dFeat = dfeat; ka.ld = c.pl.ldf; ka.p = b->p;
-  ka.centers = b->s_centers; ka.bw = ws + c.pl.bw_exp; ka.Ks = (int)b->Ks; ka.basis = b->basis;
-  ka.part = ws + c.pl.kpart; ka.slabs = c.pl.kslabs;
-  rc = launch_knot_grad(ka, st);
-  if (rc) return rc;
-  return launch_knot_finish(fa, st);
+  if (!window) {
+    rc = knot_dense_sums(c, b, P, coords);
+    if (rc) return rc;
+  }
+  return launch_knot_finish(fa, c.st);
 }
 
 // where a step's predictions land: the plan's buffer (window path: sorted order, y_pred gets the un-permuted copy)
@@ -1674,6 +1726,10 @@ static int train_fwd_bwd_impl(const StepCall &s, const StepRide *ride, StepOut *
   const stdadk_basis_desc *b = s.b;
   Ctx c;
   if (ride) { c.gradsq = ride->gradsq_parts; c.step_inc = ride->step_inc; c.bin_next = ride->bin_next; }
+  if (ride && ride->knots) {
+    c.knot_ride = true; c.knot_kt = ride->kt; c.knot_dc = ride->d_centers; c.knot_dlb = ride->d_log_bw;
+    c.knot_sq = ride->knot_sq; c.knot_inc = ride->finish_inc;
+  }
   bool window;
   int rc = open_step(c, b, s.d, s.B, s.workspace, s.workspace_bytes, s.flags, &window, s.P, s.G, s.stream, true,
                      s.drop_seed, s.step_dev);
@@ -1701,18 +1757,69 @@ static int train_fwd_bwd_impl(const StepCall &s, const StepRide *ride, StepOut *
   if (rc) return rc;
   STDADK_REQUIRE(!window || (!c.pend_valid && !c.l1_pend_valid), STDADK_E_ARG, "train_fwd_bwd: a parked launch was never issued");
   STDADK_REQUIRE(window || !c.pend_valid, STDADK_E_ARG, "train_fwd_bwd: the parked tail launch was never issued");
+  if (c.knot_ride && !c.knot_done) {
+    // no reductions launch was pending behind the weight gradients (finishing mode 2, the separate launches, the
+    // materialising route behind its products): the finishing launch runs with zero reduce workgroups
+    if (!window) {
+      rc = knot_dense_sums(c, b, s.P, s.coords);
+      if (rc) return rc;
+    }
+    ReduceGroup none;
+    rc = launch_step_finish(none, knot_finish_args(c, b, c.knot_kt, c.knot_dc, c.knot_dlb, c.mse_loss), c.knot_sq,
+                            c.knot_inc, c.st);
+    if (rc) return rc;
+  }
   if (out) *out = {c.gradsq_done ? c.gradsq_out : nullptr, c.gradsq_done ? c.gradsq_n : 0, c.bin_next_done};
   return 0;
 }
 
-// forward / backward of `s`, sparsity penalty, clip norm, AdamW + EMA; `nb`, when complete, is binned along the way
+// the second parameter group of a one-call step (stdadk_train_step_knots_f32): the learnable knots
+struct KnotStep {
+  const stdadk_knot_train *kt = nullptr;
+  float *d_centers = nullptr, *d_log_bw = nullptr;
+  const stdadk_adam_group *group = nullptr;
+};
+
+// what the knots door refuses before anything is planned: flags, the knot group, where its gradients go, the penalties
+static int check_knot_step(const StepCall &s, const KnotStep &k) {
+  const stdadk_basis_desc *b = s.b; const stdadk_mlp_desc *d = s.d;
+  STDADK_REQUIRE(b && d, STDADK_E_ARG, "train_step_knots: basis / mlp descriptor is NULL");
+  STDADK_REQUIRE((s.flags & STDADK_FLAG_LOG_BW), STDADK_E_ARG,
+                 "train_step_knots: flags need STDADK_FLAG_LOG_BW (learnable knots: basis->s_bw holds log-bandwidths)");
+  STDADK_REQUIRE(!(s.flags & STDADK_FLAG_PACK_F32), STDADK_E_ARG,
+                 "train_step_knots: flags carry STDADK_FLAG_PACK_F32; packed fp32 copies are not kept on this path");
+  STDADK_REQUIRE(b->Ks > 0 && b->Ks < (1ll << 31) && d->n_hidden >= 1, STDADK_E_ARG,
+                 "train_step_knots: no spatial knots / no hidden layer");
+  const stdadk_adam_group *g = k.group;
+  STDADK_REQUIRE(g && g->p && g->g && g->m && g->v && g->n > 0, STDADK_E_ARG, "train_step_knots: knots group incomplete");
+  STDADK_REQUIRE(!g->shadow, STDADK_E_ARG, "train_step_knots: knots->shadow must be NULL (the knot group has no operand copies)");
+  STDADK_REQUIRE(g->max_norm <= 0.f || g->sumsq_parts, STDADK_E_ARG,
+                 "train_step_knots: knots->max_norm > 0 needs knots->sumsq_parts (STDADK_SUMSQ_PARTS floats)");
+  STDADK_REQUIRE(k.d_centers && k.d_log_bw, STDADK_E_ARG, "train_step_knots: d_centers / d_log_bw is NULL");
+  const float *lo = g->g, *hi = g->g + g->n;
+  STDADK_REQUIRE(k.d_centers >= lo && k.d_centers + 2 * b->Ks <= hi, STDADK_E_ARG,
+                 "train_step_knots: d_centers [Ks,2] lies outside the knot group's gradient range [knots->g, knots->g + n)");
+  STDADK_REQUIRE(k.d_log_bw >= lo && k.d_log_bw + b->Ks <= hi, STDADK_E_ARG,
+                 "train_step_knots: d_log_bw [Ks] lies outside the knot group's gradient range [knots->g, knots->g + n)");
+  STDADK_REQUIRE(s.P && s.P->W[0], STDADK_E_ARG, "train_step_knots: params->W[0] is NULL");
+  return check_knot_train("train_step_knots: kt", k.kt);
+}
+
+// forward / backward of `s`, sparsity penalty, clip norm, AdamW + EMA; `nb`, when complete, is binned along the way.
+// `ks`: the step has a second parameter group, the learnable knots -- their finish rides in the step's finishing
+// launch (step_finish.hip), both groups are stepped by one two-group AdamW launch, and the next batch is binned by
+// the weight-gradient launch or not at all.
 static int train_step_impl(StepCall s, const stdadk_sparsity_desc *sparsity, const stdadk_optim_desc *o,
-                           const NextBatch &nb) {
+                           const NextBatch &nb, const KnotStep *ks = nullptr) {
   const stdadk_basis_desc *b = s.b; const stdadk_mlp_desc *d = s.d;
   if (nb.binned) *nb.binned = 0;
   STDADK_REQUIRE(o && o->p && o->g && o->m && o->v && o->n > 0 && o->step_dev, STDADK_E_ARG,
                  "train_step: optimiser descriptor incomplete");
   STDADK_REQUIRE(o->max_norm <= 0.f || o->sumsq_parts, STDADK_E_ARG, "train_step: max_norm > 0 needs sumsq_parts");
+  if (ks) {
+    const int rc = check_knot_step(s, *ks);
+    if (rc) return rc;
+  }
   if (s.B == 0) return 0;
   s.step_dev = o->step_dev;
   // the NEXT batch is validated and planned before anything of this step is enqueued: a call that fails on it
@@ -1747,7 +1854,14 @@ static int train_step_impl(StepCall s, const stdadk_sparsity_desc *sparsity, con
   const bool sparse = sparsity && sparsity->kind != STDADK_SPARSITY_NONE;
   // with a sparsity penalty the gradient changes once more after the reductions: the norm is a pass of its own
   const bool fuse_sq = clip && !sparse;
-  const StepRide ride = {fuse_sq ? o->sumsq_parts : nullptr, fuse_sq ? o->step_dev : nullptr, bin_in_dw ? &ba : nullptr};
+  StepRide ride = {fuse_sq ? o->sumsq_parts : nullptr, fuse_sq ? o->step_dev : nullptr, bin_in_dw ? &ba : nullptr};
+  if (ks) {
+    // the finishing launch is in every learnable step and advances the counter; no other launch of the step does
+    ride.step_inc = nullptr;
+    ride.knots = true; ride.kt = ks->kt; ride.d_centers = ks->d_centers; ride.d_log_bw = ks->d_log_bw;
+    ride.knot_sq = ks->group->max_norm > 0.f ? const_cast<float *>(ks->group->sumsq_parts) : nullptr;
+    ride.finish_inc = o->step_dev;
+  }
   StepOut out;     // where the step's own launches left the squared-norm partials, if they did
   int rc = train_fwd_bwd_impl(s, &ride, &out);
   // (a failure behind the weight-gradient launch: the next batch may be binned, but the caller is not told so and
@@ -1765,10 +1879,10 @@ static int train_step_impl(StepCall s, const stdadk_sparsity_desc *sparsity, con
   if (clip && out.sq_parts) {
     parts = out.sq_parts; n_parts = out.sq_n;      // partials (and the step advance) came out of the step's launches
   } else if (clip) {
-    rc = stdadk_sumsq_f32(o->g, o->n, o->sumsq_parts, o->step_dev, s.stream);
+    rc = stdadk_sumsq_f32(o->g, o->n, o->sumsq_parts, ks ? nullptr : o->step_dev, s.stream);
     if (rc) return rc;
     n_parts = STDADK_SUMSQ_PARTS;
-  } else {
+  } else if (!ks) {
     rc = stdadk_step_advance(o->step_dev, s.stream);
     if (rc) return rc;
   }
@@ -1778,6 +1892,15 @@ static int train_step_impl(StepCall s, const stdadk_sparsity_desc *sparsity, con
   stdadk_adam_group gr;
   AdamHyper h;
   optim_group(o, clip ? parts : nullptr, n_parts, s.loss_sum, &gr, &h);
+  if (ks) {
+    // MLP group first: it keeps the guard and the bf16 copies.  The knot group's partials are the finishing launch's.
+    stdadk_adam_group kg = *ks->group;
+    kg.n_parts = kg.max_norm > 0.f ? STDADK_SUMSQ_PARTS : 0;
+    if (!(kg.max_norm > 0.f)) kg.sumsq_parts = nullptr;
+    rc = adamw_launch("train_step_knots", 2, &gr, &kg, h, nullptr, s.stream);
+    if (rc == 0 && out.binned_next) *nb.binned = 1;
+    return rc;
+  }
   rc = adamw_launch("adamw", 1, &gr, nullptr, h, bin, s.stream, (s.flags & STDADK_FLAG_PACK_F32) != 0);
   if (rc == 0 && (bin || out.binned_next)) *nb.binned = 1;
   return rc;
@@ -1816,6 +1939,30 @@ extern "C" int stdadk_train_step_next_f32(const stdadk_basis_desc *b, const stda
   s.workspace_bytes = workspace_bytes; s.drop_seed = drop_seed; s.flags = flags; s.stream = stream;
   s.idx = idx;
   return train_step_impl(s, sparsity, o, {next_idx, next_B, next_y_cols, next_workspace, next_workspace_bytes, next_binned});
+}
+
+extern "C" int stdadk_train_step_knots_f32(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
+                                           const stdadk_mlp_tensors *P, const stdadk_mlp_tensors *G,
+                                           const float *coords_all, const float *t_all, const float *X_all,
+                                           const float *y_all, const int64_t *idx, int64_t B, float grad_scale,
+                                           const stdadk_loss_desc *loss, const stdadk_sparsity_desc *sparsity,
+                                           float *loss_sum, void *workspace, size_t workspace_bytes,
+                                           uint64_t drop_seed, int32_t flags, const stdadk_optim_desc *o,
+                                           const int64_t *next_idx, int64_t next_B, int32_t next_y_cols,
+                                           void *next_workspace, size_t next_workspace_bytes, int32_t *next_binned,
+                                           const stdadk_knot_train *kt, float *d_centers, float *d_log_bw,
+                                           const stdadk_adam_group *knots, stdadk_stream_t stream) {
+  const bool no_next = !next_idx && next_B == 0 && !next_workspace;
+  STDADK_REQUIRE(next_binned || no_next, STDADK_E_ARG, "train_step_knots: next_binned is NULL with a next batch given");
+  StepCall s;
+  s.b = b; s.d = d; s.P = P; s.G = G; s.coords = coords_all; s.t = t_all; s.X = X_all; s.y = y_all; s.B = B;
+  s.grad_scale = grad_scale; s.loss = loss; s.loss_sum = loss_sum; s.workspace = workspace;
+  s.workspace_bytes = workspace_bytes; s.drop_seed = drop_seed; s.flags = flags; s.stream = stream;
+  s.idx = idx;
+  KnotStep ks;
+  ks.kt = kt; ks.d_centers = d_centers; ks.d_log_bw = d_log_bw; ks.group = knots;
+  return train_step_impl(s, sparsity, o, {next_idx, next_B, next_y_cols, next_workspace, next_workspace_bytes, next_binned},
+                         &ks);
 }
 
 extern "C" int stdadk_bin_batch_f32(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,

@@ -148,6 +148,13 @@ _SIGNATURES = {
                                              C.POINTER(SparsityDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64,
                                              C.c_int32, C.POINTER(OptimDesc), C.c_void_p, C.c_int64, C.c_int32,
                                              C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.c_void_p]),
+    "stdadk_train_step_knots_f32": (C.c_int, [C.POINTER(BasisDesc), C.POINTER(MlpDesc), C.POINTER(MlpTensors),
+                                              C.POINTER(MlpTensors), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int64, C.c_float, C.POINTER(LossDesc),
+                                              C.POINTER(SparsityDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64,
+                                              C.c_int32, C.POINTER(OptimDesc), C.c_void_p, C.c_int64, C.c_int32,
+                                              C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(KnotTrain),
+                                              C.c_void_p, C.c_void_p, C.POINTER(AdamGroup), C.c_void_p]),
     "stdadk_sumsq2_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "stdadk_adamw_ema2_f32": (C.c_int, [C.POINTER(AdamGroup), C.POINTER(AdamGroup), C.c_float, C.c_float,
@@ -938,6 +945,36 @@ def train_step_next(basis, desc, params, grads, coords_all, t_all, X_all, y_all,
         y_all.shape[1] if y_all is not None else 0, next_workspace.data_ptr(),
         next_workspace.numel() * next_workspace.element_size(), C.byref(done), _stream())
     _check(rc, "stdadk_train_step_next_f32")
+    return bool(done.value)
+
+
+def train_step_knots(basis, desc, params, grads, coords, t, X, y, idx, B, grad_scale, loss_sum, workspace, flags, optim,
+                     knot_train, d_centers, d_log_bw, knots, nxt=None, seed=0, loss_desc=None, sparsity_desc=None):
+    """The whole single-GPU step of a learnable-knot model in one call (stdadk_train_step_knots_f32): forward, objective,
+    backward, knot gradients + penalties, both clip norms, AdamW + EMA of both parameter groups.  `optim` (make_optim)
+    describes the MLP group and the shared hyper-parameters, `knots` (make_adam_group) the knot group; `idx` may be None
+    (rows 0..B-1 of the given arrays).  `nxt` = (next_idx, next_workspace): the rows of the following step, binned by
+    this step's weight-gradient launch when it can carry them.  Returns True when it did (step on next_workspace with
+    FLAG_PREBINNED then), False when nothing was prepared."""
+    ixs = (("idx", idx),) + ((("next_idx", nxt[0]),) if nxt is not None else ())
+    for nm, ix in ixs:
+        if ix is not None and (ix.dtype != torch.int64 or not _on_device(ix) or not ix.is_contiguous()):
+            raise RuntimeError(f"train_step_knots: {nm} must be a contiguous int64 tensor on the device")
+    if nxt is not None and nxt[1].data_ptr() == workspace.data_ptr():
+        raise RuntimeError("train_step_knots: the next batch needs a workspace of its own")
+    done = C.c_int32(0)
+    rc = lib().stdadk_train_step_knots_f32(
+        C.byref(basis), C.byref(desc), C.byref(params), C.byref(grads), _dev(coords, "coords"), _dev(t, "t"),
+        _dev(X, "X"), _dev(y, "y"), idx.data_ptr() if idx is not None else None, B, grad_scale,
+        C.byref(loss_desc) if loss_desc is not None else None,
+        C.byref(sparsity_desc) if sparsity_desc is not None else None, _dev(loss_sum, "loss_sum"), workspace.data_ptr(),
+        workspace.numel() * workspace.element_size(), seed, flags, C.byref(optim),
+        nxt[0].data_ptr() if nxt is not None else None, nxt[0].numel() if nxt is not None else 0,
+        y.shape[1] if (nxt is not None and y is not None) else 0, nxt[1].data_ptr() if nxt is not None else None,
+        nxt[1].numel() * nxt[1].element_size() if nxt is not None else 0, C.byref(done),
+        C.byref(knot_train) if knot_train is not None else None, _dev(d_centers, "d_centers"),
+        _dev(d_log_bw, "d_log_bw"), C.byref(knots), _stream())
+    _check(rc, "stdadk_train_step_knots_f32")
     return bool(done.value)
 
 

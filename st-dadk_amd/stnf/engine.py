@@ -182,6 +182,12 @@ class TrainStep:
         replicated mode (scripts/train_st_interp.py:696-712: global-norm clip, step, EMA) up to the order of the
         clip norm's partial sums.
 
+    One-call learnable step (`fused_knot_step`, default off; None reads STNF_FUSED_KNOT_STEP, "1" = on): a single-GPU
+    step of a learnable-knot model without the delta head as ONE library call (stdadk_train_step_knots_f32) instead of
+    four -- the knot finish and both clip norms out of one finishing launch, the next batch binned inside the
+    weight-gradient launch.  Same arithmetic as the split calls; with clipping off bit-identical to them.
+    `fused_knot_step=True` where the call does not apply raises ValueError.
+
     Packed weights (`pack_weights`, default on; `STNF_NO_PACK_WEIGHTS=1` turns it off): fp32 one-call steps with hidden
     widths of 128 / 256 stream the hidden weights after the first from fragment-order copies (N.FLAG_PACK_F32) that
     the step's optimiser launch keeps current and `refresh_bf16` rebuilds after any other write of the parameters.
@@ -199,7 +205,7 @@ class TrainStep:
                  domain_penalty_weight=0.0, movement_penalty_weight=0.0, sparsity_penalty_type="none",
                  sparsity_lambda_l1=0.001, sparsity_lambda_group=0.01, sparsity_apply_to_spatial=True,
                  sparsity_apply_to_temporal=True, seed=None, world_size=None, dtype="f32", shard_optimizer=False,
-                 sync_init=True, nonfinite_guard=True, inline_prep=True, pack_weights=True):
+                 sync_init=True, nonfinite_guard=True, inline_prep=True, pack_weights=True, fused_knot_step=None):
         self.model = model
         if dtype not in ("f32", "bf16"):
             raise ValueError(f"unknown dtype '{dtype}'; use 'f32' or 'bf16'")
@@ -231,6 +237,20 @@ class TrainStep:
             # (split path, 1/world shares of the parameter-level penalties); see set_virtual_rank
             self.world = int(world_size)
         self.shard = bool(shard_optimizer) and self.world > 1
+        # learnable knots as ONE library call per step (stdadk_train_step_knots_f32), off by default: None reads
+        # STNF_FUSED_KNOT_STEP ("1" = on) and quietly keeps the split path where the call does not apply, True insists
+        want_knot_step = os.environ.get("STNF_FUSED_KNOT_STEP", "") == "1" if fused_knot_step is None \
+            else bool(fused_knot_step)
+        missing = [why for bad, why in (
+            (not model.spatial_basis.learnable, "a model with learnable knots (spatial_learnable=True)"),
+            (self.distributed or self.world != 1, "a single process (world size 1): data-parallel steps keep the split "
+                                                  "calls around their all-reduce"),
+            (model._has_delta, "a model without the delta head (use_delta_reparameterization=False)"),
+            (bool(two_streams), "two_streams=False (no auxiliary stream)")) if bad]
+        if missing and fused_knot_step is not None and want_knot_step:
+            raise ValueError(f"fused_knot_step=True needs {missing[0]}")
+        self._knot_step = want_knot_step and not missing
+        self._knot_plan = None          # cached descriptors of the one-call learnable step (_knot_step_plan)
         if self.distributed and sync_init:
             # identical replicas: parameters AND buffers (knot tables of the gmm / random_site initialisers depend on
             # the rank's own train_coords) from rank 0, before anything is derived from them
@@ -505,6 +525,18 @@ class TrainStep:
                          self._optim, seed=self.seed, loss_desc=self._loss_desc(y.shape[1]),
                          sparsity_desc=self._sparsity)
             return False
+        if self._knot_step:
+            # single GPU, learnable knots: the two-group step as ONE library call -- the knot finish and both clip
+            # norms come out of the step's finishing launch, the next batch is binned by the weight-gradient launch
+            if B == 0:
+                raise RuntimeError("an empty batch cannot carry the parameter-level penalties of a learnable-knot step")
+            optim, knots = self._knot_step_plan()
+            return N.train_step_knots(st.basis, st.desc, st.params, self.grads_t, coords, t, X, y,
+                                      idx if (nxt is not None or not prebinned) else None, B,
+                                      D.grad_scale(global_rows, Q), self.loss_sum, ws, flags, optim,
+                                      self._knot_train_desc(B * Q), self.g_centers, self.g_log_bw, knots, nxt=nxt,
+                                      seed=self.seed, loss_desc=self._loss_desc(y.shape[1]),
+                                      sparsity_desc=self._sparsity)
         self._enqueue_grads(X, coords, t, y, B, global_rows, idx=idx, ws=ws, prebinned=prebinned)
         if self.shard:
             if not self.distributed:
@@ -653,21 +685,47 @@ class TrainStep:
                                   self.nc_lambda * B * Q, self.d_delta,
                                   self.loss_sum if self.nc_lambda != 0.0 else None)
         if self.learnable:
-            sb = self.model.spatial_basis
-            kkey = (sb.centers_init.data_ptr(), sb.gradient_damping, sb.damping_threshold, sb.damping_strength,
-                    self.domain_w, self.movement_w, self.world, B * Q)
-            if self._knot_train is None or self._knot_train[0] != kkey:
-                self._knot_train = (kkey, N.make_knot_train(sb.centers_init, sb.gradient_damping, sb.damping_threshold,
-                                                            sb.damping_strength, self.domain_w, self.movement_w,
-                                                            penalty_grad_scale=1.0 / self.world,
-                                                            penalty_loss_scale=float(B * Q)))
-            kt = self._knot_train[1]
+            kt = self._knot_train_desc(B * Q)
             N.knot_backward(st.basis, st.desc, st.params, coords, B, ws, st.flags, kt,
                             self.g_centers, self.g_log_bw, self.loss_sum)
         if self._sparsity is not None:
             m = self.model
             N.sparsity(self._sparsity, self._w0t, self._g_w0t, True, m.p, m.k_spatial, m.k_temporal,
                        grad_scale=1.0 / self.world, loss_scale=float(B * Q), loss_sum=self.loss_sum)
+
+    def _knot_train_desc(self, rows_q):
+        """The knot penalties' descriptor for a batch of rows_q = rows x Q objective terms (cached: rebuilt when a
+        setting or the batch size changes)."""
+        sb = self.model.spatial_basis
+        kkey = (sb.centers_init.data_ptr(), sb.gradient_damping, sb.damping_threshold, sb.damping_strength,
+                self.domain_w, self.movement_w, self.world, rows_q)
+        if self._knot_train is None or self._knot_train[0] != kkey:
+            self._knot_train = (kkey, N.make_knot_train(sb.centers_init, sb.gradient_damping, sb.damping_threshold,
+                                                        sb.damping_strength, self.domain_w, self.movement_w,
+                                                        penalty_grad_scale=1.0 / self.world,
+                                                        penalty_loss_scale=float(rows_q)))
+        return self._knot_train[1]
+
+    def _knot_step_plan(self):
+        """(optimiser descriptor of the MLP group, group descriptor of the knots) of the one-call learnable step: the
+        groups of _adam_plan -- the knots are the head [0, knot_end) of the flat buffers, the MLP the rest -- in the
+        form stdadk_train_step_knots_f32 takes them.  Cached like that plan: rebuilt only when a buffer, the boundary
+        or a rate changes."""
+        ema, ke = self.ema, self.knot_end
+        key = (self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+               ema.data_ptr() if ema is not None else 0, ke, self.lr, self.grad_clip, id(self.lr_dev),
+               self.basis_lr, self.basis_clip, id(self.basis_lr_dev))
+        if self._knot_plan is not None and self._knot_plan[0] == key:
+            return self._knot_plan[1]
+        optim = N.make_optim(self.flat[ke:], self.grad[ke:], self.m[ke:], self.v[ke:],
+                             ema[ke:] if ema is not None else None, self.lr, self.lr_dev, self.betas, self.eps, self.wd,
+                             self.step_dev, self.grad_clip, self._sumsq512 if self.grad_clip > 0 else None,
+                             self.ema_decay, shadow=self._shadow(ke), nonfinite_step=self.nonfinite)
+        knots = N.make_adam_group(self.flat[:ke], self.grad[:ke], self.m[:ke], self.v[:ke],
+                                  ema[:ke] if ema is not None else None, self.basis_lr, self.basis_lr_dev,
+                                  self.basis_clip, self.sumsq_basis if self.basis_clip > 0 else None)
+        self._knot_plan = (key, (optim, knots))
+        return self._knot_plan[1]
 
     def set_virtual_rank(self, rank):
         """Tests of the data-parallel arithmetic on one GPU: play rank `rank` of `world_size` (dropout stream
@@ -883,7 +941,8 @@ class TrainStep:
             nxt = next_idx if next_idx.is_contiguous() else next_idx.contiguous()
         # one-call step on a small batch: the NEXT batch is binned by extra workgroups of this step's optimiser launch
         # (no side stream, no cross-stream packets in the main queue: DESIGN.md section 8, "the bubble between steps")
-        if (nxt is not None and self._whole_step and self.inline_prep and not self.distributed
+        # (the one-call learnable step takes it in its weight-gradient launch, or declines)
+        if (nxt is not None and (self._whole_step or self._knot_step) and self.inline_prep and not self.distributed
                 and nxt.numel() <= 8192 and nxt.dtype == torch.int64):
             me = idx if idx.is_contiguous() else idx.contiguous()
             if self._enqueue(Xa, coords_all, t_all, y_all, B, global_rows, idx=me, ws=pp["ws"][wsi],

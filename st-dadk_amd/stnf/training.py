@@ -134,7 +134,8 @@ def make_engine(model, config, batch_size, batches_per_epoch):
                      sparsity_lambda_group=config.get("sparsity_lambda_group", 0.01),
                      sparsity_apply_to_spatial=config.get("sparsity_apply_to_spatial", True),
                      sparsity_apply_to_temporal=config.get("sparsity_apply_to_temporal", True),
-                     seed=config.get("dropout_seed", None), dtype=config.get("dtype", "f32"))
+                     seed=config.get("dropout_seed", None), dtype=config.get("dtype", "f32"),
+                     fused_knot_step=config.get("fused_knot_step", None))
 
 
 def _ema_full(eng):
