@@ -747,7 +747,8 @@ int stdadk_gemm_f32(const float *A, int64_t lda, int32_t a_km, const float *B, i
  * on its launch stream.  stdadk_profile_collect synchronises them and writes one "name\tms\n" line
  * per launch (launch order) into buf; it returns the bytes needed including the terminator (call
  * again with a bigger buffer if that exceeds cap).  Enabling clears earlier records.  Not for use
- * under stream capture; host-side, single-threaded.
+ * under stream capture; host-side, single-threaded.  In a dry run (STDADK_DRY_RUN=1) nothing is launched or timed,
+ * but the names are still recorded: the lines read "name\t0.000000" -- the launch chain of a call without a device.
  * ------------------------------------------------------------------------------------------ */
 int stdadk_profile_enable(int32_t on);
 int64_t stdadk_profile_collect(char *buf, int64_t cap);

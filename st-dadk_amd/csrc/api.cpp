@@ -28,7 +28,7 @@ void set_error(const char *fmt, ...) {
 // record makes the command processor write back / invalidate the caches around the kernel it brackets, which the
 // bracket then counts as kernel time.  The events are pooled: nothing is created on the launch path.
 bool g_prof_on = false;
-struct ProfRec { std::string name; hipEvent_t e0, e1; };
+struct ProfRec { std::string name; hipEvent_t e0, e1; };    // e0 == e1 == NULL: a dry run's record, name only
 static std::vector<ProfRec> g_recs;
 static std::vector<hipEvent_t> g_pool;
 
@@ -46,13 +46,15 @@ void prof_before(const char *name, hipStream_t st) {
   (void)hipEventRecord(r.e0, st);
   g_recs.push_back(r);
 }
+void prof_dry(const char *name) { g_recs.push_back(ProfRec{name, nullptr, nullptr}); }
 void prof_after(hipStream_t st) {
   if (!g_recs.empty()) (void)hipEventRecord(g_recs.back().e1, st);
 }
 }  // namespace stdadk
 
 extern "C" int stdadk_profile_enable(int32_t on) {
-  for (auto &r : stdadk::g_recs) { stdadk::g_pool.push_back(r.e0); stdadk::g_pool.push_back(r.e1); }
+  for (auto &r : stdadk::g_recs)
+    if (r.e0) { stdadk::g_pool.push_back(r.e0); stdadk::g_pool.push_back(r.e1); }
   stdadk::g_recs.clear();
   stdadk::g_prof_on = on != 0;
   return 0;
@@ -63,9 +65,11 @@ extern "C" int stdadk_profile_enable(int32_t on) {
 extern "C" int64_t stdadk_profile_collect(char *buf, int64_t cap) {
   std::string out;
   for (auto &r : stdadk::g_recs) {
-    if (hipEventSynchronize(r.e1) != hipSuccess) return STDADK_E_ARG;
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, r.e0, r.e1) != hipSuccess) return STDADK_E_ARG;
+    if (r.e0) {
+      if (hipEventSynchronize(r.e1) != hipSuccess) return STDADK_E_ARG;
+      if (hipEventElapsedTime(&ms, r.e0, r.e1) != hipSuccess) return STDADK_E_ARG;
+    }
     char line[32];
     snprintf(line, sizeof(line), "\t%.6f\n", ms);
     out += r.name;

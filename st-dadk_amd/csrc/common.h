@@ -37,12 +37,18 @@ extern bool g_dry_run;
 
 // Every kernel launch goes through this macro so that stdadk_profile_enable() can bracket it with
 // HIP events on the launch stream (per-kernel device time without an external profiler).
+// In a dry run with the profiler on, the launch is not made but its name is: prof_dry appends a record without events,
+// so that stdadk_profile_collect lists which kernels a call would enqueue, in order (name\t0.000000).
 void prof_before(const char *name, hipStream_t st);
 void prof_after(hipStream_t st);
+void prof_dry(const char *name);
 extern bool g_prof_on;
 #define STDADK_LAUNCH(kern, grid, block, lds, st, ...)                         \
   do {                                                                        \
-    if (::stdadk::g_dry_run) break;                                           \
+    if (::stdadk::g_dry_run) {                                                \
+      if (::stdadk::g_prof_on) ::stdadk::prof_dry(#kern);                     \
+      break;                                                                  \
+    }                                                                         \
     if (::stdadk::g_prof_on) ::stdadk::prof_before(#kern, (st));              \
     hipLaunchKernelGGL(kern, grid, block, lds, st, __VA_ARGS__);              \
     if (::stdadk::g_prof_on) ::stdadk::prof_after((st));                      \
@@ -50,7 +56,10 @@ extern bool g_prof_on;
 
 #define STDADK_LAUNCH_NAMED(name, kern, grid, block, lds, st, ...)              \
   do {                                                                        \
-    if (::stdadk::g_dry_run) break;                                           \
+    if (::stdadk::g_dry_run) {                                                \
+      if (::stdadk::g_prof_on) ::stdadk::prof_dry((name));                    \
+      break;                                                                  \
+    }                                                                         \
     if (::stdadk::g_prof_on) ::stdadk::prof_before((name), (st));             \
     hipLaunchKernelGGL(kern, grid, block, lds, st, __VA_ARGS__);              \
     if (::stdadk::g_prof_on) ::stdadk::prof_after((st));                      \

@@ -37,7 +37,7 @@ static int bwd_rows(int64_t B) {
 // ---------------------------------------------------------------------------------------------
 enum PlanMode { PLAN_MLP = 0, PLAN_STEP_DENSE = 1, PLAN_STEP_WINDOW = 2 };
 
-// rows from which the merged weight-gradient launch also does the reductions (run_backward, FinArgs): measured
+// rows from which the merged weight-gradient launch also does the reductions (finishing_mode, FinArgs): measured
 // per step at 8 192 / 16 384 / 32 768 / 65 536 rows: +4 / 0 / -9 / -17 us against the reductions launch
 constexpr int64_t FIN_FULL_MIN_ROWS = 49152;
 
@@ -498,80 +498,6 @@ static int check_desc(const stdadk_mlp_desc *d) {
 // the default objective: plain MSE against y [B,Q] (y_cols 0 = Q), every quantile level 0.5
 static const LossDev LOSS_PLAIN_MSE = {STDADK_LOSS_MSE, 0, {0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f}, 0.f, 1};
 
-struct Ctx {
-  const stdadk_mlp_desc *d = nullptr;
-  const stdadk_mlp_tensors *P = nullptr, *G = nullptr;
-  float *ws = nullptr;
-  Plan pl = {};
-  hipStream_t st = nullptr;
-  int64_t B = 0;
-  bool w0t = false;     // W[0] / dW[0] stored (in,out)
-  float dp = 0.f;       // effective dropout probability (0 in eval)
-  uint64_t seed = 0;
-  const int *step_dev = nullptr;
-  const uint8_t *const *masks = nullptr;
-  // fused MSE (tail path): targets in the row order of the activations; outputs optional
-  const float *mse_y = nullptr;
-  float mse_scale = 0.f;
-  float *mse_dY = nullptr;
-  float *mse_loss = nullptr;
-  bool mse_done = false;        // set by run_forward when the loss was fused into the tail kernel
-  // fused training step: run_forward parks the tail launch here and run_backward issues it together
-  // with the backward chain as ONE kernel (the tail of a row tile is row-local through the loss)
-  bool fuse_tail = false, pend_valid = false;
-  TailFwdArgs pend = {};
-  // whole-step entry (stdadk_train_step_f32): squared-norm partials of the gradient ride along with the
-  // reductions launch when every gradient is produced by it or by the per-knot gather
-  float *gradsq = nullptr;      // [STDADK_GRADSQ_PARTS] or NULL
-  int *step_inc = nullptr;
-  bool gradsq_done = false, all_grouped = true;
-  const float *gradsq_out = nullptr;   // where the partials went when gradsq_done (gradsq, or the slots of the merged
-  int gradsq_n = 0;                    // dW launch) and how many
-  bool merge_dw = false, dw_pend = false;   // window path: grouped dW products + per-knot gather as one launch
-  int fin = 0;                  // ... 2: which also does the reductions (FinArgs; the tail launch cleared the counters);
-                                // 1: which leaves the squared-norm slots of its knot rows, reductions launch behind it
-  GemmGroup gg_pend = {};
-  ReduceGroup rg_pend = {};
-  // one-call step that announces its NEXT batch: the merged dW launch bins it when it is what the step runs
-  const BinSmallArgs *bin_next = nullptr;
-  bool bin_next_done = false;
-  bool l1_pend_valid = false;   // window path, B <= 4096: the layer-0 launch is parked as well
-  L1FwdArgs l1_pend = {};
-  int l1_basis = 0;
-  // materialising path, small D: layer 0 starts inside the tail launch from the raw observations (TailDense0)
-  bool d0 = false;
-  const float *d0_coords = nullptr, *d0_t = nullptr, *d0_X = nullptr, *d0_bw = nullptr;
-  bool scattered = false;       // STDADK_FLAG_SCATTERED: the knots of a level sit anywhere (window path through knot cell lists)
-  bool bf16 = false;            // STDADK_FLAG_BF16: bf16 operands in the fused tail kernels (P->W_bf16 / WT_bf16)
-  bool pack = false;            // STDADK_FLAG_PACK_F32: fragment-order fp32 weight copies in the fused tail kernels (the
-                                // P->W_bf16 / WT_bf16 slots read as float *PF / *PB)
-  bool cap32 = false;           // this batch's tail launches use <= 32-row tiles (bf16 + dense layer 0 in the launch)
-  bool save = true;             // false in eval mode: the forward keeps nothing for a backward (xhat, rstd, act, psi)
-  bool log_bw = false;          // basis->s_bw holds log-bandwidths (learnable knots)
-  const int64_t *idx = nullptr; // window path: the batch is rows idx[b] of the resident observation arrays
-  bool prebinned = false;       // window path: stdadk_bin_batch_f32 already filled the workspace's bins
-  LossDev loss = LOSS_PLAIN_MSE;
-  const float *dz0 = nullptr;   // set by run_backward: dZ of layer 0
-  // optional second stream: independent kernels of a step fork onto it (hipGraph-capturable
-  // fork/join through events); NULL = everything on `st`
-  hipStream_t aux = nullptr;
-  int (*fork_after_dz)(Ctx &) = nullptr;   // called by run_backward (fused tail) right after the dZ kernel
-  const stdadk_basis_desc *basis = nullptr;
-  const stdadk_basis_desc *basis_in = nullptr;   // set by open_step (scattered_bins reads the log-bandwidths)
-  bool dw0_forked = false;        // the per-knot gather of dW0^T was forked onto the auxiliary stream
-  // extra products C[M][H0] = A^T dZ_0 (reduction over the batch) to run with the dW GEMMs of the
-  // fused-tail backward: the temporal / covariate rows of dW0^T on the window path
-  int n_extra = 0;
-  struct { const float *A; int64_t lda; int M; float *C; } extra[2] = {};
-  // one-call learnable step (stdadk_train_step_knots_f32): the finishing launch (step_finish.hip) closes the knot
-  // group's gradient, leaves its clip-norm partials and advances the step counter; where the step's reductions
-  // launch is still pending behind the merged dW launch it takes that launch's place and carries its jobs
-  bool knot_ride = false, knot_done = false;
-  const stdadk_knot_train *knot_kt = nullptr;
-  float *knot_dc = nullptr, *knot_dlb = nullptr, *knot_sq = nullptr;
-  int *knot_inc = nullptr;
-};
-
 // One description of a training step call: what the public doors take positionally, by name
 struct StepCall {
   const stdadk_basis_desc *b = nullptr;
@@ -610,6 +536,77 @@ struct NextBatch {   // the batch a one-call step announces (stdadk_train_step_n
   void *workspace = nullptr;
   size_t workspace_bytes = 0;
   int32_t *binned = nullptr;   // set to 1 once the batch sits binned in `workspace`
+};
+
+static const StepRide NO_RIDE;
+
+// The description of one opened call: written by the opener (open_mlp / open_step) and the door's own preamble (loss,
+// targets, idx, auxiliary stream, fuse_tail, ride), then read-only -- every stage below takes it as `const Ctx &`.
+// What one stage of a step produces for a later one travels by value between them, visible in their caller: the
+// row-local launches the forward holds back (Held), the weight-gradient jobs behind the dZ launch (DwJobs), and what
+// the step's closing launches left for the optimiser (StepOut).
+struct Ctx {
+  const stdadk_mlp_desc *d = nullptr;
+  const stdadk_mlp_tensors *P = nullptr, *G = nullptr;
+  float *ws = nullptr;
+  Plan pl = {};
+  hipStream_t st = nullptr;
+  int64_t B = 0;
+  const stdadk_basis_desc *basis = nullptr;   // step-level calls (open_step)
+  bool window = false;          // the step runs the window path (want_window)
+  bool w0t = false;             // W[0] / dW[0] stored (in,out)
+  float dp = 0.f;               // effective dropout probability (0 in eval)
+  uint64_t seed = 0;
+  const int *step_dev = nullptr;
+  const uint8_t *const *masks = nullptr;
+  bool scattered = false;       // STDADK_FLAG_SCATTERED: the knots of a level sit anywhere (window path through knot cell lists)
+  bool bf16 = false;            // STDADK_FLAG_BF16: bf16 operands in the fused tail kernels (P->W_bf16 / WT_bf16)
+  bool pack = false;            // STDADK_FLAG_PACK_F32: fragment-order fp32 weight copies in the fused tail kernels (the
+                                // P->W_bf16 / WT_bf16 slots read as float *PF / *PB)
+  bool save = true;             // false in eval mode: the forward keeps nothing for a backward (xhat, rstd, act, psi)
+  bool log_bw = false;          // basis->s_bw holds log-bandwidths (learnable knots)
+  bool prebinned = false;       // window path: stdadk_bin_batch_f32 already filled the workspace's bins
+  // ---- the door's preamble
+  const int64_t *idx = nullptr; // window path: the batch is rows idx[b] of the resident observation arrays
+  LossDev loss = LOSS_PLAIN_MSE;
+  // fused loss (tail path): targets in the row order of the activations; outputs optional
+  const float *mse_y = nullptr;
+  float mse_scale = 0.f;
+  float *mse_dY = nullptr;
+  float *mse_loss = nullptr;
+  bool fuse_tail = false;       // training step: the forward may hold its row-local launches back for the backward's
+  // optional second stream: independent kernels of a step fork onto it (hipGraph-capturable
+  // fork/join through events); NULL = everything on `st`
+  hipStream_t aux = nullptr;
+  const StepRide *ride = &NO_RIDE;   // what the one-call step lets ride along with its launches
+};
+
+// The row-local launches a training forward filled but did not issue: the backward's row-local launch runs them with
+// the backward chain as ONE kernel (layer 0 of the window path, the tail forward and the loss are row-local, like the
+// tail backward).  Caller-owned storage, filled in place.
+struct Held {
+  TailFwdArgs tail;
+  L1FwdArgs l1;
+  bool tail_held = false, l1_held = false;   // l1_held only with tail_held
+  bool cap32 = false;           // this batch's tail launches use <= 32-row tiles (bf16 + dense layer 0 in the launch)
+  bool loss_fused = false;      // the tail launch computes the loss (issued or held)
+};
+
+// materialising path, small D: layer 0 starts inside the tail launch from the raw observations (TailDense0)
+struct Dense0Src { const float *coords, *t, *X, *s_bw; };
+
+// an extra product C[M][H0] = A^T dZ_0 (reduction over the batch) to run with the dW GEMMs of the fused-tail
+// backward: the temporal / covariate rows of dW0^T on the window path
+struct ExtraProduct { const float *A; int64_t lda; int M; float *C; };
+
+// What is left to do behind the dZ launch of the fused-tail backward: the dW products as one grouped launch, every
+// fixed-order sum as one reductions launch.  Collected by collect_dw_jobs; its caller launches them or merges them
+// into the per-knot gather.
+struct DwJobs {
+  GemmGroup gg;
+  ReduceGroup rg;
+  bool all_grouped = true;      // false: a product was not groupable and went out as a stand-alone GEMM
+  bool dw0_in_group = false;    // materialising path: dW0^T joined the group
 };
 
 // fork/join between the main and the auxiliary stream (events are created once per thread)
@@ -669,7 +666,7 @@ static void tail_fwd_model(TailFwdArgs &a, const stdadk_mlp_desc *d, const stdad
 }
 
 // one hidden layer with the generic kernels: z = in W^T (+b) -> LN -> ReLU -> Dropout
-static int generic_layer_forward(Ctx &c, int l, const float *in, int64_t ld_in, int K) {
+static int generic_layer_forward(const Ctx &c, int l, const float *in, int64_t ld_in, int K) {
   const stdadk_mlp_desc *d = c.d;
   const stdadk_mlp_tensors *P = c.P;
   float *ws = c.ws;
@@ -702,10 +699,29 @@ static int generic_layer_forward(Ctx &c, int l, const float *in, int64_t ld_in, 
   return 0;
 }
 
-// hidden layers [l0, L) and the output layer; `in` = input of layer l0.  When the fused tail
-// applies, every layer after the first, the output layer and (if c.mse_y is set) the MSE loss run
-// in ONE kernel.
-static int run_forward(Ctx &c, int l0, const float *in, int64_t ld_in, int K, float *y_pred) {
+// "The fused tail applies": every layer after the first, the output layer, the loss and their backward run in the
+// tail kernels (masks, widths the tail refuses and STDADK_NO_FUSED_TAIL take the generic kernels)
+static bool fused_tail(const stdadk_mlp_desc *d, const uint8_t *const *masks = nullptr) {
+  return tail_enabled() && !masks && d->n_hidden >= 1 && tail_supported(d, 1);
+}
+static bool fused_tail(const Ctx &c) { return fused_tail(c.d, c.masks); }
+
+// "Layer 0 runs inside the tail launch" (materialising path): small feature width, (in,out) first weight, fused tail
+// available (environment STDADK_NO_DENSE0_TAIL=1: the separate kernels, diagnostic)
+static bool dense0_in_tail(const Ctx &c) {
+  return !c.window && c.w0t && c.d->in_dim <= TAIL_D0_MAX && fused_tail(c) && c.pl.ldf == ((c.d->in_dim + 31) & ~31) &&
+         getenv("STDADK_NO_DENSE0_TAIL") == nullptr;
+}
+
+// where the backward leaves dZ of layer 0 (fused tail: its per-layer buffer; generic: the shared one)
+static const float *layer0_dz(const Ctx &c) { return c.ws + (fused_tail(c) ? c.pl.dZl[0] : c.pl.dZ); }
+
+// hidden layers [l0, L) and the output layer; `in` = input of layer l0 (`d0`: layer 0 inside the tail launch instead).
+// When the fused tail applies, every layer after the first, the output layer and (if c.mse_y is set) the loss are ONE
+// launch: its arguments are filled into `a` and *tail is set -- the caller issues it (tail_forward) or holds it for
+// the backward's launch; what comes before it is issued here.  Otherwise the generic kernels are issued.
+static int run_forward(const Ctx &c, int l0, const float *in, int64_t ld_in, int K, float *y_pred, const Dense0Src *d0,
+                       TailFwdArgs &a, bool *tail) {
   const stdadk_mlp_desc *d = c.d;
   const stdadk_mlp_tensors *P = c.P;
   float *ws = c.ws;
@@ -714,21 +730,20 @@ static int run_forward(Ctx &c, int l0, const float *in, int64_t ld_in, int K, fl
   hipStream_t st = c.st;
   const int L = d->n_hidden, Q = d->out_dim;
   int rc;
-  c.mse_done = false;
+  *tail = false;
   STDADK_REQUIRE(P->W[L] && P->b[L], STDADK_E_ARG, "mlp_forward: output layer weights NULL");
-  if (tail_enabled() && !c.masks && L >= 1 && tail_supported(d, 1)) {
+  if (fused_tail(c)) {
     int l = l0;
-    TailFwdArgs a;
     a.d0.on = 0;
-    if (l == 0 && c.d0) {
+    if (l == 0 && d0) {
       // layer 0 inside the tail launch: features of a row tile in LDS, W0^T rows as the B operand
       static const float cals[3] = {1.000000f, 0.223477f, 0.654714f};  // st_interp.py:56-60
       const stdadk_basis_desc *b = c.basis;
       TailDense0 &z = a.d0;
       z.on = 1;
-      z.coords = c.d0_coords; z.t = c.d0_t; z.X = c.d0_X;
+      z.coords = d0->coords; z.t = d0->t; z.X = d0->X;
       z.p = b->p; z.Ks = (int)b->Ks; z.Kt = (int)b->Kt; z.basis = b->basis; z.cal = cals[b->basis];
-      z.s_centers = b->s_centers; z.s_bw = c.d0_bw; z.t_centers = b->t_centers; z.t_bw = b->t_bw;
+      z.s_centers = b->s_centers; z.s_bw = d0->s_bw; z.t_centers = b->t_centers; z.t_bw = b->t_bw;
       z.feats = c.save ? ws + pl.feats : nullptr; z.ldf = pl.ldf;
       z.W0T = P->W[0];
       z.L0 = tail_layer(c, 0);
@@ -756,11 +771,9 @@ static int run_forward(Ctx &c, int l0, const float *in, int64_t ld_in, int K, fl
     if (a.loss.y_cols == 0) a.loss.y_cols = Q;
     a.drop_p = c.dp; a.seed = c.seed; a.step_dev = c.step_dev;
     a.bf16 = c.bf16 ? 1 : 0;
-    c.cap32 = c.bf16 && a.d0.on != 0;
-    c.mse_done = c.mse_y != nullptr;
     { const char *e = getenv("STDADK_TAIL_STAMPS"); a.stamps = e ? (unsigned long long *)strtoull(e, nullptr, 0) : nullptr; }
-    if (c.fuse_tail && c.mse_done) { c.pend = a; c.pend_valid = true; return 0; }
-    return tail_forward(a, st);
+    *tail = true;
+    return 0;
   }
   for (int l = l0; l < L; ++l) {
     rc = generic_layer_forward(c, l, in, ld_in, K);
@@ -779,9 +792,145 @@ static int run_forward(Ctx &c, int l0, const float *in, int64_t ld_in, int K, fl
   return 0;
 }
 
-// Output layer backward, then hidden layers L-1 .. 0.  With `layer0_dense` false the first layer
-// stops after dZ_0 and its bias / LayerNorm gradients (dW0 is produced by the window kernels).
-static int run_backward(Ctx &c, const float *dY, const float *features, int64_t ldf, bool layer0_dense) {
+// ---- the fused-tail backward: (a) the row-local launch, (b) collect the weight-gradient jobs, (c) launch them.
+// Its callers write the composition out; between (a) and (b) dZ of every layer is final, so independent consumers
+// (the per-knot gather on an auxiliary stream) may fork there, and a window-path step merges the jobs of (b) into the
+// per-knot gather in place of (c) (close_step).
+
+// (a) One kernel for the whole activation-gradient path -- with the launches the forward held back in front of it:
+// tail_backward, tail_forward_backward or l1_tail_launch.  `fin` 2: the launch also clears the arrival counters of the
+// merged weight-gradient launch.  *n_part: its workgroups = the rows of every column-sum partial it leaves.
+static int tail_row_launch(const Ctx &c, const float *dY, bool layer0_dense, int fin, Held *h, int64_t *n_part) {
+  const stdadk_mlp_desc *d = c.d;
+  const stdadk_mlp_tensors *P = c.P, *G = c.G;
+  float *ws = c.ws;
+  const Plan &pl = c.pl;
+  const int L = d->n_hidden;
+  const bool held = h && h->tail_held;
+  // (a split backward call cannot know whether its forward ran the dense layer 0 inside the launch: every
+  //  bf16 backward on the materialising path with D <= TAIL_D0_MAX takes the 32-row cap the forward took)
+  const bool cap32 = held ? h->cap32 : (c.bf16 && layer0_dense && c.w0t && d->in_dim <= TAIL_D0_MAX);
+  *n_part = ceil_div(c.B, tail_rows(c.B, cap32));
+  TailBwdArgs a;
+  a.n_layers = L;
+  for (int l = 0; l < L; ++l) {
+    STDADK_REQUIRE(G->W[l] && G->b[l] && (!d->layernorm || (G->ln_g[l] && G->ln_b[l])), STDADK_E_ARG,
+                   "mlp_backward: layer %d grads NULL", l);
+    a.L[l] = tail_layer(c, l);
+    a.dZ[l] = ws + pl.dZl[l];
+    a.part[l] = ws + pl.partl[l];
+  }
+  STDADK_REQUIRE(G->W[L] && G->b[L], STDADK_E_ARG, "mlp_backward: output layer grads NULL");
+  a.B = (int)c.B; a.Wo = P->W[L]; a.Q = d->out_dim; a.dY = dY;
+  a.act_last = ws + pl.act[L - 1]; a.part_head = ws + pl.part;
+  a.layernorm = d->layernorm; a.drop_p = c.dp; a.seed = c.seed; a.step_dev = c.step_dev;
+  a.bf16 = c.bf16 ? 1 : 0;
+  a.zero_ints = fin == 2 ? reinterpret_cast<int *>(ws + pl.fin_cnt) : nullptr;
+  a.n_zero = fin == 2 ? FIN_TILES_MAX : 0;
+  { const char *e = getenv("STDADK_TAIL_BWD_STAMPS"); a.stamps = e ? (unsigned long long *)strtoull(e, nullptr, 0) : nullptr; }
+  if (!held) return tail_backward(a, c.st, cap32);
+  h->tail_held = false;
+  if (!h->l1_held) return tail_forward_backward(h->tail, a, c.st);
+  h->l1_held = false;
+  return l1_tail_launch(h->l1, c.basis->basis, d->layernorm != 0, h->tail, a, c.st);
+}
+
+// (b) ONE grouped launch for the dW products, ONE grouped launch for every fixed-order sum: collects them into `j` and
+// launches nothing -- except a product that cannot join the group, which goes out as a stand-alone GEMM right here.
+// `extra`: products with dZ_0 that ride along; `features` (materialising path, else NULL): dW0^T joins while it is a
+// split-K product; `fin` 2: the slabs of the products are summed by the merged launch itself, not by a reduce job.
+static int collect_dw_jobs(const Ctx &c, int64_t n_part, int fin, const ExtraProduct *extra, int n_extra,
+                           const float *features, int64_t ldf, DwJobs &j) {
+  const stdadk_mlp_desc *d = c.d;
+  const stdadk_mlp_tensors *G = c.G;
+  float *ws = c.ws;
+  const Plan &pl = c.pl;
+  const int64_t B = c.B;
+  const int L = d->n_hidden, Q = d->out_dim, hL = d->hidden[L - 1];
+  float *part = ws + pl.part, *slab = ws + pl.slab;
+  const float *dz0 = ws + pl.dZl[0];
+  GemmGroup &gg = j.gg;
+  ReduceGroup &rg = j.rg;
+  size_t slab_off = 0;
+  int rc;
+  auto add_reduce = [&](const float *src, float *dst, int n, int splits, int64_t stride) -> bool {
+    if (rg.n >= REDUCE_GROUP_MAX) return false;
+    ReduceJob &r = rg.job[rg.n++];
+    r.src = src; r.dst = dst; r.n = n; r.splits = splits; r.stride = stride;
+    return true;
+  };
+  // C[M][N] (contiguous) = A^T Bm, both operands stored [B rows][.]; falls back to a stand-alone GEMM
+  // (`bf`: a layer after the first under STDADK_FLAG_BF16 -- operands rounded to bf16 at the LDS boundary)
+  auto add_tn = [&](const float *A, int64_t lda, const float *Bm, int64_t ldb, int M, int N, float *C,
+                    bool bf = false) -> int {
+    if (gg.n < GEMM_GROUP_MAX && rg.n < REDUCE_GROUP_MAX && gemm_tn_groupable(A, lda, Bm, ldb)) {
+      GemmArgs &g = gg.job[gg.n++];
+      g.A = A; g.lda = lda; g.B = Bm; g.ldb = ldb; g.C = C; g.ldc = N; g.bias = nullptr;
+      g.M = M; g.N = N; g.K = (int)B;
+      g.bf16 = bf ? 1 : 0;
+      g.splits = gemm_pick_splits(M, N, (int)B, &g.kps, false);
+      g.slab = slab + slab_off; g.slab_stride = (int64_t)M * N;
+      slab_off += (size_t)g.splits * M * N;
+      if (fin != 2) add_reduce(g.slab, C, M * N, g.splits, g.slab_stride);   // 2: the last K slice to arrive sums
+      return 0;
+    }
+    j.all_grouped = false;
+    return gemm_run(A, lda, true, Bm, ldb, true, M, N, (int)B, nullptr, C, N, slab + slab_off, false, nullptr, c.st);
+  };
+  add_reduce(part, G->W[L], Q * hL, (int)n_part, (int64_t)Q * (hL + 1));
+  add_reduce(part + Q * hL, G->b[L], Q, (int)n_part, (int64_t)Q * (hL + 1));
+  for (int l = L - 1; l >= 0; --l) {
+    const int h = d->hidden[l];
+    const float *pp = ws + pl.partl[l];
+    if (d->layernorm) {
+      add_reduce(pp, G->ln_g[l], h, (int)n_part, (int64_t)3 * h);
+      add_reduce(pp + h, G->ln_b[l], h, (int)n_part, (int64_t)3 * h);
+    }
+    add_reduce(pp + 2 * h, G->b[l], h, (int)n_part, (int64_t)3 * h);
+    if (l == 0) break;
+    // dW_l[h][kin] = dZ_l^T act_{l-1}
+    rc = add_tn(ws + pl.dZl[l], h, ws + pl.act[l - 1], d->hidden[l - 1], h, d->hidden[l - 1], G->W[l], c.bf16);
+    if (rc) return rc;
+  }
+  for (int e = 0; e < n_extra; ++e) {
+    rc = add_tn(extra[e].A, extra[e].lda, dz0, d->hidden[0], extra[e].M, d->hidden[0], extra[e].C);
+    if (rc) return rc;
+  }
+  if (features && c.w0t) {
+    // materialising path with the (in,out) layout: while dW0^T = features^T dZ_0 is a split-K product
+    // (few tiles: small D) it joins the grouped launch and its slabs the grouped reduction -- two launches
+    // fewer than a stand-alone GEMM + slab sum; a D that fills the chip on its own keeps its direct GEMM
+    int kps;
+    const int h0 = d->hidden[0];
+    const int sp = gemm_pick_splits(d->in_dim, h0, (int)B, &kps, false);
+    if (sp > 1 && slab_off + (size_t)sp * d->in_dim * h0 <= pl.slab_floats) {
+      rc = add_tn(features, ldf, dz0, h0, d->in_dim, h0, G->W[0]);
+      if (rc) return rc;
+      j.dw0_in_group = true;
+    }
+  }
+  return 0;
+}
+
+// (c) the two grouped launches; materialising path (`features`): then dW0 as a stand-alone GEMM unless it joined the group
+static int launch_dw_jobs(const Ctx &c, DwJobs &j, const float *features, int64_t ldf) {
+  int rc = launch_gemm_tn_grouped(j.gg, c.st);
+  if (rc) return rc;
+  rc = launch_reduce_jobs(j.rg, c.st);
+  if (rc || !features || j.dw0_in_group) return rc;
+  const stdadk_mlp_desc *d = c.d;
+  const int h = d->hidden[0];
+  const float *dz0 = c.ws + c.pl.dZl[0];
+  float *slab = c.ws + c.pl.slab;
+  if (c.w0t)
+    return gemm_run(features, ldf, true, dz0, h, true, d->in_dim, h, (int)c.B, nullptr, c.G->W[0], h, slab, false, nullptr, c.st);
+  return gemm_run(dz0, h, true, features, ldf, true, h, d->in_dim, (int)c.B, nullptr, c.G->W[0], d->in_dim, slab, false, nullptr, c.st);
+}
+
+// The backward with the generic kernels (masks, widths the tail refuses, STDADK_NO_FUSED_TAIL): output layer, then
+// hidden layers L-1 .. 0.  With `layer0_dense` false the first layer stops after dZ_0 and its bias / LayerNorm
+// gradients (dW0 is produced by the window kernels).
+static int generic_backward(const Ctx &c, const float *dY, const float *features, int64_t ldf, bool layer0_dense) {
   const stdadk_mlp_desc *d = c.d;
   const stdadk_mlp_tensors *P = c.P, *G = c.G;
   float *ws = c.ws;
@@ -793,155 +942,6 @@ static int run_backward(Ctx &c, const float *dY, const float *features, int64_t 
   const int64_t nblk = ceil_div(B, rows);
   float *dA = ws + pl.dA, *dZ = ws + pl.dZ, *part = ws + pl.part, *slab = ws + pl.slab;
   int rc;
-  c.dz0 = dZ;
-
-  if (tail_enabled() && !c.masks && L >= 1 && tail_supported(d, 1)) {
-    // one kernel for the whole activation-gradient path, then reductions and the dW GEMMs
-    // (a split backward call cannot know whether its forward ran the dense layer 0 inside the launch: every
-    //  bf16 backward on the materialising path with D <= TAIL_D0_MAX takes the 32-row cap the forward took)
-    const bool cap32 = c.pend_valid ? c.cap32 : (c.bf16 && layer0_dense && c.w0t && d->in_dim <= TAIL_D0_MAX);
-    const int64_t nb16 = ceil_div(B, tail_rows(B, cap32));      // workgroups of the fused backward = partial rows
-    const int hL = d->hidden[L - 1];
-    TailBwdArgs a;
-    a.n_layers = L;
-    for (int l = 0; l < L; ++l) {
-      STDADK_REQUIRE(G->W[l] && G->b[l] && (!d->layernorm || (G->ln_g[l] && G->ln_b[l])), STDADK_E_ARG,
-                     "mlp_backward: layer %d grads NULL", l);
-      a.L[l] = tail_layer(c, l);
-      a.dZ[l] = ws + pl.dZl[l];
-      a.part[l] = ws + pl.partl[l];
-    }
-    STDADK_REQUIRE(G->W[L] && G->b[L], STDADK_E_ARG, "mlp_backward: output layer grads NULL");
-    a.B = (int)B; a.Wo = P->W[L]; a.Q = Q; a.dY = dY;
-    a.act_last = ws + pl.act[L - 1]; a.part_head = part;
-    a.layernorm = d->layernorm; a.drop_p = c.dp; a.seed = c.seed; a.step_dev = c.step_dev;
-    a.bf16 = c.bf16 ? 1 : 0;
-    // merged weight-gradient launch: with the reductions inside it (FinArgs; this tail launch clears the arrival
-    // counters) for large batches, where the K slices of a tile arrive spread out and the sums hide under the rest
-    // of the launch; below that the last slices arrive together at the end of the launch and their sums would
-    // extend it by more than the reductions launch costs (measured at 4 096 rows: 45 us against 27.6 + 7.7), so the
-    // launch only leaves the squared norms of its knot rows.  Environment STDADK_DW_FIN=0|1|2 forces a mode
-    // (0 = the round-2 path: reductions launch that also re-reads the knot rows for their norm).
-    c.fin = 0;
-    if (c.merge_dw && !layer0_dense && pl.fin_cap > 0) {
-      int64_t tiles = 0;
-      for (int l = 1; l < L; ++l) tiles += ceil_div(d->hidden[l], 64) * ceil_div(d->hidden[l - 1], 64);
-      for (int e = 0; e < c.n_extra; ++e) tiles += ceil_div(c.extra[e].M, 64) * ceil_div(d->hidden[0], 64);
-      const char *e = getenv("STDADK_DW_FIN");
-      c.fin = e ? atoi(e) : (B >= FIN_FULL_MIN_ROWS ? 2 : 1);
-      if (c.fin < 0 || c.fin > 2) c.fin = 1;
-      if (c.fin == 2 && tiles > FIN_TILES_MAX) c.fin = 1;
-    }
-    a.zero_ints = c.fin == 2 ? reinterpret_cast<int *>(ws + pl.fin_cnt) : nullptr;
-    a.n_zero = c.fin == 2 ? FIN_TILES_MAX : 0;
-    { const char *e = getenv("STDADK_TAIL_BWD_STAMPS"); a.stamps = e ? (unsigned long long *)strtoull(e, nullptr, 0) : nullptr; }
-    if (c.pend_valid) {
-      c.pend_valid = false;
-      if (c.l1_pend_valid) {
-        c.l1_pend_valid = false;
-        rc = l1_tail_launch(c.l1_pend, c.l1_basis, d->layernorm != 0, c.pend, a, st);
-      } else {
-        rc = tail_forward_backward(c.pend, a, st);
-      }
-    } else {
-      rc = tail_backward(a, st, cap32);
-    }
-    if (rc) return rc;
-    c.dz0 = ws + pl.dZl[0];
-    if (c.fork_after_dz) {       // dZ of every layer is final: independent consumers may start now
-      rc = c.fork_after_dz(c);
-      if (rc) return rc;
-    }
-    // ---- ONE grouped launch for the dW products, ONE grouped launch for every fixed-order sum
-    GemmGroup gg;
-    ReduceGroup rg;
-    size_t slab_off = 0;
-    auto add_reduce = [&](const float *src, float *dst, int n, int splits, int64_t stride) -> bool {
-      if (rg.n >= REDUCE_GROUP_MAX) return false;
-      ReduceJob &j = rg.job[rg.n++];
-      j.src = src; j.dst = dst; j.n = n; j.splits = splits; j.stride = stride;
-      return true;
-    };
-    // C[M][N] (contiguous) = A^T Bm, both operands stored [B rows][.]; falls back to a stand-alone GEMM
-    // (`bf`: a layer after the first under STDADK_FLAG_BF16 -- operands rounded to bf16 at the LDS boundary)
-    auto add_tn = [&](const float *A, int64_t lda, const float *Bm, int64_t ldb, int M, int N, float *C,
-                      bool bf = false) -> int {
-      if (gg.n < GEMM_GROUP_MAX && rg.n < REDUCE_GROUP_MAX && gemm_tn_groupable(A, lda, Bm, ldb)) {
-        GemmArgs &g = gg.job[gg.n++];
-        g.A = A; g.lda = lda; g.B = Bm; g.ldb = ldb; g.C = C; g.ldc = N; g.bias = nullptr;
-        g.M = M; g.N = N; g.K = (int)B;
-        g.bf16 = bf ? 1 : 0;
-        g.splits = gemm_pick_splits(M, N, (int)B, &g.kps, false);
-        g.slab = slab + slab_off; g.slab_stride = (int64_t)M * N;
-        slab_off += (size_t)g.splits * M * N;
-        if (c.fin != 2) add_reduce(g.slab, C, M * N, g.splits, g.slab_stride);   // 2: the last K slice to arrive sums
-        return 0;
-      }
-      c.all_grouped = false;
-      return gemm_run(A, lda, true, Bm, ldb, true, M, N, (int)B, nullptr, C, N, slab + slab_off, false, nullptr, st);
-    };
-    add_reduce(part, G->W[L], Q * hL, (int)nb16, (int64_t)Q * (hL + 1));
-    add_reduce(part + Q * hL, G->b[L], Q, (int)nb16, (int64_t)Q * (hL + 1));
-    for (int l = L - 1; l >= 0; --l) {
-      const int h = d->hidden[l];
-      const float *pp = ws + pl.partl[l];
-      if (d->layernorm) {
-        add_reduce(pp, G->ln_g[l], h, (int)nb16, (int64_t)3 * h);
-        add_reduce(pp + h, G->ln_b[l], h, (int)nb16, (int64_t)3 * h);
-      }
-      add_reduce(pp + 2 * h, G->b[l], h, (int)nb16, (int64_t)3 * h);
-      if (l == 0) break;
-      // dW_l[h][kin] = dZ_l^T act_{l-1}
-      rc = add_tn(ws + pl.dZl[l], h, ws + pl.act[l - 1], d->hidden[l - 1], h, d->hidden[l - 1], G->W[l], c.bf16);
-      if (rc) return rc;
-    }
-    for (int e = 0; e < c.n_extra; ++e) {
-      rc = add_tn(c.extra[e].A, c.extra[e].lda, c.dz0, d->hidden[0], c.extra[e].M, d->hidden[0], c.extra[e].C);
-      if (rc) return rc;
-    }
-    c.n_extra = 0;     // consumed
-    bool dw0_in_group = false;
-    if (layer0_dense && c.w0t) {
-      // materialising path with the (in,out) layout: while dW0^T = features^T dZ_0 is a split-K product
-      // (few tiles: small D) it joins the grouped launch and its slabs the grouped reduction -- two launches
-      // fewer than a stand-alone GEMM + slab sum; a D that fills the chip on its own keeps its direct GEMM
-      int kps;
-      const int h0 = d->hidden[0];
-      const int sp = gemm_pick_splits(d->in_dim, h0, (int)B, &kps, false);
-      if (sp > 1 && slab_off + (size_t)sp * d->in_dim * h0 <= pl.slab_floats) {
-        rc = add_tn(features, ldf, c.dz0, h0, d->in_dim, h0, G->W[0]);
-        if (rc) return rc;
-        dw0_in_group = true;
-      }
-    }
-    if (c.merge_dw && !layer0_dense) {
-      // window path: the caller issues these products together with the per-knot gather of dW0^T as one
-      // launch, then the reductions (step_backward)
-      c.gg_pend = gg; c.rg_pend = rg; c.dw_pend = true;
-      return 0;
-    }
-    rc = launch_gemm_tn_grouped(gg, st);
-    if (rc) return rc;
-    if (c.gradsq && c.all_grouped && layer0_dense && dw0_in_group && reduce_jobs_block_count(rg) > 0 &&
-        reduce_jobs_block_count(rg) <= STDADK_GRADSQ_PARTS) {
-      // one-call step: every gradient of the step is an output of this reductions launch, which then also
-      // leaves the squared-norm partials for the clip (no region beside them)
-      rg.sq_parts = c.gradsq; rg.step_inc = c.step_inc;
-      c.gradsq_done = true; c.gradsq_out = c.gradsq; c.gradsq_n = reduce_jobs_block_count(rg);
-    }
-    rc = launch_reduce_jobs(rg, st);
-    if (rc) return rc;
-    if (layer0_dense && !dw0_in_group) {
-      const int h = d->hidden[0];
-      if (c.w0t)
-        rc = gemm_run(features, ldf, true, c.dz0, h, true, d->in_dim, h, (int)B, nullptr, G->W[0], h, slab, false, nullptr, st);
-      else
-        rc = gemm_run(c.dz0, h, true, features, ldf, true, h, d->in_dim, (int)B, nullptr, G->W[0], d->in_dim, slab, false, nullptr, st);
-      if (rc) return rc;
-    }
-    return 0;
-  }
-
   const float *aL = L > 0 ? ws + pl.act[L - 1] : features;
   const int64_t ldaL = L > 0 ? d->hidden[L - 1] : ldf;
   const int hL = L > 0 ? d->hidden[L - 1] : d->in_dim;
@@ -1099,9 +1099,9 @@ static BinBuffers plan_bins(float *ws, const Plan &pl) {
 }
 
 // scattered knots: bin the knots of every level into cells (knot_bins) and point the forward at the lists
-static int scattered_bins(Ctx &c, L1FwdArgs &a) {
+static int scattered_bins(const Ctx &c, L1FwdArgs &a) {
   const Plan &pl = c.pl;
-  const stdadk_basis_desc *b = c.basis_in;
+  const stdadk_basis_desc *b = c.basis;
   int *kcs = (int *)(c.ws + pl.kcs), *kperm = (int *)(c.ws + pl.kperm), *ktmp = (int *)(c.ws + pl.kperm_tmp);
   float *reach = c.ws + pl.reach;
   int rc;
@@ -1116,10 +1116,12 @@ static int scattered_bins(Ctx &c, L1FwdArgs &a) {
   return 0;
 }
 
-// feature build + layer 0 for the window path (sorted order); returns with act[0] ready
-static int window_layer0_forward(Ctx &c, const stdadk_basis_desc *b, const float *coords, const float *t,
-                                 const float *X, const float *y) {
+// Window path, in front of layer 0: bins the batch (and the knots, where they move) and fills the arguments of the
+// feature build + layer 0 launch (sorted order) into `a`; the caller issues it (l1_window_forward) or holds it
+static int window_layer0_forward(const Ctx &c, const float *coords, const float *t, const float *X, const float *y,
+                                 L1FwdArgs &a) {
   const Plan &pl = c.pl;
+  const stdadk_basis_desc *b = c.basis;
   BinBuffers bb = plan_bins(c.ws, pl);
   int rc = 0;
   if (!c.prebinned) {
@@ -1128,7 +1130,6 @@ static int window_layer0_forward(Ctx &c, const stdadk_basis_desc *b, const float
                  c.idx);
     if (rc) return rc;
   }
-  L1FwdArgs a;
   a.g = make_grid(b, c.scattered);
   a.halo = nullptr;
   if (c.scattered) {
@@ -1155,14 +1156,7 @@ static int window_layer0_forward(Ctx &c, const stdadk_basis_desc *b, const float
   a.drop_p = c.dp; a.seed = c.seed; a.step_dev = c.step_dev;
   a.rows_per_wg = 0; a.n_wg = 0;
   STDADK_REQUIRE(a.W0T && a.b0, STDADK_E_ARG, "window forward: layer 0 weights NULL");
-  // fused training step at <= 16 rows per CU: park this launch too; run_backward issues layer 0, the tail
-  // forward, the loss and the tail backward as ONE kernel (every one of them is row-local)
-  if (c.fuse_tail && c.mse_y && !c.masks && tail_enabled() && c.d->n_hidden >= 1 && tail_supported(c.d, 1) &&
-      tail_rows(c.B) == 16 && l1_tail_supported(c.B, a.H) && getenv("STDADK_NO_L1_TAIL") == nullptr) {
-    c.l1_pend = a; c.l1_pend_valid = true; c.l1_basis = b->basis;
-    return 0;
-  }
-  return l1_window_forward(a, b->basis, c.d->layernorm != 0, c.st);
+  return 0;
 }
 
 // The opener of the two stdadk_mlp_*_f32 doors: plans and fills `c`; false = workspace too small (worded by the door)
@@ -1205,7 +1199,11 @@ extern "C" int stdadk_mlp_forward_f32(const stdadk_mlp_desc *d, const stdadk_mlp
   STDADK_REQUIRE(open_mlp(c, d, B, workspace, workspace_bytes, P, nullptr, stream, training != 0, drop_seed, drop_mask),
                  STDADK_E_WORKSPACE, "mlp_forward: workspace %zu < %zu bytes", workspace_bytes,
                  c.pl.total_floats * sizeof(float));
-  return run_forward(c, 0, features, ldf, d->in_dim, y_pred);
+  TailFwdArgs tail;
+  bool is_tail;
+  rc = run_forward(c, 0, features, ldf, d->in_dim, y_pred, nullptr, tail, &is_tail);
+  if (rc || !is_tail) return rc;
+  return tail_forward(tail, c.st);
 }
 
 extern "C" int stdadk_mlp_backward_f32(const stdadk_mlp_desc *d, const stdadk_mlp_tensors *P,
@@ -1221,7 +1219,14 @@ extern "C" int stdadk_mlp_backward_f32(const stdadk_mlp_desc *d, const stdadk_ml
   Ctx c;
   STDADK_REQUIRE(open_mlp(c, d, B, workspace, workspace_bytes, P, G, stream, true, drop_seed, drop_mask),
                  STDADK_E_WORKSPACE, "mlp_backward: workspace too small");
-  return run_backward(c, dY, features, ldf, true);
+  if (!fused_tail(c)) return generic_backward(c, dY, features, ldf, true);
+  int64_t n_part;
+  DwJobs jobs;
+  rc = tail_row_launch(c, dY, true, 0, nullptr, &n_part);
+  if (rc) return rc;
+  rc = collect_dw_jobs(c, n_part, 0, nullptr, 0, features, ldf, jobs);
+  if (rc) return rc;
+  return launch_dw_jobs(c, jobs, features, ldf);
 }
 
 extern "C" int stdadk_mse_f32(const float *y_pred, const float *y, int64_t n, float grad_scale,
@@ -1257,7 +1262,7 @@ extern "C" size_t stdadk_step_workspace_bytes(const stdadk_basis_desc *b, const 
 // The one opener of a step-level Ctx: validates descriptors, batch size, workspace and flags, plans, fills `c` (`training`
 // false: no dropout, nothing kept for a backward).  P and G are stored unchecked: each door refuses NULLs in its own words.
 static int open_step(Ctx &c, const stdadk_basis_desc *b, const stdadk_mlp_desc *d, int64_t B, void *workspace,
-                     size_t workspace_bytes, int32_t flags, bool *window, const stdadk_mlp_tensors *P,
+                     size_t workspace_bytes, int32_t flags, const stdadk_mlp_tensors *P,
                      const stdadk_mlp_tensors *G, stdadk_stream_t stream, bool training, uint64_t drop_seed = 0,
                      const int32_t *step_dev = nullptr) {
   int rc = check_desc(d);
@@ -1266,20 +1271,20 @@ static int open_step(Ctx &c, const stdadk_basis_desc *b, const stdadk_mlp_desc *
   if (rc) return rc;
   STDADK_REQUIRE(B > 0 && B < (1ll << 31), STDADK_E_ARG, "step: bad B");
   STDADK_REQUIRE(workspace && aligned16(workspace), STDADK_E_ALIGN, "step: workspace NULL or not 16-byte aligned");
-  *window = want_window(b, d, flags);
+  c.window = want_window(b, d, flags);
   rc = check_levels(b, flags);
   if (rc) return rc;
-  c.scattered = *window && is_scattered(b, flags);
+  c.scattered = c.window && is_scattered(b, flags);
   plan_step(b, d, B, flags, &c.pl);
   c.log_bw = (flags & STDADK_FLAG_LOG_BW) != 0;
   c.bf16 = (flags & STDADK_FLAG_BF16) != 0;
-  STDADK_REQUIRE(!c.bf16 || (tail_enabled() && d->n_hidden >= 1 && tail_supported(d, 1)), STDADK_E_ARG,
+  STDADK_REQUIRE(!c.bf16 || fused_tail(d), STDADK_E_ARG,
                  "step: STDADK_FLAG_BF16 needs the fused tail kernels (hidden widths multiples of 16 up to %d, out_dim <= %d)",
                  TAIL_MAX_W, TAIL_MAXQ);
   c.pack = (flags & STDADK_FLAG_PACK_F32) != 0;
   if (c.pack) {
     STDADK_REQUIRE(!c.bf16, STDADK_E_ARG, "step: STDADK_FLAG_PACK_F32 and STDADK_FLAG_BF16 exclude each other");
-    STDADK_REQUIRE(tail_enabled() && d->n_hidden >= 1 && tail_supported(d, 1), STDADK_E_ARG,
+    STDADK_REQUIRE(fused_tail(d), STDADK_E_ARG,
                    "step: STDADK_FLAG_PACK_F32 needs the fused tail kernels (hidden widths multiples of 16 up to %d, "
                    "out_dim <= %d)", TAIL_MAX_W, TAIL_MAXQ);
     for (int l = 1; P && l < d->n_hidden; ++l) {
@@ -1293,90 +1298,101 @@ static int open_step(Ctx &c, const stdadk_basis_desc *b, const stdadk_mlp_desc *
   STDADK_REQUIRE(workspace_bytes >= c.pl.total_floats * sizeof(float), STDADK_E_WORKSPACE,
                  "step: workspace %zu < %zu bytes", workspace_bytes, c.pl.total_floats * sizeof(float));
   c.d = d; c.P = P; c.G = G; c.ws = (float *)workspace; c.st = (hipStream_t)stream; c.B = B;
-  c.basis_in = b; c.w0t = (flags & STDADK_FLAG_W0_T) != 0;
+  c.basis = b; c.w0t = (flags & STDADK_FLAG_W0_T) != 0;
   c.dp = training ? d->dropout_p : 0.f; c.seed = drop_seed; c.step_dev = step_dev; c.save = training;
-  c.prebinned = *window && (flags & STDADK_FLAG_PREBINNED) != 0;
-  STDADK_REQUIRE(*window || !(flags & STDADK_FLAG_PREBINNED), STDADK_E_ARG,
+  c.prebinned = c.window && (flags & STDADK_FLAG_PREBINNED) != 0;
+  STDADK_REQUIRE(c.window || !(flags & STDADK_FLAG_PREBINNED), STDADK_E_ARG,
                  "step: STDADK_FLAG_PREBINNED needs the window path");
   return 0;
 }
 
 // dW0^T spatial rows (window path): every knot row by the wave that owns it
-static int window_dw0(Ctx &c, hipStream_t st, GemmGroup *with_products = nullptr, const FinArgs *fin = nullptr,
-                      ReduceGroup *tall = nullptr, int *n_slots = nullptr, int slot_cap = 0) {
-  const stdadk_basis_desc *b = c.basis;
+static L1BwdArgs window_gather_args(const Ctx &c) {
   float *ws = c.ws;
   L1BwdArgs a;
-  a.g = make_grid(b, c.scattered);
+  a.g = make_grid(c.basis, c.scattered);
   a.xs = ws + c.pl.xs; a.ys = ws + c.pl.ys;
   a.cell_start = (const int *)(ws + c.pl.cell_start);
   a.G = c.pl.G; a.B = (int)c.B; a.H = c.d->hidden[0];
-  a.dZ = c.dz0; a.dW0T = c.G->W[0];
+  a.dZ = layer0_dz(c); a.dW0T = c.G->W[0];
   a.W0T = nullptr; a.kpart = nullptr;
   if (c.log_bw) {      // learnable knots: the same pass also yields the raw knot gradients
     a.g.bw = ws + c.pl.bw_exp;
     a.W0T = c.P->W[0];
     a.kpart = ws + c.pl.kpart;
   }
-  if (with_products && fin) {
-    int need = dw_all_knot_blocks(a);
-    if (fin->cnt) {
-      STDADK_REQUIRE(tall && tall->n > 0, STDADK_E_ARG, "dw_all: finishing work without its reduce table");
-      for (int j = 0; j < with_products->n; ++j)
-        need += (int)(ceil_div(with_products->job[j].M, 64) * ceil_div(with_products->job[j].N, 64));
-      need += reduce_jobs_block_count(*tall);
-    }
-    STDADK_REQUIRE(need <= slot_cap, STDADK_E_WORKSPACE, "dw_all: %d squared-norm slots, the plan holds %d", need,
-                   slot_cap);
-    const int rc = launch_dw_all(*with_products, a, b->basis, st, fin, tall, n_slots, c.bin_next);
-    if (rc == 0 && c.bin_next) c.bin_next_done = true;
-    return rc;
+  return a;
+}
+// ... as a launch of its own
+static int window_gather(const Ctx &c, hipStream_t st) { return l1_window_backward(window_gather_args(c), c.basis->basis, st); }
+// ... merged with the grouped dW products of `j` (dw_all.hip), which also bins the announced next batch; `fin`: with
+// finishing work (FinArgs) -- the squared-norm slots, *n_slots of them out of `slot_cap`, and with fin->cnt the sums of
+// `j.rg` as well
+static int window_dw_all(const Ctx &c, DwJobs &j, const FinArgs *fin = nullptr, int *n_slots = nullptr, int slot_cap = 0) {
+  const L1BwdArgs a = window_gather_args(c);
+  if (!fin) return launch_dw_all(j.gg, a, c.basis->basis, c.st, nullptr, nullptr, nullptr, c.ride->bin_next);
+  int need = dw_all_knot_blocks(a);
+  if (fin->cnt) {
+    STDADK_REQUIRE(j.rg.n > 0, STDADK_E_ARG, "dw_all: finishing work without its reduce table");
+    for (int i = 0; i < j.gg.n; ++i) need += (int)(ceil_div(j.gg.job[i].M, 64) * ceil_div(j.gg.job[i].N, 64));
+    need += reduce_jobs_block_count(j.rg);
   }
-  if (with_products) {
-    const int rc = launch_dw_all(*with_products, a, b->basis, st, nullptr, nullptr, nullptr, c.bin_next);
-    if (rc == 0 && c.bin_next) c.bin_next_done = true;
-    return rc;
-  }
-  return l1_window_backward(a, b->basis, st);
+  STDADK_REQUIRE(need <= slot_cap, STDADK_E_WORKSPACE, "dw_all: %d squared-norm slots, the plan holds %d", need, slot_cap);
+  return launch_dw_all(j.gg, a, c.basis->basis, c.st, fin, fin->cnt ? &j.rg : nullptr, n_slots, c.ride->bin_next);
 }
 
 // forward of one batch; training != 0 keeps everything backward needs in the workspace
 // (window path: `y`, when given, is carried into sorted order next to the observations, and the
-//  predictions stay in sorted order in the plan's ypred buffer; y_pred NULL skips the un-permute)
-static int step_forward(Ctx &c, const stdadk_basis_desc *b, bool window, const float *coords, const float *t,
-                        const float *X, const float *y, float *y_pred, stdadk_stream_t stream) {
+//  predictions stay in sorted order in the plan's ypred buffer; y_pred NULL skips the un-permute).
+// `hold` (training step): the row-local launches are filled into it and, where the step's backward can run them inside
+// its own row-local launch, left to it (tail_held / l1_held); NULL: everything is issued here.
+static int step_forward(const Ctx &c, const float *coords, const float *t, const float *X, const float *y, float *y_pred,
+                        Held *hold) {
   const stdadk_mlp_desc *d = c.d;
+  const stdadk_basis_desc *b = c.basis;
   float *ws = c.ws;
+  Held local;
+  Held &h = hold ? *hold : local;
+  // one launch for the forward and backward chains of the tail when the loss is fused into it
+  const bool can_hold = hold && c.fuse_tail && c.mse_y && fused_tail(c);
+  bool is_tail;
   int rc;
-  if (window) {
-    rc = window_layer0_forward(c, b, coords, t, X, y);
+  if (c.window) {
+    rc = window_layer0_forward(c, coords, t, X, y, h.l1);
     if (rc) return rc;
-    rc = run_forward(c, 1, ws + c.pl.act[0], d->hidden[0], d->hidden[0], ws + c.pl.ypred);
-    if (rc) return rc;
-    if (!y_pred) return 0;
-    return unpermute_rows(ws + c.pl.ypred, (const int *)(ws + c.pl.perm), (int)c.B, d->out_dim, y_pred, c.st);
+    // at <= 16 rows per CU layer 0 is held too: layer 0, the tail forward, the loss and the tail backward as ONE kernel
+    h.l1_held = can_hold && tail_rows(c.B) == 16 && l1_tail_supported(c.B, h.l1.H) && getenv("STDADK_NO_L1_TAIL") == nullptr;
+    if (!h.l1_held) {
+      rc = l1_window_forward(h.l1, b->basis, d->layernorm != 0, c.st);
+      if (rc) return rc;
+    }
+    rc = run_forward(c, 1, ws + c.pl.act[0], d->hidden[0], d->hidden[0], ws + c.pl.ypred, nullptr, h.tail, &is_tail);
+  } else {
+    Dense0Src d0 = {coords, t, X, b->s_bw};
+    if (c.log_bw && b->Ks > 0) {        // bandwidth = exp(log_bandwidth)  (st_interp.py:146-148)
+      rc = launch_exp(b->s_bw, b->Ks, ws + c.pl.bw_exp, c.st);
+      if (rc) return rc;
+      d0.s_bw = ws + c.pl.bw_exp;
+    }
+    if (dense0_in_tail(c)) {
+      rc = run_forward(c, 0, nullptr, 0, d->in_dim, y_pred, &d0, h.tail, &is_tail);
+    } else {
+      rc = stdadk_rbf_build_f32(coords, t, X, c.B, b->p, b->s_centers, d0.s_bw, b->Ks, b->basis, b->t_centers,
+                                b->t_bw, b->Kt, ws + c.pl.feats, c.pl.ldf, (stdadk_stream_t)c.st);
+      if (rc) return rc;
+      rc = run_forward(c, 0, ws + c.pl.feats, c.pl.ldf, d->in_dim, y_pred, nullptr, h.tail, &is_tail);
+    }
   }
-  const float *s_bw = b->s_bw;
-  if (c.log_bw && b->Ks > 0) {        // bandwidth = exp(log_bandwidth)  (st_interp.py:146-148)
-    rc = launch_exp(b->s_bw, b->Ks, ws + c.pl.bw_exp, c.st);
-    if (rc) return rc;
-    s_bw = ws + c.pl.bw_exp;
-  }
-  // small feature width, (in,out) first weight, fused tail available: features and layer 0 inside the tail
-  // launch (environment STDADK_NO_DENSE0_TAIL=1: the separate kernels, diagnostic)
-  c.d0 = c.w0t && d->in_dim <= TAIL_D0_MAX && d->n_hidden >= 1 && tail_enabled() && !c.masks && tail_supported(d, 1) &&
-         c.pl.ldf == ((d->in_dim + 31) & ~31) && getenv("STDADK_NO_DENSE0_TAIL") == nullptr;
-  if (c.d0) {
-    c.basis = b;
-    c.d0_coords = coords; c.d0_t = t; c.d0_X = X; c.d0_bw = s_bw;
-    rc = run_forward(c, 0, nullptr, 0, d->in_dim, y_pred);
-    c.d0 = false;
-    return rc;
-  }
-  rc = stdadk_rbf_build_f32(coords, t, X, c.B, b->p, b->s_centers, s_bw, b->Ks, b->basis, b->t_centers,
-                            b->t_bw, b->Kt, ws + c.pl.feats, c.pl.ldf, stream);
   if (rc) return rc;
-  return run_forward(c, 0, ws + c.pl.feats, c.pl.ldf, d->in_dim, y_pred);
+  h.loss_fused = is_tail && c.mse_y != nullptr;
+  h.cap32 = is_tail && c.bf16 && h.tail.d0.on != 0;
+  h.tail_held = is_tail && can_hold;
+  if (is_tail && !h.tail_held) {
+    rc = tail_forward(h.tail, c.st);
+    if (rc) return rc;
+  }
+  if (!c.window || !y_pred) return 0;
+  return unpermute_rows(ws + c.pl.ypred, (const int *)(ws + c.pl.perm), (int)c.B, d->out_dim, y_pred, c.st);
 }
 
 // the knot penalties' checks, shared by the doors that take them
@@ -1402,13 +1418,12 @@ static KnotFinishArgs knot_finish_args(const Ctx &c, const stdadk_basis_desc *b,
   return fa;
 }
 
-// materialising path: the raw per-slab knot sums from dZ of layer 0, which run_backward left in the workspace
+// materialising path: the raw per-slab knot sums from dZ of layer 0, which the backward left in the workspace
 static int knot_dense_sums(const Ctx &c, const stdadk_basis_desc *b, const stdadk_mlp_tensors *P, const float *coords) {
   const stdadk_mlp_desc *d = c.d;
   float *ws = c.ws;
   const int H = d->hidden[0];
-  // where run_backward left dZ of layer 0 (fused tail: its per-layer buffer; generic: the shared one)
-  const float *dz0 = (tail_enabled() && tail_supported(d, 1)) ? ws + c.pl.dZl[0] : ws + c.pl.dZ;
+  const float *dz0 = layer0_dz(c);
   // dFeat = dZ0 . W0 over ALL feature columns, into the (now free) feature buffer
   float *dfeat = ws + c.pl.feats;
   int rc;
@@ -1426,30 +1441,143 @@ static int knot_dense_sums(const Ctx &c, const stdadk_basis_desc *b, const stdad
   return launch_knot_grad(ka, c.st);
 }
 
-// The reductions launch that is pending behind the merged dW launch of a window-path step -- or, in a one-call
-// learnable step, the finishing launch that takes its place and carries its jobs (the per-knot sums are final once
-// the dW launch is).  Mode 0's 256 region workgroups stay in a launch of their own there.
-static int launch_step_reductions(Ctx &c, const stdadk_basis_desc *b, ReduceGroup &rg) {
-  if (!c.knot_ride) return launch_reduce_jobs(rg, c.st);
-  if (rg.sq_region_parts) {
-    ReduceGroup region;
-    region.sq_region_parts = rg.sq_region_parts; region.sq_src = rg.sq_src; region.sq_n = rg.sq_n;
-    rg.sq_region_parts = nullptr; rg.sq_src = nullptr; rg.sq_n = 0;
-    const int rc = launch_reduce_jobs(region, c.st);
+// "The merged weight-gradient launch applies": window path behind the fused tail, no auxiliary stream to fork the per-knot
+// gather onto (environment STDADK_NO_DW_ALL=1: the separate launches, diagnostic)
+static bool merged_dw(const Ctx &c) { return c.window && !c.aux && fused_tail(c) && getenv("STDADK_NO_DW_ALL") == nullptr; }
+
+// The finishing mode of the merged weight-gradient launch (FinArgs), decided before the row-local launch, which clears the
+// arrival counters for mode 2.  2: the launch also does the reductions -- for large batches, where the K slices of a tile
+// arrive spread out and the sums hide under the rest of the launch; below that the last slices arrive together at the
+// end of the launch and their sums would extend it by more than the reductions launch costs (measured at 4 096 rows:
+// 45 us against 27.6 + 7.7), so 1: the launch only leaves the squared norms of its knot rows.  Environment
+// STDADK_DW_FIN=0|1|2 forces a mode (0 = the round-2 path: reductions launch that also re-reads the knot rows for their norm).
+static int finishing_mode(const Ctx &c) {
+  if (c.pl.fin_cap <= 0) return 0;
+  const stdadk_mlp_desc *d = c.d;
+  const int64_t t0 = ceil_div(d->hidden[0], 64);
+  int64_t tiles = ceil_div(c.basis->Kt, 64) * t0 + (c.basis->p > 0 ? ceil_div(c.basis->p, 64) * t0 : 0);
+  for (int l = 1; l < d->n_hidden; ++l) tiles += ceil_div(d->hidden[l], 64) * ceil_div(d->hidden[l - 1], 64);
+  const char *e = getenv("STDADK_DW_FIN");
+  int fin = e ? atoi(e) : (c.B >= FIN_FULL_MIN_ROWS ? 2 : 1);
+  if (fin < 0 || fin > 2) fin = 1;
+  if (fin == 2 && tiles > FIN_TILES_MAX) fin = 1;
+  return fin;
+}
+
+// Closes the weight gradients of a step behind the dZ launch: issues whatever is still to launch of `jobs` (NULL: the
+// generic kernels left nothing pending) and of the per-knot gather, lets the step's riders (c.ride) ride, and says in
+// `out` where the clip-norm partials went and whether the next batch is binned.  `merged`: merged_dw(c), which `fin`
+// was decided from.  Who leaves the partials also advances the step counter (ride.step_inc); when nobody
+// does (out.sq_parts NULL) the caller's own norm pass or stdadk_step_advance does.  A learnable one-call step
+// (ride.knots) passes no step_inc: its finishing launch (step_finish.hip) is in every case and advances finish_inc.
+//
+//   case                                    launches                                    partials + step_inc ride in
+//   merged dW launch, finishing mode 2      dw_all                                      dw_all (its slots)
+//   merged dW launch, finishing mode 1      dw_all, reductions                          dw_all (knot rows) + reductions
+//   merged dW launch, finishing mode 0      dw_all, reductions                          reductions (+ its 256 region workgroups)
+//   separate launches (auxiliary stream,    grouped GEMMs, reductions, dW0 GEMM /       reductions, on the materialising path when
+//     STDADK_NO_DW_ALL, materialising path)   per-knot gather (or its join)               every gradient is its output; else nobody
+//   learnable, reductions pending (0 / 1)   the finishing launch in the reductions' place, carrying their jobs (mode 0's
+//                                           region workgroups stay a reductions launch of their own)
+//   learnable, nothing pending (mode 2,     the finishing launch with zero reduce workgroups, last
+//     separate launches, generic kernels)
+static int close_step(const Ctx &c, DwJobs *jobs, bool merged, int fin, const float *coords, StepOut &out) {
+  const StepRide &r = *c.ride;
+  float *ws = c.ws;
+  const stdadk_basis_desc *b = c.basis;
+  const bool forked = jobs && c.aux;      // window path: the per-knot gather already runs on the auxiliary stream
+  const bool sq = jobs && r.gradsq_parts && jobs->all_grouped;
+  const int nrb = jobs ? reduce_jobs_block_count(jobs->rg) : 0;
+  bool reductions_pending = false;
+  int rc = 0;
+  if (merged && fin == 2) {
+    // products, per-knot gather, every fixed-order sum and the squared-norm partials: ONE launch
+    FinArgs f;
+    f.cnt = reinterpret_cast<int *>(ws + c.pl.fin_cnt);
+    f.slots = sq ? ws + c.pl.fin_slots : nullptr;
+    f.step_inc = sq ? r.step_inc : nullptr;
+    int n_slots = 0;
+    rc = window_dw_all(c, *jobs, &f, &n_slots, c.pl.fin_cap);
+    if (sq) { out.sq_parts = f.slots; out.sq_n = n_slots; }
+  } else if (merged && fin == 1 && sq && nrb > 0) {
+    // the knot workgroups leave the squares of the rows they write (no second pass over dW0^T), the reductions
+    // launch adds the partials of what it writes behind them
+    FinArgs f;
+    f.slots = ws + c.pl.fin_slots;
+    int n_knot = 0;
+    rc = window_dw_all(c, *jobs, &f, &n_knot, c.pl.fin_cap - nrb);
+    jobs->rg.sq_parts = f.slots + n_knot;
+    jobs->rg.step_inc = r.step_inc;
+    out.sq_parts = f.slots; out.sq_n = n_knot + nrb;
+    reductions_pending = true;
+  } else if (merged) {
+    rc = window_dw_all(c, *jobs);
+    if (rc) return rc;
+    if (sq && nrb > 0 && nrb <= STDADK_GRADSQ_PARTS - 256) {
+      // every gradient of the step is either an output of the reductions launch or a spatial row of dW0^T (final
+      // after the launch above): their squared norm comes out of the same launch
+      ReduceGroup own;
+      ReduceGroup &region = r.knots ? own : jobs->rg;
+      region.sq_region_parts = r.gradsq_parts;
+      region.sq_src = c.G->W[0] + (size_t)b->p * c.d->hidden[0];
+      region.sq_n = (int64_t)b->Ks * c.d->hidden[0];
+      if (r.knots) rc = launch_reduce_jobs(region, c.st);
+      jobs->rg.sq_parts = r.gradsq_parts + 256;
+      jobs->rg.step_inc = r.step_inc;
+      out.sq_parts = r.gradsq_parts; out.sq_n = 256 + nrb;
+    }
+    reductions_pending = true;
+  } else if (jobs) {
+    if (sq && !c.window && jobs->dw0_in_group && nrb > 0 && nrb <= STDADK_GRADSQ_PARTS) {
+      // one-call step: every gradient of the step is an output of this reductions launch, which then also
+      // leaves the squared-norm partials for the clip (no region beside them)
+      jobs->rg.sq_parts = r.gradsq_parts; jobs->rg.step_inc = r.step_inc;
+      out.sq_parts = r.gradsq_parts; out.sq_n = nrb;
+    }
+    rc = launch_dw_jobs(c, *jobs, c.window ? nullptr : ws + c.pl.feats, c.pl.ldf);
+  }
+  if (rc) return rc;
+  if (merged) out.binned_next = r.bin_next != nullptr;
+  if (c.window && !merged) {
+    rc = forked ? stream_depends(c.st, c.aux, 3) : window_gather(c, c.st);      // join | the gather, last
     if (rc) return rc;
   }
-  const KnotFinishArgs fa = knot_finish_args(c, b, c.knot_kt, c.knot_dc, c.knot_dlb, c.mse_loss);
-  c.knot_done = true;
-  return launch_step_finish(rg, fa, c.knot_sq, c.knot_inc, c.st);
+  if (reductions_pending && !r.knots) return launch_reduce_jobs(jobs->rg, c.st);
+  if (!r.knots) return 0;
+  // the per-knot sums are final: once the dW launch is (window path), or from dZ of layer 0 here (materialising path)
+  if (!c.window) {
+    rc = knot_dense_sums(c, b, c.P, coords);
+    if (rc) return rc;
+  }
+  ReduceGroup none;
+  return launch_step_finish(reductions_pending ? jobs->rg : none, knot_finish_args(c, b, r.kt, r.d_centers, r.d_log_bw, c.mse_loss),
+                            r.knot_sq, r.finish_inc, c.st);
 }
 
 // backward of the batch whose training forward left its state in the workspace; dY in caller order
-// (`dY_sorted`: window path only — dY is already the plan's dY buffer in sorted order)
-static int step_backward(Ctx &c, const stdadk_basis_desc *b, bool window, const float *dY, bool dY_sorted) {
+// (`dY_sorted`: window path only — dY is already the plan's dY buffer in sorted order); `h`: what that forward held
+// back (NULL: nothing, a split call); `coords`: the batch's, for the knot sums of a learnable one-call step on the
+// materialising path
+static int step_backward(const Ctx &c, const float *dY, bool dY_sorted, Held *h, const float *coords, StepOut &out) {
   const stdadk_mlp_desc *d = c.d;
+  const stdadk_basis_desc *b = c.basis;
   float *ws = c.ws;
+  const bool fused = fused_tail(c);
+  int64_t n_part;
+  DwJobs jobs;
   int rc;
-  if (!window) return run_backward(c, dY, ws + c.pl.feats, c.pl.ldf, true);
+  if (!c.window) {
+    if (!fused) {
+      rc = generic_backward(c, dY, ws + c.pl.feats, c.pl.ldf, true);
+      if (rc) return rc;
+      return close_step(c, nullptr, false, 0, coords, out);
+    }
+    rc = tail_row_launch(c, dY, true, 0, h, &n_part);
+    if (rc) return rc;
+    rc = collect_dw_jobs(c, n_part, 0, nullptr, 0, ws + c.pl.feats, c.pl.ldf, jobs);
+    if (rc) return rc;
+    return close_step(c, &jobs, false, 0, coords, out);
+  }
   const int H = d->hidden[0], Q = d->out_dim;
   if (!dY_sorted) {   // dY rows into sorted order
     STDADK_LAUNCH(gather_rows_kernel, dim3((unsigned)ceil_div(c.B * Q, 256)), dim3(256), 0, c.st, dY,
@@ -1458,87 +1586,36 @@ static int step_backward(Ctx &c, const stdadk_basis_desc *b, bool window, const 
   }
   // dW0^T rows of the temporal / covariate columns: small products that ride along with the dW
   // GEMMs of the fused-tail backward (or run on their own on the generic path)
-  c.n_extra = 0;
-  c.extra[c.n_extra].A = ws + c.pl.psi; c.extra[c.n_extra].lda = c.pl.ld_psi; c.extra[c.n_extra].M = (int)b->Kt;
-  c.extra[c.n_extra].C = c.G->W[0] + (size_t)(b->p + b->Ks) * H;
-  ++c.n_extra;
-  if (b->p > 0) {
-    c.extra[c.n_extra].A = ws + c.pl.X_s; c.extra[c.n_extra].lda = b->p; c.extra[c.n_extra].M = b->p;
-    c.extra[c.n_extra].C = c.G->W[0];
-    ++c.n_extra;
-  }
+  ExtraProduct extra[2];
+  int n_extra = 0;
+  extra[n_extra++] = {ws + c.pl.psi, c.pl.ld_psi, (int)b->Kt, c.G->W[0] + (size_t)(b->p + b->Ks) * H};
+  if (b->p > 0) extra[n_extra++] = {ws + c.pl.X_s, b->p, b->p, c.G->W[0]};
   STDADK_REQUIRE(c.G->W[0], STDADK_E_ARG, "backward: dW[0] NULL");
-  c.basis = b;
-  c.dw0_forked = false;
-  if (c.aux) {
-    // as soon as dZ is final, the knot-row gather of dW0^T runs on the auxiliary stream beside the
-    // dW GEMMs and reductions of the other layers
-    c.fork_after_dz = [](Ctx &cc) -> int {
-      int r = stream_depends(cc.aux, cc.st, 2);
-      if (r) return r;
-      cc.dw0_forked = true;
-      return window_dw0(cc, cc.aux);
-    };
+  if (!fused) {
+    rc = generic_backward(c, ws + c.pl.dY, nullptr, 0, false);
+    if (rc) return rc;
+    for (int e = 0; e < n_extra; ++e) {
+      rc = gemm_run(extra[e].A, extra[e].lda, true, layer0_dz(c), H, true, extra[e].M, H, (int)c.B, nullptr,
+                    extra[e].C, H, ws + c.pl.slab, false, nullptr, c.st);
+      if (rc) return rc;
+    }
+    return close_step(c, nullptr, false, 0, coords, out);
   }
-  c.merge_dw = !c.aux && getenv("STDADK_NO_DW_ALL") == nullptr;
-  c.dw_pend = false;
-  rc = run_backward(c, ws + c.pl.dY, nullptr, 0, false);
-  c.fork_after_dz = nullptr;
-  c.merge_dw = false;
+  const bool merged = merged_dw(c);
+  const int fin = merged ? finishing_mode(c) : 0;
+  rc = tail_row_launch(c, ws + c.pl.dY, false, fin, h, &n_part);
   if (rc) return rc;
-  if (c.dw_pend) {
-    c.dw_pend = false;
-    const bool sq = c.gradsq && c.all_grouped;
-    const int fin_mode = c.fin;
-    c.fin = 0;
-    if (fin_mode == 2) {
-      // products, per-knot gather, every fixed-order sum and the squared-norm partials: ONE launch
-      FinArgs fin;
-      fin.cnt = reinterpret_cast<int *>(ws + c.pl.fin_cnt);
-      fin.slots = sq ? ws + c.pl.fin_slots : nullptr;
-      fin.step_inc = sq ? c.step_inc : nullptr;
-      int n_slots = 0;
-      rc = window_dw0(c, c.st, &c.gg_pend, &fin, &c.rg_pend, &n_slots, c.pl.fin_cap);
-      if (rc) return rc;
-      if (sq) { c.gradsq_done = true; c.gradsq_out = fin.slots; c.gradsq_n = n_slots; }
-      return 0;
-    }
-    const int nrb = reduce_jobs_block_count(c.rg_pend);
-    if (fin_mode == 1 && sq && nrb > 0) {
-      // the knot workgroups leave the squares of the rows they write (no second pass over dW0^T), the reductions
-      // launch adds the partials of what it writes behind them
-      FinArgs fin;
-      fin.slots = ws + c.pl.fin_slots;
-      int n_knot = 0;
-      rc = window_dw0(c, c.st, &c.gg_pend, &fin, nullptr, &n_knot, c.pl.fin_cap - nrb);
-      if (rc) return rc;
-      c.rg_pend.sq_parts = fin.slots + n_knot;
-      c.rg_pend.step_inc = c.step_inc;
-      c.gradsq_done = true; c.gradsq_out = fin.slots; c.gradsq_n = n_knot + nrb;
-      return launch_step_reductions(c, b, c.rg_pend);
-    }
-    rc = window_dw0(c, c.st, &c.gg_pend);
+  if (c.aux) {
+    // dZ is final: the knot-row gather of dW0^T runs on the auxiliary stream beside the dW GEMMs and reductions of
+    // the other layers
+    rc = stream_depends(c.aux, c.st, 2);
     if (rc) return rc;
-    if (sq && nrb > 0 && nrb <= STDADK_GRADSQ_PARTS - 256) {
-      // every gradient of the step is either an output of this launch or a spatial row of dW0^T (final
-      // after the launch above): their squared norm comes out of the same launch
-      c.rg_pend.sq_region_parts = c.gradsq;
-      c.rg_pend.sq_parts = c.gradsq + 256;
-      c.rg_pend.sq_src = c.G->W[0] + (size_t)b->p * H;
-      c.rg_pend.sq_n = (int64_t)b->Ks * H;
-      c.rg_pend.step_inc = c.step_inc;
-      c.gradsq_done = true; c.gradsq_out = c.gradsq; c.gradsq_n = 256 + nrb;
-    }
-    return launch_step_reductions(c, b, c.rg_pend);
-  }
-  for (int e = 0; e < c.n_extra; ++e) {     // not consumed by a grouped launch
-    rc = gemm_run(c.extra[e].A, c.extra[e].lda, true, c.dz0, H, true, c.extra[e].M, H, (int)c.B, nullptr,
-                  c.extra[e].C, H, ws + c.pl.slab, false, nullptr, c.st);
+    rc = window_gather(c, c.aux);
     if (rc) return rc;
   }
-  c.n_extra = 0;
-  if (c.dw0_forked) return stream_depends(c.st, c.aux, 3);      // join
-  return window_dw0(c, c.st);
+  rc = collect_dw_jobs(c, n_part, fin, extra, n_extra, nullptr, 0, jobs);
+  if (rc) return rc;
+  return close_step(c, &jobs, merged, fin, coords, out);
 }
 
 extern "C" int stdadk_forward_f32(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
@@ -1548,13 +1625,11 @@ extern "C" int stdadk_forward_f32(const stdadk_basis_desc *b, const stdadk_mlp_d
                                   const int32_t *step_dev, int32_t flags, stdadk_stream_t stream) {
   if (B == 0) return 0;
   Ctx c;
-  bool window;
-  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags, &window, P, nullptr, stream, training != 0, drop_seed,
-                     step_dev);
+  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags, P, nullptr, stream, training != 0, drop_seed, step_dev);
   if (rc) return rc;
   STDADK_REQUIRE(P && coords && t && y_pred, STDADK_E_ARG, "forward: NULL pointer");
   STDADK_REQUIRE(b->p == 0 || X, STDADK_E_ARG, "forward: X is NULL with p=%d", b->p);
-  return step_forward(c, b, window, coords, t, X, nullptr, y_pred, stream);
+  return step_forward(c, coords, t, X, nullptr, y_pred, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1579,11 +1654,10 @@ extern "C" int stdadk_spatial_partial_f32(const stdadk_basis_desc *b, const stda
                                           stdadk_stream_t stream) {
   if (S == 0) return 0;
   Ctx c;
-  bool window;
   // (`training` false: this door reads neither dp nor save)
-  int rc = open_step(c, b, d, S, workspace, workspace_bytes, flags, &window, P, nullptr, stream, false);
+  int rc = open_step(c, b, d, S, workspace, workspace_bytes, flags, P, nullptr, stream, false);
   if (rc) return rc;
-  STDADK_REQUIRE(window && !(flags & STDADK_FLAG_LOG_BW), STDADK_E_ARG,
+  STDADK_REQUIRE(c.window && !(flags & STDADK_FLAG_LOG_BW), STDADK_E_ARG,
                  "spatial_partial: needs the window path with fixed grid knots (compact-support basis, W0 stored (in,out))");
   STDADK_REQUIRE(b->p == 0, STDADK_E_ARG, "spatial_partial: covariates are per (site, time) row; p must be 0");
   STDADK_REQUIRE(P && P->W[0] && P->b[0] && coords && out, STDADK_E_ARG, "spatial_partial: NULL pointer");
@@ -1674,11 +1748,11 @@ extern "C" int stdadk_backward_f32(const stdadk_basis_desc *b, const stdadk_mlp_
                                    stdadk_stream_t stream) {
   if (B == 0) return 0;
   Ctx c;
-  bool window;
-  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags, &window, P, G, stream, true, drop_seed, step_dev);
+  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags, P, G, stream, true, drop_seed, step_dev);
   if (rc) return rc;
   STDADK_REQUIRE(P && G && dY, STDADK_E_ARG, "backward: NULL pointer");
-  return step_backward(c, b, window, dY, false);
+  StepOut out;
+  return step_backward(c, dY, false, nullptr, nullptr, out);
 }
 
 extern "C" int stdadk_knot_backward_f32(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
@@ -1688,20 +1762,19 @@ extern "C" int stdadk_knot_backward_f32(const stdadk_basis_desc *b, const stdadk
                                         float *loss_sum, stdadk_stream_t stream) {
   if (B == 0) return 0;
   Ctx c;
-  bool window;
   // (`training` false: this door reads neither dp nor save)
-  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags, &window, P, nullptr, stream, false);
+  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags, P, nullptr, stream, false);
   if (rc) return rc;
   STDADK_REQUIRE((flags & STDADK_FLAG_LOG_BW), STDADK_E_ARG,
                  "knot_backward: needs STDADK_FLAG_LOG_BW (the state of a learnable-knot forward/backward)");
-  STDADK_REQUIRE(P && P->W[0] && (coords || window) && d_centers && d_log_bw, STDADK_E_ARG,
+  STDADK_REQUIRE(P && P->W[0] && (coords || c.window) && d_centers && d_log_bw, STDADK_E_ARG,
                  "knot_backward: NULL pointer");
   STDADK_REQUIRE(b->Ks > 0 && d->n_hidden >= 1, STDADK_E_ARG, "knot_backward: no spatial knots / no hidden layer");
   rc = check_knot_train("knot_backward", kt);
   if (rc) return rc;
   const KnotFinishArgs fa = knot_finish_args(c, b, kt, d_centers, d_log_bw, loss_sum);
   // window path: the per-knot gather of the backward already left the raw sums in the workspace
-  if (!window) {
+  if (!c.window) {
     rc = knot_dense_sums(c, b, P, coords);
     if (rc) return rc;
   }
@@ -1709,14 +1782,25 @@ extern "C" int stdadk_knot_backward_f32(const stdadk_basis_desc *b, const stdadk
 }
 
 // where a step's predictions land: the plan's buffer (window path: sorted order, y_pred gets the un-permuted copy)
-static float *pred_buffer(const Ctx &c, bool window, float *y_pred) { return (window || !y_pred) ? c.ws + c.pl.ypred : y_pred; }
+static float *pred_buffer(const Ctx &c, float *y_pred) { return (c.window || !y_pred) ? c.ws + c.pl.ypred : y_pred; }
 
-// the loss of a step on predictions `yp`, unless the tail launch fused it: c.mse_y -> c.mse_dY / c.mse_loss, as the tail does
+// the loss of a step on predictions `yp` where no tail launch fused it: c.mse_y -> c.mse_dY / c.mse_loss, as the tail does
 static int launch_step_loss(const Ctx &c, const float *yp) {
   const int Q = c.d->out_dim;
-  if (c.mse_done) return 0;
   if (loss_is_plain_mse(c.loss, Q)) return launch_mse(yp, c.mse_y, c.B * Q, c.mse_scale, c.mse_dY, c.mse_loss, c.st);
   return launch_loss(c.loss, yp, c.mse_y, c.B, Q, c.mse_scale, c.mse_dY, c.mse_loss, c.st);
+}
+
+// what every training door fills alike
+static StepCall step_call(const stdadk_basis_desc *b, const stdadk_mlp_desc *d, const stdadk_mlp_tensors *P,
+                          const stdadk_mlp_tensors *G, const float *coords, const float *t, const float *X, const float *y,
+                          int64_t B, float grad_scale, const stdadk_loss_desc *loss, float *loss_sum, void *workspace,
+                          size_t workspace_bytes, uint64_t drop_seed, int32_t flags, stdadk_stream_t stream) {
+  StepCall s;
+  s.b = b; s.d = d; s.P = P; s.G = G; s.coords = coords; s.t = t; s.X = X; s.y = y; s.B = B;
+  s.grad_scale = grad_scale; s.loss = loss; s.loss_sum = loss_sum; s.workspace = workspace;
+  s.workspace_bytes = workspace_bytes; s.drop_seed = drop_seed; s.flags = flags; s.stream = stream;
+  return s;
 }
 
 // forward, loss and backward of one batch; `ride` / `out`: one-call step only (an error return leaves {NULL, 0, false})
@@ -1725,51 +1809,39 @@ static int train_fwd_bwd_impl(const StepCall &s, const StepRide *ride, StepOut *
   if (s.B == 0) return 0;
   const stdadk_basis_desc *b = s.b;
   Ctx c;
-  if (ride) { c.gradsq = ride->gradsq_parts; c.step_inc = ride->step_inc; c.bin_next = ride->bin_next; }
-  if (ride && ride->knots) {
-    c.knot_ride = true; c.knot_kt = ride->kt; c.knot_dc = ride->d_centers; c.knot_dlb = ride->d_log_bw;
-    c.knot_sq = ride->knot_sq; c.knot_inc = ride->finish_inc;
-  }
-  bool window;
-  int rc = open_step(c, b, s.d, s.B, s.workspace, s.workspace_bytes, s.flags, &window, s.P, s.G, s.stream, true,
-                     s.drop_seed, s.step_dev);
+  int rc = open_step(c, b, s.d, s.B, s.workspace, s.workspace_bytes, s.flags, s.P, s.G, s.stream, true, s.drop_seed,
+                     s.step_dev);
   if (rc) return rc;
-  STDADK_REQUIRE(!s.idx || window, STDADK_E_ARG,
+  STDADK_REQUIRE(!s.idx || c.window, STDADK_E_ARG,
                  "train_fwd_bwd_indexed: only the window path gathers in place; use stdadk_gather_batch_f32 + "
                  "stdadk_train_fwd_bwd_f32 for the materialising path");
   c.idx = s.idx;
+  if (ride) c.ride = ride;
   STDADK_REQUIRE(s.P && s.G && (c.prebinned || (s.coords && s.t && s.y)), STDADK_E_ARG, "train_fwd_bwd: NULL pointer");
   c.aux = (s.aux_stream && s.aux_stream != s.stream) ? (hipStream_t)s.aux_stream : nullptr;
   STDADK_REQUIRE(b->p == 0 || s.X || c.prebinned, STDADK_E_ARG, "train_fwd_bwd: X is NULL with p=%d", b->p);
   rc = make_loss(s.loss, s.d->out_dim, &c.loss);
   if (rc) return rc;
   // window path: predictions, targets and dY stay in sorted order between the binning and the weight gradients
-  float *yp = pred_buffer(c, window, s.y_pred);
-  c.mse_y = window ? c.ws + c.pl.y_s : s.y; c.mse_scale = s.grad_scale; c.mse_dY = c.ws + c.pl.dY; c.mse_loss = s.loss_sum;
-  // one launch for the forward and backward chains of the tail when nothing has to read the
-  // predictions in between (window path: the un-permute of y_pred) and the loss is fused
-  c.fuse_tail = getenv("STDADK_NO_TAIL_FWD_BWD") == nullptr && !(window && s.y_pred);
-  rc = step_forward(c, b, window, s.coords, s.t, s.X, s.y, window ? s.y_pred : yp, s.stream);
+  float *yp = pred_buffer(c, s.y_pred);
+  c.mse_y = c.window ? c.ws + c.pl.y_s : s.y; c.mse_scale = s.grad_scale; c.mse_dY = c.ws + c.pl.dY; c.mse_loss = s.loss_sum;
+  // the forward may hold its row-local launches back for the backward's when nothing has to read the predictions
+  // in between (window path: the un-permute of y_pred)
+  c.fuse_tail = getenv("STDADK_NO_TAIL_FWD_BWD") == nullptr && !(c.window && s.y_pred);
+  // ---- from here on `c` is read-only: forward -> (loss) -> backward, what they hand on by value
+  Held held;
+  StepOut left;
+  rc = step_forward(c, s.coords, s.t, s.X, s.y, c.window ? s.y_pred : yp, &held);
   if (rc) return rc;
-  rc = launch_step_loss(c, yp);
-  if (rc) return rc;
-  rc = step_backward(c, b, window, c.mse_dY, window);
-  if (rc) return rc;
-  STDADK_REQUIRE(!window || (!c.pend_valid && !c.l1_pend_valid), STDADK_E_ARG, "train_fwd_bwd: a parked launch was never issued");
-  STDADK_REQUIRE(window || !c.pend_valid, STDADK_E_ARG, "train_fwd_bwd: the parked tail launch was never issued");
-  if (c.knot_ride && !c.knot_done) {
-    // no reductions launch was pending behind the weight gradients (finishing mode 2, the separate launches, the
-    // materialising route behind its products): the finishing launch runs with zero reduce workgroups
-    if (!window) {
-      rc = knot_dense_sums(c, b, s.P, s.coords);
-      if (rc) return rc;
-    }
-    ReduceGroup none;
-    rc = launch_step_finish(none, knot_finish_args(c, b, c.knot_kt, c.knot_dc, c.knot_dlb, c.mse_loss), c.knot_sq,
-                            c.knot_inc, c.st);
+  if (!held.loss_fused) {
+    rc = launch_step_loss(c, yp);
     if (rc) return rc;
   }
-  if (out) *out = {c.gradsq_done ? c.gradsq_out : nullptr, c.gradsq_done ? c.gradsq_n : 0, c.bin_next_done};
+  rc = step_backward(c, c.mse_dY, c.window, &held, s.coords, left);
+  if (rc) return rc;
+  STDADK_REQUIRE(!c.window || (!held.tail_held && !held.l1_held), STDADK_E_ARG, "train_fwd_bwd: a parked launch was never issued");
+  STDADK_REQUIRE(c.window || !held.tail_held, STDADK_E_ARG, "train_fwd_bwd: the parked tail launch was never issued");
+  if (out) *out = left;
   return 0;
 }
 
@@ -1827,11 +1899,10 @@ static int train_step_impl(StepCall s, const stdadk_sparsity_desc *sparsity, con
   Ctx cn;
   bool bin_next = false;
   if (nb.idx && nb.B > 0 && nb.workspace && nb.binned) {
-    bool window_n = false;
-    int rc = open_step(cn, b, d, nb.B, nb.workspace, nb.workspace_bytes, s.flags & ~STDADK_FLAG_PREBINNED, &window_n, nullptr,
-                       nullptr, s.stream, false);   // planned only: cn.pl and cn.ws are read
+    int rc = open_step(cn, b, d, nb.B, nb.workspace, nb.workspace_bytes, s.flags & ~STDADK_FLAG_PREBINNED, nullptr, nullptr,
+                       s.stream, false);   // planned only: cn.pl, cn.ws and cn.window are read
     if (rc) return rc;
-    bin_next = window_n && bin_small_eligible((int)nb.B, cn.pl.G) && s.coords && s.t && (b->p == 0 || s.X);
+    bin_next = cn.window && bin_small_eligible((int)nb.B, cn.pl.G) && s.coords && s.t && (b->p == 0 || s.X);
     STDADK_REQUIRE(!bin_next || (nb.y_cols >= 0 && nb.y_cols <= d->out_dim && (nb.y_cols == 0 || s.y)),
                    STDADK_E_ARG, "train_step: next_y_cols=%d must be in 0..Q with y given", nb.y_cols);
   }
@@ -1914,10 +1985,8 @@ extern "C" int stdadk_train_step_f32(const stdadk_basis_desc *b, const stdadk_ml
                                      float *loss_sum, void *workspace, size_t workspace_bytes,
                                      uint64_t drop_seed, int32_t flags, const stdadk_optim_desc *o,
                                      stdadk_stream_t stream) {
-  StepCall s;
-  s.b = b; s.d = d; s.P = P; s.G = G; s.coords = coords; s.t = t; s.X = X; s.y = y; s.B = B;
-  s.grad_scale = grad_scale; s.loss = loss; s.loss_sum = loss_sum; s.workspace = workspace;
-  s.workspace_bytes = workspace_bytes; s.drop_seed = drop_seed; s.flags = flags; s.stream = stream;
+  StepCall s = step_call(b, d, P, G, coords, t, X, y, B, grad_scale, loss, loss_sum, workspace, workspace_bytes,
+                         drop_seed, flags, stream);
   s.idx = idx;
   return train_step_impl(s, sparsity, o, NextBatch{});
 }
@@ -1933,10 +2002,8 @@ extern "C" int stdadk_train_step_next_f32(const stdadk_basis_desc *b, const stda
                                           void *next_workspace, size_t next_workspace_bytes, int32_t *next_binned,
                                           stdadk_stream_t stream) {
   STDADK_REQUIRE(next_binned, STDADK_E_ARG, "train_step_next: next_binned is NULL");
-  StepCall s;
-  s.b = b; s.d = d; s.P = P; s.G = G; s.coords = coords_all; s.t = t_all; s.X = X_all; s.y = y_all; s.B = B;
-  s.grad_scale = grad_scale; s.loss = loss; s.loss_sum = loss_sum; s.workspace = workspace;
-  s.workspace_bytes = workspace_bytes; s.drop_seed = drop_seed; s.flags = flags; s.stream = stream;
+  StepCall s = step_call(b, d, P, G, coords_all, t_all, X_all, y_all, B, grad_scale, loss, loss_sum, workspace, workspace_bytes,
+                         drop_seed, flags, stream);
   s.idx = idx;
   return train_step_impl(s, sparsity, o, {next_idx, next_B, next_y_cols, next_workspace, next_workspace_bytes, next_binned});
 }
@@ -1954,10 +2021,8 @@ extern "C" int stdadk_train_step_knots_f32(const stdadk_basis_desc *b, const std
                                            const stdadk_adam_group *knots, stdadk_stream_t stream) {
   const bool no_next = !next_idx && next_B == 0 && !next_workspace;
   STDADK_REQUIRE(next_binned || no_next, STDADK_E_ARG, "train_step_knots: next_binned is NULL with a next batch given");
-  StepCall s;
-  s.b = b; s.d = d; s.P = P; s.G = G; s.coords = coords_all; s.t = t_all; s.X = X_all; s.y = y_all; s.B = B;
-  s.grad_scale = grad_scale; s.loss = loss; s.loss_sum = loss_sum; s.workspace = workspace;
-  s.workspace_bytes = workspace_bytes; s.drop_seed = drop_seed; s.flags = flags; s.stream = stream;
+  StepCall s = step_call(b, d, P, G, coords_all, t_all, X_all, y_all, B, grad_scale, loss, loss_sum, workspace, workspace_bytes,
+                         drop_seed, flags, stream);
   s.idx = idx;
   KnotStep ks;
   ks.kt = kt; ks.d_centers = d_centers; ks.d_log_bw = d_log_bw; ks.group = knots;
@@ -1972,12 +2037,10 @@ extern "C" int stdadk_bin_batch_f32(const stdadk_basis_desc *b, const stdadk_mlp
                                     stdadk_stream_t stream) {
   if (B == 0) return 0;
   Ctx c;
-  bool window;
   // (`training` false: this door reads neither dp nor save)
-  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags & ~STDADK_FLAG_PREBINNED, &window, nullptr, nullptr,
-                     stream, false);
+  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags & ~STDADK_FLAG_PREBINNED, nullptr, nullptr, stream, false);
   if (rc) return rc;
-  STDADK_REQUIRE(window, STDADK_E_ARG, "bin_batch: only the window path bins its batches");
+  STDADK_REQUIRE(c.window, STDADK_E_ARG, "bin_batch: only the window path bins its batches");
   STDADK_REQUIRE(coords_all && t_all && (b->p == 0 || X_all), STDADK_E_ARG, "bin_batch: NULL pointer");
   STDADK_REQUIRE(y_cols >= 0 && y_cols <= d->out_dim && (y_cols == 0 || y_all), STDADK_E_ARG,
                  "bin_batch: y_cols=%d must be in 0..Q with y_all given", y_cols);
@@ -1997,10 +2060,8 @@ extern "C" int stdadk_train_fwd_bwd_f32(const stdadk_basis_desc *b, const stdadk
                                         float *y_pred, void *workspace, size_t workspace_bytes,
                                         uint64_t drop_seed, const int32_t *step_dev, int32_t flags,
                                         stdadk_stream_t stream, stdadk_stream_t aux_stream) {
-  StepCall s;
-  s.b = b; s.d = d; s.P = P; s.G = G; s.coords = coords; s.t = t; s.X = X; s.y = y; s.B = B;
-  s.grad_scale = grad_scale; s.loss = loss; s.loss_sum = loss_sum; s.workspace = workspace;
-  s.workspace_bytes = workspace_bytes; s.drop_seed = drop_seed; s.flags = flags; s.stream = stream;
+  StepCall s = step_call(b, d, P, G, coords, t, X, y, B, grad_scale, loss, loss_sum, workspace, workspace_bytes,
+                         drop_seed, flags, stream);
   s.y_pred = y_pred; s.step_dev = step_dev; s.aux_stream = aux_stream;
   return train_fwd_bwd_impl(s, nullptr, nullptr);
 }
@@ -2015,10 +2076,8 @@ extern "C" int stdadk_train_fwd_bwd_indexed_f32(const stdadk_basis_desc *b, cons
                                                 const int32_t *step_dev, int32_t flags,
                                                 stdadk_stream_t stream, stdadk_stream_t aux_stream) {
   STDADK_REQUIRE(idx || B == 0, STDADK_E_ARG, "train_fwd_bwd_indexed: idx is NULL");
-  StepCall s;
-  s.b = b; s.d = d; s.P = P; s.G = G; s.coords = coords_all; s.t = t_all; s.X = X_all; s.y = y_all; s.B = B;
-  s.grad_scale = grad_scale; s.loss = loss; s.loss_sum = loss_sum; s.workspace = workspace;
-  s.workspace_bytes = workspace_bytes; s.drop_seed = drop_seed; s.flags = flags; s.stream = stream;
+  StepCall s = step_call(b, d, P, G, coords_all, t_all, X_all, y_all, B, grad_scale, loss, loss_sum, workspace, workspace_bytes,
+                         drop_seed, flags, stream);
   s.idx = idx; s.y_pred = y_pred; s.step_dev = step_dev; s.aux_stream = aux_stream;
   return train_fwd_bwd_impl(s, nullptr, nullptr);
 }
@@ -2064,9 +2123,8 @@ extern "C" int stdadk_eval_indexed_f32(const stdadk_basis_desc *b, const stdadk_
   STDADK_REQUIRE(!(flags & STDADK_FLAG_PREBINNED), STDADK_E_ARG, "eval_indexed: STDADK_FLAG_PREBINNED is not accepted");
   STDADK_REQUIRE(workspace_bytes >= 256, STDADK_E_WORKSPACE, "eval_indexed: workspace %zu bytes", workspace_bytes);
   Ctx c;
-  bool window;
   // the step plan is validated against whatever the workspace holds; the evaluation's own buffers are checked below
-  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags, &window, P, nullptr, stream, false);   // eval mode
+  int rc = open_step(c, b, d, B, workspace, workspace_bytes, flags, P, nullptr, stream, false);   // eval mode
   if (rc) return rc;
   const int Q = d->out_dim;
   const EvalPlan ep = eval_plan(c.pl.total_floats * sizeof(float), B, Q, b->p);
@@ -2083,10 +2141,10 @@ extern "C" int stdadk_eval_indexed_f32(const stdadk_basis_desc *b, const stdadk_
   const LossDev L = c.loss;
   char *base = (char *)workspace;
   double *part = (double *)(base + ep.part);
-  if (window) {
+  if (c.window) {
     // the indexed training step's binning: rows idx[b] read in place, targets carried into sorted order
     c.idx = idx;
-    rc = step_forward(c, b, true, coords_all, t_all, X_all, y_all, y_pred, stream);
+    rc = step_forward(c, coords_all, t_all, X_all, y_all, y_pred, nullptr);
     if (rc) return rc;
     return launch_eval_metrics(L, c.ws + c.pl.ypred, c.ws + c.pl.y_s, B, Q, metric_col, batch_weight, part, acc, c.st);
   }
@@ -2095,8 +2153,8 @@ extern "C" int stdadk_eval_indexed_f32(const stdadk_basis_desc *b, const stdadk_
   rc = stdadk_gather_batch_f32(coords_all, t_all, y_all, b->p > 0 ? X_all : nullptr, idx, B, L.y_cols, b->p, cg, tg, yg,
                                Xg, stream);
   if (rc) return rc;
-  float *yp = pred_buffer(c, false, y_pred);
-  rc = step_forward(c, b, false, cg, tg, Xg, nullptr, yp, stream);
+  float *yp = pred_buffer(c, y_pred);
+  rc = step_forward(c, cg, tg, Xg, nullptr, yp, nullptr);
   if (rc) return rc;
   return launch_eval_metrics(L, yp, yg, B, Q, metric_col, batch_weight, part, acc, c.st);
 }

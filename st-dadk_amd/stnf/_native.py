@@ -265,7 +265,8 @@ def dry_run():
     """STDADK_DRY_RUN=1 (read by the library when it is loaded): every entry point validates and plans but launches
     NOTHING -- the hook of the host-side sanitizer pass (tools/build_asan.sh, tests/test_host_sanitizer.py), which runs
     without a GPU.  Host tensors are then accepted as stand-ins for device buffers (the host never dereferences
-    them); whatever comes out is meaningless.  Not a CPU path: without the variable host tensors raise."""
+    them); whatever comes out is meaningless.  Not a CPU path: without the variable host tensors raise.  With
+    profile_enable() on, profile_collect() still lists the names of the launches a call would make, at 0 ms each."""
     return _DRY_RUN
 
 
