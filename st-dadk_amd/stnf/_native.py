@@ -279,8 +279,8 @@ def _on_device(tensor):
     return tensor.is_cuda or _DRY_RUN
 
 
-def _dev(tensor, name):
-    """Validate a device tensor and return its address."""
+def _dev(tensor, name, cur=None):
+    """Validate a device tensor and return its address (`cur`: the current device, when the caller has asked)."""
     if tensor is None:
         return None
     if _DRY_RUN and not tensor.is_cuda:
@@ -294,7 +294,7 @@ def _dev(tensor, name):
         raise RuntimeError(f"{name}: unsupported dtype {tensor.dtype}")
     if not tensor.is_contiguous():
         raise RuntimeError(f"{name}: tensor must be contiguous")
-    if tensor.device.index != _current_device():
+    if tensor.get_device() != (_current_device() if cur is None else cur):
         # the launch stream is the CURRENT device's current stream (_stream below)
         raise RuntimeError(f"{name}: tensor lives on {tensor.device} but the current device is cuda:"
                            f"{torch.cuda.current_device()}; call under torch.cuda.device({tensor.device.index})")
@@ -308,13 +308,36 @@ _current_device = getattr(torch._C, "_cuda_getDevice", None) or torch.cuda.curre
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
-def _stream():
-    """The current HIP stream of the current device (every tensor of a call is checked to live there)."""
+def _stream(cur=None):
+    """The current HIP stream of the current device (every tensor of a call is checked to live there); `cur`: that
+    device, when the caller has asked already."""
     if _DRY_RUN and not torch.cuda.is_available():
         return None
     if _raw_stream is not None:
-        return _raw_stream(_current_device())
+        return _raw_stream(_current_device() if cur is None else cur)
     return torch.cuda.current_stream().cuda_stream
+
+
+def _ref(x):
+    """byref of an optional descriptor."""
+    return C.byref(x) if x is not None else None
+
+
+def _ws(t):
+    """Address and size in bytes of a workspace tensor."""
+    return t.data_ptr(), t.numel() * t.element_size()
+
+
+def _contig(idx):
+    """`idx` itself when it is contiguous, else a contiguous copy (the library reads index tensors as plain arrays)."""
+    return idx if idx.is_contiguous() else idx.contiguous()
+
+
+def _idx(t, what):
+    """Address and count of an index tensor (`what` names it in the error)."""
+    if t.dtype != torch.int64 or not (t.is_cuda or _DRY_RUN) or not t.is_contiguous():
+        raise RuntimeError(f"{what} must be a contiguous int64 tensor on the device")
+    return t.data_ptr(), t.numel()
 
 
 # --------------------------------------------------------------------------------------------
@@ -433,8 +456,7 @@ def _mask_array(masks):
 
 def mlp_forward(desc, params, features, B, y_pred, workspace, training, seed=0, masks=None):
     rc = lib().stdadk_mlp_forward_f32(C.byref(desc), C.byref(params), _dev(features, "features"),
-                                      features.stride(0), B, _dev(y_pred, "y_pred"),
-                                      workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                      features.stride(0), B, _dev(y_pred, "y_pred"), *_ws(workspace),
                                       int(training), seed, _mask_array(masks), _stream())
     _check(rc, "stdadk_mlp_forward_f32")
 
@@ -442,9 +464,7 @@ def mlp_forward(desc, params, features, B, y_pred, workspace, training, seed=0, 
 def mlp_backward(desc, params, grads, features, B, dY, workspace, seed=0, masks=None):
     rc = lib().stdadk_mlp_backward_f32(C.byref(desc), C.byref(params), C.byref(grads),
                                        _dev(features, "features"), features.stride(0), B,
-                                       _dev(dY, "dY"), workspace.data_ptr(),
-                                       workspace.numel() * workspace.element_size(), seed,
-                                       _mask_array(masks), _stream())
+                                       _dev(dY, "dY"), *_ws(workspace), seed, _mask_array(masks), _stream())
     _check(rc, "stdadk_mlp_backward_f32")
 
 
@@ -493,17 +513,15 @@ def step_workspace_bytes(basis, desc, B, flags):
 def forward(basis, desc, params, coords, t, X, B, y_pred, workspace, flags, training=False, seed=0,
             step_dev=None):
     rc = lib().stdadk_forward_f32(C.byref(basis), C.byref(desc), C.byref(params), _dev(coords, "coords"),
-                                  _dev(t, "t"), _dev(X, "X"), B, _dev(y_pred, "y_pred"),
-                                  workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                  _dev(t, "t"), _dev(X, "X"), B, _dev(y_pred, "y_pred"), *_ws(workspace),
                                   int(training), seed, _dev(step_dev, "step_dev"), flags, _stream())
     _check(rc, "stdadk_forward_f32")
 
 
 def backward(basis, desc, params, grads, B, dY, workspace, flags, seed=0, step_dev=None):
     rc = lib().stdadk_backward_f32(C.byref(basis), C.byref(desc), C.byref(params), C.byref(grads), B,
-                                   _dev(dY, "dY"), workspace.data_ptr(),
-                                   workspace.numel() * workspace.element_size(), seed,
-                                   _dev(step_dev, "step_dev"), flags, _stream())
+                                   _dev(dY, "dY"), *_ws(workspace), seed, _dev(step_dev, "step_dev"), flags,
+                                   _stream())
     _check(rc, "stdadk_backward_f32")
 
 
@@ -533,9 +551,8 @@ def make_loss(kind="mse", Q=1, y_cols=None, taus=None, nc_weight=0.0, nc_power=1
 def loss(desc, y_pred, y, grad_scale, dY=None, loss_sum=None):
     """stdadk_loss_f32 on y_pred (B,Q), y (B,y_cols); desc None = MSE."""
     B, Q = y_pred.shape
-    rc = lib().stdadk_loss_f32(C.byref(desc) if desc is not None else None, _dev(y_pred, "y_pred"),
-                               _dev(y, "y"), B, Q, grad_scale, _dev(dY, "dY"), _dev(loss_sum, "loss_sum"),
-                               _stream())
+    rc = lib().stdadk_loss_f32(_ref(desc), _dev(y_pred, "y_pred"), _dev(y, "y"), B, Q, grad_scale, _dev(dY, "dY"),
+                               _dev(loss_sum, "loss_sum"), _stream())
     _check(rc, "stdadk_loss_f32")
 
 
@@ -575,8 +592,7 @@ def spatial_partial(basis, desc, params, coords, out, workspace, flags):
     if tuple(out.shape) != (S, desc.hidden[0]):
         raise RuntimeError(f"spatial_partial: out has shape {tuple(out.shape)}")
     rc = lib().stdadk_spatial_partial_f32(C.byref(basis), C.byref(desc), C.byref(params), _dev(coords, "coords"), S,
-                                          _dev(out, "out"), workspace.data_ptr(),
-                                          workspace.numel() * workspace.element_size(), flags, _stream())
+                                          _dev(out, "out"), *_ws(workspace), flags, _stream())
     _check(rc, "stdadk_spatial_partial_f32")
 
 
@@ -631,45 +647,53 @@ def sparsity(sp, W0, dW0, w0_t, p, Ks, Kt, grad_scale=1.0, loss_scale=0.0, loss_
     _check(rc, "stdadk_sparsity_f32")
 
 
+def _train(name, basis, desc, params, grads, coords, t, X, y, rows, grad_scale, loss_desc, loss_sum, workspace, seed,
+           flags, optim=None, sparsity_desc=None, tail=(), y_pred=None, step_dev=None, aux_stream=None):
+    """The call behind the five training doors: what they share, in the order the library takes it.  `rows` stands
+    between the arrays and the gradient scale: (B,), or (address, count) of the index tensor.  With `optim` it is a
+    one-call door (sparsity descriptor before the accumulator, optimiser descriptor and the door's own `tail` after the
+    flags); without, a split door (`y_pred` after the accumulator, the device step counter, the auxiliary stream)."""
+    cur = None if _DRY_RUN else _current_device()           # asked once for the call's tensors
+    stream = _stream(cur)
+    fn = getattr(lib(), name)
+    # (the hot call of every step: `_ref` and `_ws` written out, a Python frame each otherwise)
+    loss_ref = C.byref(loss_desc) if loss_desc is not None else None
+    ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    if optim is not None:
+        rc = fn(C.byref(basis), C.byref(desc), C.byref(params), C.byref(grads), _dev(coords, "coords", cur),
+                _dev(t, "t", cur), _dev(X, "X", cur), _dev(y, "y", cur), *rows, grad_scale, loss_ref,
+                C.byref(sparsity_desc) if sparsity_desc is not None else None, _dev(loss_sum, "loss_sum", cur),
+                ws_ptr, ws_bytes, seed, flags, C.byref(optim), *tail, stream)
+    else:
+        rc = fn(C.byref(basis), C.byref(desc), C.byref(params), C.byref(grads), _dev(coords, "coords", cur),
+                _dev(t, "t", cur), _dev(X, "X", cur), _dev(y, "y", cur), *rows, grad_scale, loss_ref,
+                _dev(loss_sum, "loss_sum", cur), _dev(y_pred, "y_pred", cur), ws_ptr, ws_bytes, seed,
+                _dev(step_dev, "step_dev", cur), flags, stream,
+                aux_stream.cuda_stream if aux_stream is not None else None)
+    _check(rc, name)
+
+
 def train_fwd_bwd(basis, desc, params, grads, coords, t, X, y, B, grad_scale, loss_sum, y_pred,
                   workspace, flags, seed=0, step_dev=None, aux_stream=None, loss_desc=None):
-    rc = lib().stdadk_train_fwd_bwd_f32(C.byref(basis), C.byref(desc), C.byref(params), C.byref(grads),
-                                        _dev(coords, "coords"), _dev(t, "t"), _dev(X, "X"), _dev(y, "y"),
-                                        B, grad_scale,
-                                        C.byref(loss_desc) if loss_desc is not None else None,
-                                        _dev(loss_sum, "loss_sum"), _dev(y_pred, "y_pred"),
-                                        workspace.data_ptr(),
-                                        workspace.numel() * workspace.element_size(), seed,
-                                        _dev(step_dev, "step_dev"), flags, _stream(),
-                                        aux_stream.cuda_stream if aux_stream is not None else None)
-    _check(rc, "stdadk_train_fwd_bwd_f32")
+    _train("stdadk_train_fwd_bwd_f32", basis, desc, params, grads, coords, t, X, y, (B,), grad_scale, loss_desc,
+           loss_sum, workspace, seed, flags, y_pred=y_pred, step_dev=step_dev, aux_stream=aux_stream)
 
 
 def train_fwd_bwd_indexed(basis, desc, params, grads, coords_all, t_all, X_all, y_all, idx, grad_scale,
                           loss_sum, y_pred, workspace, flags, seed=0, step_dev=None, aux_stream=None,
                           loss_desc=None):
     """The fused step on rows `idx` (contiguous int64 device tensor) of the resident arrays (window path)."""
-    if idx.dtype != torch.int64 or not _on_device(idx) or not idx.is_contiguous():
-        raise RuntimeError("train_fwd_bwd_indexed: idx must be a contiguous int64 tensor on the device")
-    rc = lib().stdadk_train_fwd_bwd_indexed_f32(
-        C.byref(basis), C.byref(desc), C.byref(params), C.byref(grads), _dev(coords_all, "coords"),
-        _dev(t_all, "t"), _dev(X_all, "X"), _dev(y_all, "y"), idx.data_ptr(), idx.numel(), grad_scale,
-        C.byref(loss_desc) if loss_desc is not None else None, _dev(loss_sum, "loss_sum"),
-        _dev(y_pred, "y_pred"), workspace.data_ptr(), workspace.numel() * workspace.element_size(), seed,
-        _dev(step_dev, "step_dev"), flags, _stream(),
-        aux_stream.cuda_stream if aux_stream is not None else None)
-    _check(rc, "stdadk_train_fwd_bwd_indexed_f32")
+    _train("stdadk_train_fwd_bwd_indexed_f32", basis, desc, params, grads, coords_all, t_all, X_all, y_all,
+           _idx(idx, "train_fwd_bwd_indexed: idx"), grad_scale, loss_desc, loss_sum, workspace, seed, flags,
+           y_pred=y_pred, step_dev=step_dev, aux_stream=aux_stream)
 
 
 def bin_batch(basis, desc, coords_all, t_all, X_all, y_all, idx, workspace, flags):
     """Batch preparation of the window path on its own (rows `idx` of the resident arrays binned into
     `workspace`) on the current stream; the step then runs with FLAG_PREBINNED."""
-    if idx.dtype != torch.int64 or not _on_device(idx) or not idx.is_contiguous():
-        raise RuntimeError("bin_batch: idx must be a contiguous int64 tensor on the device")
     rc = lib().stdadk_bin_batch_f32(C.byref(basis), C.byref(desc), _dev(coords_all, "coords"), _dev(t_all, "t"),
-                                    _dev(X_all, "X"), _dev(y_all, "y"), idx.data_ptr(), idx.numel(),
-                                    y_all.shape[1] if y_all is not None else 0, workspace.data_ptr(),
-                                    workspace.numel() * workspace.element_size(), flags, _stream())
+                                    _dev(X_all, "X"), _dev(y_all, "y"), *_idx(idx, "bin_batch: idx"),
+                                    y_all.shape[1] if y_all is not None else 0, *_ws(workspace), flags, _stream())
     _check(rc, "stdadk_bin_batch_f32")
 
 
@@ -688,15 +712,12 @@ def eval_indexed(basis, desc, params, coords_all, t_all, X_all, y_all, idx, loss
                  y_pred, workspace, flags):
     """Forward-only pass on rows `idx` (contiguous int64 device tensor) of the resident arrays; the batch's metric
     sums are ADDED into `acc` (EVAL_SLOTS float64 on the device); `y_pred` (B,Q) or None."""
-    if idx.dtype != torch.int64 or not _on_device(idx) or not idx.is_contiguous():
-        raise RuntimeError("eval_indexed: idx must be a contiguous int64 tensor on the device")
     if acc.dtype != torch.float64 or not _on_device(acc) or not acc.is_contiguous() or acc.numel() < EVAL_SLOTS:
         raise RuntimeError(f"eval_indexed: acc must be {EVAL_SLOTS} contiguous float64 on the device")
     rc = lib().stdadk_eval_indexed_f32(
         C.byref(basis), C.byref(desc), C.byref(params), _dev(coords_all, "coords"), _dev(t_all, "t"),
-        _dev(X_all, "X"), _dev(y_all, "y"), idx.data_ptr(), idx.numel(),
-        C.byref(loss_desc) if loss_desc is not None else None, int(metric_col), float(batch_weight), acc.data_ptr(),
-        _dev(y_pred, "y_pred"), workspace.data_ptr(), workspace.numel() * workspace.element_size(), flags, _stream())
+        _dev(X_all, "X"), _dev(y_all, "y"), *_idx(idx, "eval_indexed: idx"), _ref(loss_desc), int(metric_col),
+        float(batch_weight), acc.data_ptr(), _dev(y_pred, "y_pred"), *_ws(workspace), flags, _stream())
     _check(rc, "stdadk_eval_indexed_f32")
 
 
@@ -795,10 +816,8 @@ def knot_backward(basis, desc, params, coords, B, workspace, flags, knot_train, 
                   loss_sum=None):
     """Gradients w.r.t. the learnable knots for the batch whose backward just ran on `workspace`."""
     rc = lib().stdadk_knot_backward_f32(C.byref(basis), C.byref(desc), C.byref(params), _dev(coords, "coords"),
-                                        B, workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                        flags, C.byref(knot_train) if knot_train is not None else None,
-                                        _dev(d_centers, "d_centers"), _dev(d_log_bw, "d_log_bw"),
-                                        _dev(loss_sum, "loss_sum"), _stream())
+                                        B, *_ws(workspace), flags, _ref(knot_train), _dev(d_centers, "d_centers"),
+                                        _dev(d_log_bw, "d_log_bw"), _dev(loss_sum, "loss_sum"), _stream())
     _check(rc, "stdadk_knot_backward_f32")
 
 
@@ -818,13 +837,11 @@ def knot_grad(coords, d_phi, centers, log_bw, basis, d_centers, d_log_bw):
 
 def gather_batch(coords, t, y, X, idx, coords_out, t_out, y_out, X_out):
     """Rows idx (int64 device tensor) of the resident observation arrays -> contiguous batch buffers."""
-    if idx.dtype != torch.int64 or not _on_device(idx) or not idx.is_contiguous():
-        raise RuntimeError("gather_batch: idx must be a contiguous int64 tensor on the device")
-    B = idx.numel()
+    ip, B = _idx(idx, "gather_batch: idx")
     Q = y.shape[1] if y is not None else 0
     p = X.shape[1] if X is not None else 0
     rc = lib().stdadk_gather_batch_f32(_dev(coords, "coords"), _dev(t, "t"), _dev(y, "y"), _dev(X, "X"),
-                                       idx.data_ptr(), B, Q, p, _dev(coords_out, "coords_out"),
+                                       ip, B, Q, p, _dev(coords_out, "coords_out"),
                                        _dev(t_out, "t_out"), _dev(y_out, "y_out"), _dev(X_out, "X_out"),
                                        _stream())
     _check(rc, "stdadk_gather_batch_f32")
@@ -887,43 +904,54 @@ def adamw_ema(p, g, m, v, ema, lr, betas, eps, weight_decay, step, max_norm=0.0,
                                     betas[0], betas[1], eps, weight_decay, int(step),
                                     _dev(step_dev, "step_dev"), max_norm, _dev(sumsq_parts, "sumsq"),
                                     0 if sumsq_parts is None else sumsq_parts.numel(),
-                                    grad_mul, ema_decay, C.byref(shadow) if shadow is not None else None,
-                                    _dev(loss_watch, "loss_watch"), _dev(nonfinite_step, "nonfinite_step"), _stream())
+                                    grad_mul, ema_decay, _ref(shadow), _dev(loss_watch, "loss_watch"),
+                                    _dev(nonfinite_step, "nonfinite_step"), _stream())
     _check(rc, "stdadk_adamw_ema_f32")
 
 
 def make_optim(p, g, m, v, ema, lr, lr_dev, betas, eps, weight_decay, step_dev, max_norm, sumsq_parts, ema_decay,
                shadow=None, nonfinite_step=None):
-    o = OptimDesc()
-    o.nonfinite_step = _dev(nonfinite_step, "nonfinite_step")
-    o._keep = shadow                 # the descriptor points at it
-    o.shadow = C.pointer(shadow) if shadow is not None else None
-    o.p, o.g, o.m, o.v, o.ema = _dev(p, "p"), _dev(g, "g"), _dev(m, "m"), _dev(v, "v"), _dev(ema, "ema")
-    o.n = p.numel()
-    o.lr, o.lr_dev = float(lr), _dev(lr_dev, "lr_dev")
-    o.beta1, o.beta2, o.eps, o.weight_decay = float(betas[0]), float(betas[1]), float(eps), float(weight_decay)
-    o.step_dev = _dev(step_dev, "step_dev")
-    o.max_norm = float(max_norm)
     if sumsq_parts is not None and sumsq_parts.numel() != GRADSQ_PARTS:
         raise RuntimeError(f"make_optim: sumsq_parts must hold {GRADSQ_PARTS} floats")
-    o.sumsq_parts = _dev(sumsq_parts, "sumsq_parts")
+    o = _fill_group(OptimDesc(), p, g, m, v, ema, lr, lr_dev, max_norm, sumsq_parts, shadow)
+    o.nonfinite_step = _dev(nonfinite_step, "nonfinite_step")
+    o.beta1, o.beta2, o.eps, o.weight_decay = float(betas[0]), float(betas[1]), float(eps), float(weight_decay)
+    o.step_dev = _dev(step_dev, "step_dev")
     o.ema_decay = float(ema_decay)
     return o
+
+
+def _fill_group(d, p, g, m, v, ema, lr, lr_dev, max_norm, sumsq_parts, shadow):
+    """The fields an OptimDesc and an AdamGroup share: buffers, rate, clip norm and its partials, operand copies."""
+    d._keep = shadow                 # the descriptor points at it
+    d.shadow = C.pointer(shadow) if shadow is not None else None
+    d.p, d.g, d.m, d.v, d.ema = _dev(p, "p"), _dev(g, "g"), _dev(m, "m"), _dev(v, "v"), _dev(ema, "ema")
+    d.n = p.numel()
+    d.lr, d.lr_dev = float(lr), _dev(lr_dev, "lr_dev")
+    d.max_norm = float(max_norm)
+    d.sumsq_parts = _dev(sumsq_parts, "sumsq_parts")
+    return d
 
 
 def train_step(basis, desc, params, grads, coords, t, X, y, idx, B, grad_scale, loss_sum, workspace, flags, optim,
                seed=0, loss_desc=None, sparsity_desc=None):
     """The whole single-GPU step in one call: forward, objective (+ first-layer sparsity penalties), backward,
     clip + AdamW + EMA."""
-    if idx is not None and (idx.dtype != torch.int64 or not _on_device(idx) or not idx.is_contiguous()):
-        raise RuntimeError("train_step: idx must be a contiguous int64 tensor on the device")
-    rc = lib().stdadk_train_step_f32(
-        C.byref(basis), C.byref(desc), C.byref(params), C.byref(grads), _dev(coords, "coords"), _dev(t, "t"),
-        _dev(X, "X"), _dev(y, "y"), idx.data_ptr() if idx is not None else None, B, grad_scale,
-        C.byref(loss_desc) if loss_desc is not None else None,
-        C.byref(sparsity_desc) if sparsity_desc is not None else None, _dev(loss_sum, "loss_sum"), workspace.data_ptr(),
-        workspace.numel() * workspace.element_size(), seed, flags, C.byref(optim), _stream())
-    _check(rc, "stdadk_train_step_f32")
+    _train("stdadk_train_step_f32", basis, desc, params, grads, coords, t, X, y,
+           (_idx(idx, "train_step: idx")[0] if idx is not None else None, B), grad_scale, loss_desc, loss_sum,
+           workspace, seed, flags, optim, sparsity_desc)
+
+
+def _next_batch(nxt, y, workspace, what):
+    """Trailing arguments of the doors that may bin the next batch, `nxt` = (next_idx, next_workspace) or None: its
+    rows, the target columns, its workspace and the word the library answers in; returns (them, that word)."""
+    done = C.c_int32(0)
+    if nxt is None:
+        return (None, 0, 0, None, 0, C.byref(done)), done
+    if nxt[1].data_ptr() == workspace.data_ptr():
+        raise RuntimeError(f"{what}: the next batch needs a workspace of its own")
+    return _idx(nxt[0], f"{what}: next_idx") + (y.shape[1] if y is not None else 0,) + _ws(nxt[1]) \
+        + (C.byref(done),), done
 
 
 def train_step_next(basis, desc, params, grads, coords_all, t_all, X_all, y_all, idx, grad_scale, loss_sum, workspace,
@@ -931,21 +959,10 @@ def train_step_next(basis, desc, params, grads, coords_all, t_all, X_all, y_all,
     """train_step on rows `idx` of the resident arrays whose optimiser launch also bins rows `next_idx` into
     `next_workspace` (stdadk_train_step_next_f32).  Returns True when the next batch was binned (step on
     next_workspace with FLAG_PREBINNED then), False when nothing was prepared."""
-    for nm, ix in (("idx", idx), ("next_idx", next_idx)):
-        if ix.dtype != torch.int64 or not _on_device(ix) or not ix.is_contiguous():
-            raise RuntimeError(f"train_step_next: {nm} must be a contiguous int64 tensor on the device")
-    if next_workspace.data_ptr() == workspace.data_ptr():
-        raise RuntimeError("train_step_next: the next batch needs a workspace of its own")
-    done = C.c_int32(0)
-    rc = lib().stdadk_train_step_next_f32(
-        C.byref(basis), C.byref(desc), C.byref(params), C.byref(grads), _dev(coords_all, "coords"), _dev(t_all, "t"),
-        _dev(X_all, "X"), _dev(y_all, "y"), idx.data_ptr(), idx.numel(), grad_scale,
-        C.byref(loss_desc) if loss_desc is not None else None,
-        C.byref(sparsity_desc) if sparsity_desc is not None else None, _dev(loss_sum, "loss_sum"), workspace.data_ptr(),
-        workspace.numel() * workspace.element_size(), seed, flags, C.byref(optim), next_idx.data_ptr(), next_idx.numel(),
-        y_all.shape[1] if y_all is not None else 0, next_workspace.data_ptr(),
-        next_workspace.numel() * next_workspace.element_size(), C.byref(done), _stream())
-    _check(rc, "stdadk_train_step_next_f32")
+    rows = _idx(idx, "train_step_next: idx")
+    tail, done = _next_batch((next_idx, next_workspace), y_all, workspace, "train_step_next")
+    _train("stdadk_train_step_next_f32", basis, desc, params, grads, coords_all, t_all, X_all, y_all, rows, grad_scale,
+           loss_desc, loss_sum, workspace, seed, flags, optim, sparsity_desc, tail)
     return bool(done.value)
 
 
@@ -957,25 +974,11 @@ def train_step_knots(basis, desc, params, grads, coords, t, X, y, idx, B, grad_s
     (rows 0..B-1 of the given arrays).  `nxt` = (next_idx, next_workspace): the rows of the following step, binned by
     this step's weight-gradient launch when it can carry them.  Returns True when it did (step on next_workspace with
     FLAG_PREBINNED then), False when nothing was prepared."""
-    ixs = (("idx", idx),) + ((("next_idx", nxt[0]),) if nxt is not None else ())
-    for nm, ix in ixs:
-        if ix is not None and (ix.dtype != torch.int64 or not _on_device(ix) or not ix.is_contiguous()):
-            raise RuntimeError(f"train_step_knots: {nm} must be a contiguous int64 tensor on the device")
-    if nxt is not None and nxt[1].data_ptr() == workspace.data_ptr():
-        raise RuntimeError("train_step_knots: the next batch needs a workspace of its own")
-    done = C.c_int32(0)
-    rc = lib().stdadk_train_step_knots_f32(
-        C.byref(basis), C.byref(desc), C.byref(params), C.byref(grads), _dev(coords, "coords"), _dev(t, "t"),
-        _dev(X, "X"), _dev(y, "y"), idx.data_ptr() if idx is not None else None, B, grad_scale,
-        C.byref(loss_desc) if loss_desc is not None else None,
-        C.byref(sparsity_desc) if sparsity_desc is not None else None, _dev(loss_sum, "loss_sum"), workspace.data_ptr(),
-        workspace.numel() * workspace.element_size(), seed, flags, C.byref(optim),
-        nxt[0].data_ptr() if nxt is not None else None, nxt[0].numel() if nxt is not None else 0,
-        y.shape[1] if (nxt is not None and y is not None) else 0, nxt[1].data_ptr() if nxt is not None else None,
-        nxt[1].numel() * nxt[1].element_size() if nxt is not None else 0, C.byref(done),
-        C.byref(knot_train) if knot_train is not None else None, _dev(d_centers, "d_centers"),
-        _dev(d_log_bw, "d_log_bw"), C.byref(knots), _stream())
-    _check(rc, "stdadk_train_step_knots_f32")
+    rows = (_idx(idx, "train_step_knots: idx")[0] if idx is not None else None, B)
+    tail, done = _next_batch(nxt, y, workspace, "train_step_knots")
+    tail += (_ref(knot_train), _dev(d_centers, "d_centers"), _dev(d_log_bw, "d_log_bw"), C.byref(knots))
+    _train("stdadk_train_step_knots_f32", basis, desc, params, grads, coords, t, X, y, rows, grad_scale, loss_desc,
+           loss_sum, workspace, seed, flags, optim, sparsity_desc, tail)
     return bool(done.value)
 
 
@@ -989,14 +992,7 @@ def sumsq2(g0, parts0, g1, parts1, step_inc=None):
 
 
 def make_adam_group(p, g, m, v, ema, lr, lr_dev=None, max_norm=0.0, sumsq_parts=None, shadow=None):
-    gr = AdamGroup()
-    gr._keep = shadow
-    gr.shadow = C.pointer(shadow) if shadow is not None else None
-    gr.p, gr.g, gr.m, gr.v, gr.ema = _dev(p, "p"), _dev(g, "g"), _dev(m, "m"), _dev(v, "v"), _dev(ema, "ema")
-    gr.n = p.numel()
-    gr.lr, gr.lr_dev = float(lr), _dev(lr_dev, "lr_dev")
-    gr.max_norm = float(max_norm)
-    gr.sumsq_parts = _dev(sumsq_parts, "sumsq")
+    gr = _fill_group(AdamGroup(), p, g, m, v, ema, lr, lr_dev, max_norm, sumsq_parts, shadow)
     gr.n_parts = 0 if sumsq_parts is None else sumsq_parts.numel()
     return gr
 

@@ -22,6 +22,9 @@ import torch.distributed as dist
 
 from . import _native as N
 from . import distributed as D
+from ._native import _contig
+from .flat import Cached, _bump_engine_version, flatten_parameters
+from .losses import Objective
 
 
 # Batches up to this size are binned by ONE workgroup (window.hip: SMALL_B); random row reads from a
@@ -29,34 +32,6 @@ from . import distributed as D
 # B = 4096: 0.185 ms/step gathered first vs 0.197 ms reading in place); above it the multi-kernel binning
 # spreads the reads over the chip and reading in place saves the gather launch.
 _INDEXED_MIN_B = 8192
-
-
-def flatten_parameters(model, transpose_first=True, pad_multiple=4):
-    """Move every trainable parameter of `model` into one flat fp32 buffer (the parameters become
-    views, so state_dict()/checkpoints keep their names and shapes).  Each parameter is padded to a
-    multiple of 4 floats so every view is 16-byte aligned.  With `transpose_first` the first
-    Linear's weight is STORED (in,out) row-major — the layout the window kernels gather rows from —
-    and `model.mlp[0].weight` becomes its .t() view (same values, shape (out,in)).
-    The buffer's length is rounded up to `pad_multiple` floats (zeros: equal shards of a sharded optimiser).
-    Returns (flat, [(name, offset, numel)])."""
-    params = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
-    dev = params[0][1].device
-    offs, total = [], 0
-    for n, p in params:
-        offs.append((n, total, p.numel()))
-        total += (p.numel() + 3) // 4 * 4
-    total = (total + pad_multiple - 1) // pad_multiple * pad_multiple
-    flat = torch.zeros(total, device=dev, dtype=torch.float32)
-    first_w = model._body[0].weight
-    for (n, p), (_, o, k) in zip(params, offs):
-        if transpose_first and p is first_w:
-            out_f, in_f = p.shape
-            flat[o:o + k].view(in_f, out_f).copy_(p.data.t())
-            p.data = flat[o:o + k].view(in_f, out_f).t()
-        else:
-            flat[o:o + k].copy_(p.data.reshape(-1))
-            p.data = flat[o:o + k].view(p.shape)
-    return flat, offs
 
 
 def _rank_seed(base, rank):
@@ -149,7 +124,7 @@ class _GraphRunner:
         self.graph.replay()
 
 
-class TrainStep:
+class TrainStep(Cached):
     """One fused optimisation step of STInterpMLP (fixed or learnable knots).
 
     Objective (scripts/train_st_interp.py:617-658): loss="mse" (regression_type 'mean'), or
@@ -210,22 +185,31 @@ class TrainStep:
         if dtype not in ("f32", "bf16"):
             raise ValueError(f"unknown dtype '{dtype}'; use 'f32' or 'bf16'")
         self.dtype = dtype
-        if loss not in ("mse", "pinball"):
-            raise ValueError(f"unknown loss '{loss}'; use 'mse' or 'pinball'")
-        self.loss_kind = loss
-        self.quantile_levels = [float(q) for q in quantile_levels] if quantile_levels is not None else None
-        if loss == "pinball" and (self.quantile_levels is None
-                                  or len(self.quantile_levels) != model.output_dim):
-            raise ValueError(f"pinball loss needs output_dim={model.output_dim} quantile levels")
-        self.nc_weight = 0.0 if model._has_delta else float(non_crossing_weight)
-        self.nc_power = int(non_crossing_power)
-        self.nc_lambda = float(non_crossing_lambda) if model._has_delta else 0.0
-        self._loss_descs = {}
+        self.objective = Objective(model, loss, quantile_levels, non_crossing_weight, non_crossing_power,
+                                   non_crossing_lambda)
+        self._cache = {}                # descriptors by slot (_cached): optimiser plans, knot penalties, bf16 tables
         self.indexed_min_batch = _INDEXED_MIN_B
         self.dev = next(model.parameters()).device
         if self.dev.type != "cuda" and not N.dry_run():
             raise RuntimeError("TrainStep needs the model on a HIP device; there is no CPU path")
-        # distributed
+        # (the order of these is the order of the allocations, of the draw from torch's generator and of the broadcasts)
+        self._setup_distributed(process_group, distributed, world_size, shard_optimizer, sync_init, fused_knot_step,
+                                two_streams)
+        self._setup_flat_buffers(lr, weight_decay, betas, eps, grad_clip, ema_decay, max_batch)
+        self._setup_operand_copies(force_dense)
+        self._setup_gradient_views(sparsity_penalty_type, sparsity_lambda_l1, sparsity_lambda_group,
+                                   sparsity_apply_to_spatial, sparsity_apply_to_temporal)
+        self._setup_knots(basis_lr_ratio, basis_clip_ratio, domain_penalty_weight, movement_penalty_weight)
+        self._setup_delta_head()
+        self._setup_step_buffers(seed, two_streams, sync_init, use_graph, pack_weights, inline_prep, nonfinite_guard)
+
+    def _src_rank(self):
+        """Global rank of the group's rank 0, the source of the construction-time broadcasts."""
+        return dist.get_global_rank(self.pg, 0) if self.pg is not None else 0
+
+    def _setup_distributed(self, process_group, distributed, world_size, shard_optimizer, sync_init, fused_knot_step,
+                           two_streams):
+        model = self.model
         if distributed is None:
             distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1
         self.distributed = bool(distributed)
@@ -250,20 +234,19 @@ class TrainStep:
         if missing and fused_knot_step is not None and want_knot_step:
             raise ValueError(f"fused_knot_step=True needs {missing[0]}")
         self._knot_step = want_knot_step and not missing
-        self._knot_plan = None          # cached descriptors of the one-call learnable step (_knot_step_plan)
         if self.distributed and sync_init:
             # identical replicas: parameters AND buffers (knot tables of the gmm / random_site initialisers depend on
             # the rank's own train_coords) from rank 0, before anything is derived from them
             with torch.no_grad():
                 for tns in list(model.parameters()) + list(model.buffers()):
-                    dist.broadcast(tns.data, src=dist.get_global_rank(process_group, 0) if process_group is not None else 0,
-                                   group=process_group)
+                    dist.broadcast(tns.data, src=self._src_rank(), group=process_group)
+
+    def _setup_flat_buffers(self, lr, weight_decay, betas, eps, grad_clip, ema_decay, max_batch):
         # every rank's slice of the flat buffers starts on a 128-byte line: chunk = a multiple of 32 floats
-        self.flat, self.offsets = flatten_parameters(model, transpose_first=True,
-                                                     pad_multiple=32 * self.world if self.shard else 4)
+        self.flat, self.layout = flatten_parameters(self.model, transpose_first=True,
+                                                    pad_multiple=32 * self.world if self.shard else 4)
+        self.offsets = self.layout.offsets
         self.grad = torch.zeros_like(self.flat)
-        self._plan = None               # cached slices / descriptors of the optimiser's parameter groups (_adam_plan)
-        self._knot_train = None         # ... and of the knot penalties
         self.chunk = self.flat.numel() // self.world if self.shard else self.flat.numel()
         self.lo = self.rank * self.chunk if self.shard else 0
         self.hi = self.lo + self.chunk
@@ -278,77 +261,74 @@ class TrainStep:
         self.grad_clip = float(grad_clip or 0.0)
         self.step_count = 0
         self.max_batch = int(max_batch)
+
+    def _setup_operand_copies(self, force_dense):
         # BASELINE config C3 (dtype="bf16"): the Linear layers after the first take bf16 operands on the matrix
         # cores.  Master weights, gradients, AdamW state and the EMA stay fp32 in the flat buffers; the bf16
         # operand copies (each weight and its transpose) live in one buffer that the optimiser kernel rewrites
         # from the values it has just stepped.
+        model = self.model
         self._shadow_buf = None
         self._shadow_regions = []
-        self._shadow_tables = {}
         self._pack_buf = None           # fragment-order fp32 copies of the same weights (_install_packed_copies)
         self._pack_regions = []
         self._pack_table = None
         self._pack_params = None
-        model.compute_dtype = dtype
+        model.compute_dtype = self.dtype
         model._bf16_engine = None
-        if dtype == "bf16":
+        if self.dtype == "bf16":
             self._install_bf16_copies()
         self.state = model._step_state(self.dev, force_dense=force_dense, training=True)
         assert self.state.w0_transposed
         self.uses_window = N.step_uses_window(self.state.basis, self.state.desc, self.state.flags)
+
+    def _setup_gradient_views(self, penalty_type, lambda_l1, lambda_group, apply_spatial, apply_temporal):
         # gradient views in _param_list() order; dW0 is stored transposed like W0
-        views, dviews = [], []
-        by_name = {n: (o, k) for n, o, k in self.offsets}
-        first_w = model._body[0].weight
+        model, lay = self.model, self.layout
+        self.grad_views, self._delta_views = [], []
         for n, p in model.named_parameters():
-            if p.requires_grad:
-                o, k = by_name[n]
-                if p is first_w:
-                    views.append(self.grad[o:o + k].view(p.shape[1], p.shape[0]))
-                elif n.startswith("delta_params."):
-                    dviews.append(self.grad[o:o + k])
-                elif n.startswith("spatial_basis."):
-                    pass            # knot gradients come from stdadk_knot_backward_f32 (below)
-                else:
-                    views.append(self.grad[o:o + k].view(p.shape))
-        self.grad_views = views
+            if p.requires_grad and not n.startswith("spatial_basis."):     # (knot gradients: stdadk_knot_backward_f32)
+                (self._delta_views if n.startswith("delta_params.") else self.grad_views).append(lay.view(self.grad, p))
         # sparsity penalties on the first layer (config keys of train_st_interp.py:674-691): their gradient
         # is added to dW0^T by stdadk_sparsity_f32 between backward and clipping
         self._sparsity = None
-        if sparsity_penalty_type != "none":
-            self._sparsity = N.make_sparsity(sparsity_penalty_type, sparsity_lambda_l1, sparsity_lambda_group,
-                                             sparsity_apply_to_spatial, sparsity_apply_to_temporal)
-            o, k = by_name[next(n for n, p in model.named_parameters() if p is first_w)]
-            self._w0t = self.flat[o:o + k].view(first_w.shape[1], first_w.shape[0])
-            self._g_w0t = self.grad[o:o + k].view(first_w.shape[1], first_w.shape[0])
+        if penalty_type != "none":
+            self._sparsity = N.make_sparsity(penalty_type, lambda_l1, lambda_group, apply_spatial, apply_temporal)
+            self._w0t, self._g_w0t = lay.view(self.flat, lay.first_w), lay.view(self.grad, lay.first_w)
+
+    def _setup_knots(self, basis_lr_ratio, basis_clip_ratio, domain_penalty_weight, movement_penalty_weight):
         # learnable knots (DA-STDK): their own AdamW group (lr x basis_lr_ratio) and clip norm
         # (grad_clip x basis_clip_ratio), scripts/train_st_interp.py:470-483,698-705; the knot tensors
         # are registered first, so they occupy the head [0, knot_end) of the flat buffers
-        self.learnable = bool(model.spatial_basis.learnable)
+        sb = self.model.spatial_basis
+        self.learnable = bool(sb.learnable)
         self.knot_end = 0
         if self.learnable:
-            sb = model.spatial_basis
-            (nc, oc, kc), (nl, ol, kl) = self.offsets[0], self.offsets[1]
-            assert nc == "spatial_basis.centers" and nl == "spatial_basis.log_bandwidths" and oc == 0
-            self.g_centers = self.grad[oc:oc + kc].view(sb.k, 2)
-            self.g_log_bw = self.grad[ol:ol + kl]
+            assert [n for n, _, _ in self.offsets[:2]] == ["spatial_basis.centers", "spatial_basis.log_bandwidths"]
+            self.g_centers = self.layout.view(self.grad, sb.centers).view(sb.k, 2)
+            self.g_log_bw = self.layout.view(self.grad, sb.log_bandwidths)
             self.knot_end = self.offsets[2][1]
             self.basis_lr = self.lr * float(basis_lr_ratio)
             self.basis_clip = self.grad_clip * float(basis_clip_ratio)
             self.basis_lr_dev = torch.full((1,), self.basis_lr, device=self.dev)
             self.sumsq_basis = torch.zeros(N.SUMSQ_PARTS, device=self.dev)
             self.domain_w, self.movement_w = float(domain_penalty_weight), float(movement_penalty_weight)
+
+    def _setup_delta_head(self):
+        model = self.model
         self.d_head = self.d_delta = None
         if model._has_delta:
             # the library differentiates w.r.t. the derived output layer; dWo/dbo are scratch and
             # stdadk_delta_head_backward_f32 folds them into the delta rows of the flat gradient
+            dviews = self._delta_views
             self.d_head = [torch.empty_like(self.state.head[0]), torch.empty_like(self.state.head[1])]
             self.d_delta = model._delta_matrix(dviews)
             assert self.d_delta.data_ptr() == dviews[0].data_ptr() and self.state.delta.stride(0) == self.d_delta.stride(0)
-        self.grads_t = model._pack(views + (self.d_head or []))
-        B = self.max_batch
-        self.ws = torch.empty(N.step_workspace_bytes(self.state.basis, self.state.desc, B, self.state.flags) // 4,
-                              device=self.dev)
+        self.grads_t = model._pack(self.grad_views + (self.d_head or []))
+
+    def _setup_step_buffers(self, seed, two_streams, sync_init, use_graph, pack_weights, inline_prep, nonfinite_guard):
+        st = self.state
+        self.ws = torch.empty(N.step_workspace_bytes(st.basis, st.desc, self.max_batch, st.flags) // 4, device=self.dev)
         self.loss_sum = torch.zeros(1, device=self.dev)       # running sum of squared errors
         self._loss_snap = None          # run_epoch(loss="batches"): copy of the accumulator before the last batch
         self.sumsq = torch.zeros(N.SUMSQ_PARTS, device=self.dev)
@@ -365,8 +345,7 @@ class TrainStep:
         self.rows_seen = 0
         if self.distributed and sync_init:
             bs = torch.tensor([self.base_seed], dtype=torch.int64, device=self.dev)
-            dist.broadcast(bs, src=dist.get_global_rank(process_group, 0) if process_group is not None else 0,
-                           group=process_group)
+            dist.broadcast(bs, src=self._src_rank(), group=self.pg)
             self.base_seed = int(bs.item())
         self.seed = _rank_seed(self.base_seed, self.rank)
         # graph: step() and step_indexed() capture their own chains and share the eager first call
@@ -378,7 +357,7 @@ class TrainStep:
         # the one-call step applies with a single parameter group on one GPU (data-parallel training needs
         # the all-reduce between backward and optimiser; learnable knots / the delta head have extra kernels there)
         self._whole_step = (not self.distributed and self.world == 1 and not self.learnable
-                            and not model._has_delta and self.aux_stream is None)
+                            and not self.model._has_delta and self.aux_stream is None)
         self._optim = None
         self._sumsq512 = torch.zeros(N.GRADSQ_PARTS, device=self.dev)
         # fp32 one-call steps stream the hidden weights after the first from fragment-order copies that the step's
@@ -405,24 +384,24 @@ class TrainStep:
     # ------------------------------------------------------------------------------------
     def _install_bf16_copies(self):
         m = self.model
-        lins = m._linears()
-        by_name = {n: (o, k) for n, o, k in self.offsets}
-        names = {id(p): n for n, p in m.named_parameters()}
-        total = sum(2 * lins[l].weight.numel() for l in range(1, len(m.hidden_dims)))
+        total = sum(2 * h * hp for _, _, h, hp in self.layout.hidden)
         self._shadow_buf = torch.empty(max(total, 8), device=self.dev, dtype=torch.bfloat16)
-        pairs, regions, pos = [None] * len(lins), [], 0
-        for l in range(1, len(m.hidden_dims)):
-            w = lins[l].weight
-            h, hp = w.shape
-            wb = self._shadow_buf[pos:pos + h * hp].view(h, hp)
-            wt = self._shadow_buf[pos + h * hp:pos + 2 * h * hp].view(hp, h)
-            pos += 2 * h * hp
-            pairs[l] = (wb, wt)
-            regions.append((by_name[names[id(w)]][0], h, hp, wb, wt))
-        self._shadow_regions = regions
+        carve = self._carver(self._shadow_buf)
+        pairs, self._shadow_regions = self.layout.hidden_copies(
+            lambda h, hp: (carve(h * hp).view(h, hp), carve(h * hp).view(hp, h)))
         m._bf16_engine = pairs
         m._bf16_refresh = weakref.WeakMethod(self.refresh_bf16)
         self.refresh_bf16()
+
+    @staticmethod
+    def _carver(buf):
+        """carve(n): the next n elements of `buf`."""
+        pos = [0]
+
+        def carve(n):
+            pos[0] += n
+            return buf[pos[0] - n:pos[0]]
+        return carve
 
     def _pack_qualifies(self):
         """fp32 one-call steps whose hidden layers after the first run in the fused tail kernels with in / out widths
@@ -435,22 +414,16 @@ class TrainStep:
                 and os.environ.get("STDADK_NO_FUSED_TAIL", "") != "1")
 
     def _install_packed_copies(self):
-        m = self.model
-        lins = m._linears()
-        by_name = {n: (o, k) for n, o, k in self.offsets}
-        names = {id(p): n for n, p in m.named_parameters()}
-        shapes = [tuple(lins[l].weight.shape) for l in range(1, len(m.hidden_dims))]
-        self._pack_buf = torch.zeros(sum(sum(N.pack_f32_sizes(h, hp)) for h, hp in shapes), device=self.dev)
-        regions, pos = [], 0
+        self._pack_buf = torch.zeros(sum(sum(N.pack_f32_sizes(h, hp)) for _, _, h, hp in self.layout.hidden),
+                                     device=self.dev)
+        carve = self._carver(self._pack_buf)
+        pairs, self._pack_regions = self.layout.hidden_copies(
+            lambda h, hp: [carve(n) for n in N.pack_f32_sizes(h, hp)])
         self._pack_params = N.MlpTensors.from_buffer_copy(self.state.params)
-        for l, (h, hp) in enumerate(shapes, start=1):
-            nf, nb = N.pack_f32_sizes(h, hp)
-            pf, pb = self._pack_buf[pos:pos + nf], self._pack_buf[pos + nf:pos + nf + nb]
-            pos += nf + nb
-            regions.append((by_name[names[id(lins[l].weight)]][0], h, hp, pf, pb))
-            self._pack_params.W_bf16[l], self._pack_params.WT_bf16[l] = pf.data_ptr(), pb.data_ptr()
-        self._pack_regions = regions
-        self._pack_table = N.make_bf16_shadow(regions)
+        for l, pair in enumerate(pairs):
+            if pair is not None:
+                self._pack_params.W_bf16[l], self._pack_params.WT_bf16[l] = pair[0].data_ptr(), pair[1].data_ptr()
+        self._pack_table = N.make_bf16_shadow(self._pack_regions)
         self.refresh_bf16()
 
     def _shadow(self, base=0):
@@ -458,11 +431,10 @@ class TrainStep:
         after the first)."""
         if not self._shadow_regions:
             return None
-        key = int(base)
-        if key not in self._shadow_tables:
-            self._shadow_tables[key] = N.make_bf16_shadow([(o - key, h, hp, wb, wt)
-                                                           for o, h, hp, wb, wt in self._shadow_regions])
-        return self._shadow_tables[key]
+        return self._cached(("shadow", base), None, self._make_shadow, int(base))
+
+    def _make_shadow(self, base):
+        return N.make_bf16_shadow([(o - base, h, hp, wb, wt) for o, h, hp, wb, wt in self._shadow_regions])
 
     def refresh_bf16(self):
         """Re-round the bf16 operand copies from the fp32 master weights: needed after the parameters were
@@ -493,37 +465,43 @@ class TrainStep:
         self.basis_lr = float(lr)
         self.basis_lr_dev.fill_(self.basis_lr)
 
+    def _step_call(self, door, coords, t, X, y, rows, global_rows, ws, flags, optim_tail=None, params=None):
+        """One of the five training doors of the binding: what they all take -- the descriptors, the arrays, `rows`
+        ((B,), (idx,) or (idx, B), as the door has them), the gradient scale, the loss accumulator, workspace, flags,
+        dropout seed and loss descriptor -- is assembled here.  `optim_tail`: for a one-call door, the optimiser
+        descriptor and whatever the door takes after it (the sparsity descriptor goes along); None for a split door,
+        which has y_pred (none here) before the workspace and takes the device step counter and the auxiliary stream."""
+        st = self.state
+        scale = D.grad_scale(global_rows, self.model.output_dim)
+        loss_desc = self.objective.desc(y.shape[1])
+        if optim_tail is None:
+            return door(st.basis, st.desc, st.params, self.grads_t, coords, t, X, y, *rows, scale, self.loss_sum, None,
+                        ws, flags, seed=self.seed, step_dev=self.step_dev, aux_stream=self.aux_stream,
+                        loss_desc=loss_desc)
+        return door(st.basis, st.desc, st.params if params is None else params, self.grads_t, coords, t, X, y, *rows,
+                    scale, self.loss_sum, ws, flags, *optim_tail, seed=self.seed, loss_desc=loss_desc,
+                    sparsity_desc=self._sparsity)
+
     def _enqueue(self, X, coords, t, y, B, global_rows, idx=None, ws=None, prebinned=False, nxt=None):
         """All kernels of one step on the current stream (capturable: no sync, no allocation).
         With `idx` (window path) X/coords/t/y are the RESIDENT arrays and the batch is their rows idx;
         `prebinned`: the batch already sits binned in workspace `ws` (pipelined preparation).
         `nxt` = (next_idx, next_workspace), one-call step only: the optimiser launch also bins the next batch
         (stdadk_train_step_next_f32); returns True when it did."""
-        st = self.state
         ws = self.ws if ws is None else ws
-        flags = st.flags | (N.FLAG_PREBINNED if prebinned else 0)
-        Q = self.model.output_dim
+        flags = self.state.flags | (N.FLAG_PREBINNED if prebinned else 0)
         if self._whole_step:
             # single GPU, one parameter group: the whole step is ONE library call, which also takes the
             # gradient's squared norm out of the launches that produce it (no separate pass over it)
-            if self._optim is None:
-                self._optim = N.make_optim(self.flat, self.grad, self.m, self.v, self.ema, self.lr, self.lr_dev,
-                                           self.betas, self.eps, self.wd, self.step_dev, self.grad_clip,
-                                           self._sumsq512 if self.grad_clip > 0 else None, self.ema_decay,
-                                           shadow=self._shadow(0) if self._pack_table is None else self._pack_table,
-                                           nonfinite_step=self.nonfinite)
-            params = st.params
-            if self._pack_params is not None:
-                params, flags = self._pack_params, flags | N.FLAG_PACK_F32
+            self._optim = self._cached("one_call", self._plan_key(), self._one_call_plan)[0]
+            params = self._pack_params
+            if params is not None:
+                flags |= N.FLAG_PACK_F32
             if nxt is not None:
-                return N.train_step_next(st.basis, st.desc, params, self.grads_t, coords, t, X, y, idx,
-                                         D.grad_scale(global_rows, Q), self.loss_sum, ws, flags, self._optim, nxt[0],
-                                         nxt[1], seed=self.seed, loss_desc=self._loss_desc(y.shape[1]),
-                                         sparsity_desc=self._sparsity)
-            N.train_step(st.basis, st.desc, params, self.grads_t, coords, t, X, y,
-                         idx if not prebinned else None, B, D.grad_scale(global_rows, Q), self.loss_sum, ws, flags,
-                         self._optim, seed=self.seed, loss_desc=self._loss_desc(y.shape[1]),
-                         sparsity_desc=self._sparsity)
+                return self._step_call(N.train_step_next, coords, t, X, y, (idx,), global_rows, ws, flags,
+                                       (self._optim, nxt[0], nxt[1]), params)
+            self._step_call(N.train_step, coords, t, X, y, (idx if not prebinned else None, B), global_rows, ws, flags,
+                            (self._optim,), params)
             return False
         if self._knot_step:
             # single GPU, learnable knots: the two-group step as ONE library call -- the knot finish and both clip
@@ -531,12 +509,10 @@ class TrainStep:
             if B == 0:
                 raise RuntimeError("an empty batch cannot carry the parameter-level penalties of a learnable-knot step")
             optim, knots = self._knot_step_plan()
-            return N.train_step_knots(st.basis, st.desc, st.params, self.grads_t, coords, t, X, y,
-                                      idx if (nxt is not None or not prebinned) else None, B,
-                                      D.grad_scale(global_rows, Q), self.loss_sum, ws, flags, optim,
-                                      self._knot_train_desc(B * Q), self.g_centers, self.g_log_bw, knots, nxt=nxt,
-                                      seed=self.seed, loss_desc=self._loss_desc(y.shape[1]),
-                                      sparsity_desc=self._sparsity)
+            return self._step_call(N.train_step_knots, coords, t, X, y,
+                                   (idx if (nxt is not None or not prebinned) else None, B), global_rows, ws, flags,
+                                   (optim, self._knot_train_desc(B * self.model.output_dim), self.g_centers,
+                                    self.g_log_bw, knots, nxt))
         self._enqueue_grads(X, coords, t, y, B, global_rows, idx=idx, ws=ws, prebinned=prebinned)
         if self.shard:
             if not self.distributed:
@@ -561,44 +537,76 @@ class TrainStep:
         return out
 
     # ---- optimiser half of a step: replicated on every rank, or on this rank's slice (shard_optimizer=True) -----
-    def _adam_plan(self):
-        """The optimiser's view of the flat range [lo, hi) (everything when replicated, this rank's slice when sharded):
-        (arguments of the sum-of-squares launch, parameter groups).  The MLP group comes first; learnable knots, the
-        head [0, knot_end) of the flat buffers, form the second with their own rate and clip norm.  The sum of squares
-        reads the gradient slice of EVERY group, an empty one included (a rank that holds nothing of a group
-        contributes zeros to its global clip norm); `groups` has an N.make_adam_group descriptor for each non-empty
-        one, moments / EMA shadow indexed from `lo`.  Rebuilt only when a buffer, a boundary or a rate changes: up to
-        14 buffer addresses and 10 slices, per step they were a quarter of the host time of a path that is host-bound."""
-        ema, ke, lo, hi = self.ema, self.knot_end, self.lo, self.hi
+    def _plan_key(self):
+        """Which buffers, boundaries and rates the optimiser's descriptors were built from: they are rebuilt only when
+        one of these changes (up to 14 buffer addresses and 10 slices -- per step they were a quarter of the host time
+        of a path that is host-bound)."""
+        ema = self.ema
         key = (self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-               ema.data_ptr() if ema is not None else 0, lo, hi, ke, self.lr, self.grad_clip, id(self.lr_dev),
-               self.shard) + ((self.basis_lr, self.basis_clip, id(self.basis_lr_dev)) if ke else ())
-        if self._plan is not None and self._plan[0] == key:
-            return self._plan[1]
-        clip = self.grad_clip > 0
-        # replicated: the optimiser kernel re-rounds the bf16 operand copies of the MLP weights it has just stepped;
-        # sharded: they are refreshed from the gathered parameters
-        spans = [(max(ke, lo), min(self.flat.numel(), hi), self.lr, self.lr_dev, self.grad_clip, self.sumsq,
-                  not self.shard)]
+               ema.data_ptr() if ema is not None else 0, self.lo, self.hi, self.knot_end, self.lr, self.grad_clip,
+               id(self.lr_dev), self.shard)
+        return (key + (self.basis_lr, self.basis_clip, id(self.basis_lr_dev))) if self.knot_end else key
+
+    def _group_spans(self, one_call=False):
+        """The optimiser's parameter groups over the flat range [lo, hi) (everything when replicated, this rank's slice
+        when sharded), the one source of every optimiser descriptor: the MLP group first; learnable knots, the head
+        [0, knot_end) of the flat buffers, second, with their own rate and clip norm.  Per group
+        (buffers, lr, lr_dev, max_norm, parts, named, shadow): `buffers` = the (p, g, m, v, ema) slices (moments and
+        shadow indexed from `lo`; possibly empty: a rank that holds nothing of a group still contributes zeros to its
+        global clip norm), `parts` the group's clip-norm partials, `named` = `parts` where the descriptor names them,
+        `shadow` the table of operand copies the launch keeps current.  `one_call`: for the one-call steps, whose
+        finishing launch leaves the MLP group's squared norm in 512 partials."""
+        ema, ke, lo, hi = self.ema, self.knot_end, self.lo, self.hi
+        spans = [(max(ke, lo), min(self.flat.numel(), hi), self.lr, self.lr_dev, self.grad_clip,
+                  self._sumsq512 if one_call else self.sumsq, True)]
         if ke:
             spans.append((max(0, lo), min(ke, hi), self.basis_lr, self.basis_lr_dev, self.basis_clip, self.sumsq_basis,
                           False))
-        sq, groups = [], []
-        for a, b, lr, lr_dev, max_norm, parts, shadowed in spans:
+        out = []
+        for a, b, lr, lr_dev, max_norm, parts, mlp in spans:
             b = max(a, b)
-            sq += [self.grad[a:b], parts]
-            if b == a:
-                continue
             bufs = (self.flat[a:b], self.grad[a:b], self.m[a - lo:b - lo], self.v[a - lo:b - lo],
                     ema[a - lo:b - lo] if ema is not None else None)
-            # (unclipped, max_norm = 0, nothing reads the partials: the sharded descriptors have never named them then,
-            # every other launch does; kept as it was)
-            gr = N.make_adam_group(*bufs, lr, lr_dev, max_norm, None if self.shard and not clip else parts,
-                                   shadow=self._shadow(a) if shadowed else None)
-            gr.tensors = bufs + (lr_dev, parts)      # what N.adamw_ema takes when the group is stepped alone
-            groups.append(gr)
-        self._plan = (key, (sq, groups))
-        return self._plan[1]
+            # unclipped (max_norm = 0) nothing reads the partials: the one-call steps and the sharded optimiser have
+            # never named them then, every other launch does (kept as it was)
+            named = parts if (max_norm > 0 if one_call else self.grad_clip > 0 or not self.shard) else None
+            # replicated: the optimiser kernel re-rounds the bf16 operand copies of the MLP weights it has just stepped;
+            # sharded: they are refreshed from the gathered parameters.  The packed fp32 copies go to the one-call
+            # step alone: only its launch writes fragment order (FLAG_PACK_F32), a split one would round bf16 into them
+            shadow = None
+            if mlp and b > a and not self.shard:
+                shadow = self._pack_table if one_call and self._pack_table is not None else self._shadow(a)
+            out.append((bufs, lr, lr_dev, max_norm, parts, named, shadow))
+        return out
+
+    def _adam_plan(self):
+        """The split launches' view of the groups: (arguments of the sum-of-squares launch -- the gradient slice and the
+        partials of EVERY group, an empty one included --, an N.make_adam_group descriptor per non-empty group)."""
+        return self._cached("split", self._plan_key(), self._split_plan)
+
+    def _split_plan(self):
+        sq, groups = [], []
+        for bufs, lr, lr_dev, max_norm, parts, named, shadow in self._group_spans():
+            sq += [bufs[1], parts]
+            if bufs[0].numel():
+                gr = N.make_adam_group(*bufs, lr, lr_dev, max_norm, named, shadow=shadow)
+                gr.tensors = bufs + (lr_dev, parts)      # what N.adamw_ema takes when the group is stepped alone
+                groups.append(gr)
+        return sq, groups
+
+    def _knot_step_plan(self):
+        """(optimiser descriptor of the MLP group, group descriptor of the knots) of the one-call learnable step: the
+        same two groups in the form stdadk_train_step_knots_f32 takes them."""
+        return self._cached("one_call", self._plan_key(), self._one_call_plan)
+
+    def _one_call_plan(self):
+        """The one-call steps' view of the groups: an N.make_optim descriptor of the MLP group, which carries the shared
+        hyper-parameters, then the knots' group descriptor when there are learnable knots."""
+        (bufs, lr, lr_dev, max_norm, _, named, shadow), *knots = self._group_spans(one_call=True)
+        optim = N.make_optim(*bufs, lr, lr_dev, self.betas, self.eps, self.wd, self.step_dev, max_norm, named,
+                             self.ema_decay, shadow=shadow, nonfinite_step=self.nonfinite)
+        return (optim,) + tuple(N.make_adam_group(*kb, klr, klr_dev, knorm, knamed)
+                                for kb, klr, klr_dev, knorm, _, knamed, _ in knots)
 
     # (`_shard_*`: the plan's range is this rank's shard -- everything when the optimiser is replicated; the virtual-rank
     # tests and tools/asan_driver.py drive these two halves by hand under these names)
@@ -657,33 +665,24 @@ class TrainStep:
         st = self.state
         ws = self.ws if ws is None else ws
         flags = st.flags | (N.FLAG_PREBINNED if prebinned else 0)
-        Q = self.model.output_dim
+        Q, nc_lambda = self.model.output_dim, self.objective.nc_lambda
         if B == 0:
             # a rank without rows in this step (possible only with caller-made batches; run_epoch's schedule
             # never produces one): no data term; the penalty shares below need a batch's backward state
-            if self.learnable or self._sparsity is not None or (st.head is not None and self.nc_lambda != 0.0):
+            if self.learnable or self._sparsity is not None or (st.head is not None and nc_lambda != 0.0):
                 raise RuntimeError("an empty local batch cannot carry this rank's share of the parameter-level "
                                    "penalties; use run_epoch's schedule (stnf.distributed.epoch_schedule)")
             self.grad.zero_()
             return
         if st.head is not None:
             N.delta_head(st.delta, st.head[0], st.head[1])          # output layer of this step's delta
-        if idx is not None and not prebinned:
-            N.train_fwd_bwd_indexed(st.basis, st.desc, st.params, self.grads_t, coords, t, X, y, idx,
-                                    D.grad_scale(global_rows, Q), self.loss_sum, None, ws, flags,
-                                    seed=self.seed, step_dev=self.step_dev, aux_stream=self.aux_stream,
-                                    loss_desc=self._loss_desc(y.shape[1]))
-        else:
-            N.train_fwd_bwd(st.basis, st.desc, st.params, self.grads_t, coords, t, X, y, B,
-                            D.grad_scale(global_rows, Q), self.loss_sum, None, ws, flags,
-                            seed=self.seed, step_dev=self.step_dev, aux_stream=self.aux_stream,
-                            loss_desc=self._loss_desc(y.shape[1]))
+        door, rows = (N.train_fwd_bwd_indexed, (idx,)) if idx is not None and not prebinned else (N.train_fwd_bwd, (B,))
+        self._step_call(door, coords, t, X, y, rows, global_rows, ws, flags)
         if st.head is not None:
             # every rank adds 1/world of the parameter-level penalty gradient (the all-reduce SUMs);
             # the loss accumulator is in units of rows*Q like the data term
-            N.delta_head_backward(st.delta, self.d_head[0], self.d_head[1], self.nc_lambda / self.world,
-                                  self.nc_lambda * B * Q, self.d_delta,
-                                  self.loss_sum if self.nc_lambda != 0.0 else None)
+            N.delta_head_backward(st.delta, self.d_head[0], self.d_head[1], nc_lambda / self.world, nc_lambda * B * Q,
+                                  self.d_delta, self.loss_sum if nc_lambda != 0.0 else None)
         if self.learnable:
             kt = self._knot_train_desc(B * Q)
             N.knot_backward(st.basis, st.desc, st.params, coords, B, ws, st.flags, kt,
@@ -694,38 +693,19 @@ class TrainStep:
                        grad_scale=1.0 / self.world, loss_scale=float(B * Q), loss_sum=self.loss_sum)
 
     def _knot_train_desc(self, rows_q):
-        """The knot penalties' descriptor for a batch of rows_q = rows x Q objective terms (cached: rebuilt when a
-        setting or the batch size changes)."""
+        """The knot penalties' descriptor for a batch of rows_q = rows x Q objective terms (rebuilt when a setting or
+        the batch size changes)."""
         sb = self.model.spatial_basis
-        kkey = (sb.centers_init.data_ptr(), sb.gradient_damping, sb.damping_threshold, sb.damping_strength,
-                self.domain_w, self.movement_w, self.world, rows_q)
-        if self._knot_train is None or self._knot_train[0] != kkey:
-            self._knot_train = (kkey, N.make_knot_train(sb.centers_init, sb.gradient_damping, sb.damping_threshold,
-                                                        sb.damping_strength, self.domain_w, self.movement_w,
-                                                        penalty_grad_scale=1.0 / self.world,
-                                                        penalty_loss_scale=float(rows_q)))
-        return self._knot_train[1]
+        init = sb.centers_init
+        key = (init.data_ptr(), sb.gradient_damping, sb.damping_threshold, sb.damping_strength, self.domain_w,
+               self.movement_w, self.world, rows_q)
+        return self._cached("knot_train", key, self._make_knot_train, init, rows_q)
 
-    def _knot_step_plan(self):
-        """(optimiser descriptor of the MLP group, group descriptor of the knots) of the one-call learnable step: the
-        groups of _adam_plan -- the knots are the head [0, knot_end) of the flat buffers, the MLP the rest -- in the
-        form stdadk_train_step_knots_f32 takes them.  Cached like that plan: rebuilt only when a buffer, the boundary
-        or a rate changes."""
-        ema, ke = self.ema, self.knot_end
-        key = (self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-               ema.data_ptr() if ema is not None else 0, ke, self.lr, self.grad_clip, id(self.lr_dev),
-               self.basis_lr, self.basis_clip, id(self.basis_lr_dev))
-        if self._knot_plan is not None and self._knot_plan[0] == key:
-            return self._knot_plan[1]
-        optim = N.make_optim(self.flat[ke:], self.grad[ke:], self.m[ke:], self.v[ke:],
-                             ema[ke:] if ema is not None else None, self.lr, self.lr_dev, self.betas, self.eps, self.wd,
-                             self.step_dev, self.grad_clip, self._sumsq512 if self.grad_clip > 0 else None,
-                             self.ema_decay, shadow=self._shadow(ke), nonfinite_step=self.nonfinite)
-        knots = N.make_adam_group(self.flat[:ke], self.grad[:ke], self.m[:ke], self.v[:ke],
-                                  ema[:ke] if ema is not None else None, self.basis_lr, self.basis_lr_dev,
-                                  self.basis_clip, self.sumsq_basis if self.basis_clip > 0 else None)
-        self._knot_plan = (key, (optim, knots))
-        return self._knot_plan[1]
+    def _make_knot_train(self, init, rows_q):
+        sb = self.model.spatial_basis
+        return N.make_knot_train(init, sb.gradient_damping, sb.damping_threshold, sb.damping_strength, self.domain_w,
+                                 self.movement_w, penalty_grad_scale=1.0 / self.world,
+                                 penalty_loss_scale=float(rows_q))
 
     def set_virtual_rank(self, rank):
         """Tests of the data-parallel arithmetic on one GPU: play rank `rank` of `world_size` (dropout stream
@@ -744,15 +724,7 @@ class TrainStep:
 
     def _loss_desc(self, y_cols):
         """ABI loss descriptor for targets with `y_cols` columns (None = the plain MSE fast path)."""
-        Q = self.model.output_dim
-        if y_cols not in (1, Q):
-            raise RuntimeError(f"targets have {y_cols} columns; expected 1 or output_dim={Q}")
-        if self.loss_kind == "mse" and y_cols == Q:
-            return None
-        if y_cols not in self._loss_descs:
-            self._loss_descs[y_cols] = N.make_loss(self.loss_kind, Q, y_cols, self.quantile_levels,
-                                                   self.nc_weight, self.nc_power)
-        return self._loss_descs[y_cols]
+        return self.objective.desc(y_cols)
 
     def step(self, X, coords, t, y, global_rows=None):
         """One optimisation step on device tensors coords (B,2), t (B,1)/(B,), y (B,Q), X (B,p)|None.
@@ -781,7 +753,7 @@ class TrainStep:
         self.rows_seen += B
         # the kernels update the parameters through raw pointers (no autograd version bump): Predictors that
         # cache derived tensors (the delta head's output layer) watch this counter
-        self.model._engine_version = getattr(self.model, "_engine_version", 0) + 1
+        _bump_engine_version(self.model)
         if self._shadow_regions or self._pack_regions:
             self.model._bf16_key = self.model._bf16_master_key()      # the optimiser kernel has just rewritten them
 
@@ -820,7 +792,7 @@ class TrainStep:
 
         graphed = self.use_graph and not self.distributed
         # a captured graph reads the indices from a static buffer; the eager chain takes them as they are
-        src = ib if graphed else (idx if idx.is_contiguous() else idx.contiguous())
+        src = ib if graphed else _contig(idx)
         if self.uses_window and not graphed and (next_idx is not None or self._prepared is not None):
             # announcements are keyed on the CALLER's tensors (a .contiguous() copy has a new address every call)
             self._step_pipelined(coords_all, t_all, y_all, Xa, src, next_idx, B, global_rows, _idx_key(idx))
@@ -938,14 +910,14 @@ class TrainStep:
         resident = (coords_all, t_all, y_all, Xa)
         nxt = None
         if next_idx is not None:
-            nxt = next_idx if next_idx.is_contiguous() else next_idx.contiguous()
+            nxt = _contig(next_idx)
         # one-call step on a small batch: the NEXT batch is binned by extra workgroups of this step's optimiser launch
         # (no side stream, no cross-stream packets in the main queue: DESIGN.md section 8, "the bubble between steps")
         # (the one-call learnable step takes it in its weight-gradient launch, or declines)
         if (nxt is not None and (self._whole_step or self._knot_step) and self.inline_prep and not self.distributed
                 and nxt.numel() <= 8192 and nxt.dtype == torch.int64):
-            me = idx if idx.is_contiguous() else idx.contiguous()
-            if self._enqueue(Xa, coords_all, t_all, y_all, B, global_rows, idx=me, ws=pp["ws"][wsi],
+            # (`idx` is contiguous: step_indexed hands on `src`)
+            if self._enqueue(Xa, coords_all, t_all, y_all, B, global_rows, idx=idx, ws=pp["ws"][wsi],
                              prebinned=prebinned, nxt=(nxt, pp["ws"][1 - wsi])):
                 self._prepared = _Announced(_idx_key(next_idx), 1 - wsi, nxt, True)
             else:
@@ -1031,7 +1003,7 @@ class TrainStep:
             tmp = self.flat.clone()
             self.flat.copy_(self.ema)
             self.ema.copy_(tmp)
-        self.model._engine_version = getattr(self.model, "_engine_version", 0) + 1
+        _bump_engine_version(self.model)
         self.refresh_bf16()
 
     def first_nonfinite_step(self):

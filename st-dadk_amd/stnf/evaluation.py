@@ -26,16 +26,9 @@ class Evaluator:
 
     def __init__(self, model, loss="mse", quantile_levels=None, non_crossing_weight=0.0, non_crossing_power=1,
                  non_crossing_lambda=0.0, max_batch=65536, force_dense=False, process_group=None):
-        if loss not in ("mse", "pinball"):
-            raise ValueError(f"unknown loss '{loss}'; use 'mse' or 'pinball'")
         self.model = model
-        self.loss_kind = loss
-        self.quantile_levels = [float(q) for q in quantile_levels] if quantile_levels is not None else None
-        if loss == "pinball" and (self.quantile_levels is None or len(self.quantile_levels) != model.output_dim):
-            raise ValueError(f"pinball loss needs output_dim={model.output_dim} quantile levels")
-        self.nc_weight = 0.0 if model._has_delta else float(non_crossing_weight)
-        self.nc_power = int(non_crossing_power)
-        self.nc_lambda = float(non_crossing_lambda) if model._has_delta else 0.0
+        self.objective = losses.Objective(model, loss, quantile_levels, non_crossing_weight, non_crossing_power,
+                                          non_crossing_lambda)
         self.max_batch = int(max_batch)
         self.force_dense = bool(force_dense)
         self.pg = process_group
@@ -45,21 +38,12 @@ class Evaluator:
         self.acc = torch.zeros(N.EVAL_SLOTS, dtype=torch.float64, device=self.dev)
         self.sums = None               # the accumulator of the last call as host floats
         self._desc = None
-        self._loss_descs = {}
         self._ws = {}
         self._ema = None               # (key, parameter table over engine.ema, bf16 refresh table or None)
 
     # ------------------------------------------------------------------------------------
     def _loss_desc(self, y_cols):
-        Q = self.model.output_dim
-        if y_cols not in (1, Q):
-            raise RuntimeError(f"targets have {y_cols} columns; expected 1 or output_dim={Q}")
-        if self.loss_kind == "mse" and y_cols == Q:
-            return None
-        if y_cols not in self._loss_descs:
-            self._loss_descs[y_cols] = N.make_loss(self.loss_kind, Q, y_cols, self.quantile_levels, self.nc_weight,
-                                                   self.nc_power)
-        return self._loss_descs[y_cols]
+        return self.objective.desc(y_cols)
 
     def _workspace(self, basis, desc, B, flags):
         B = max(int(B), self.max_batch)
@@ -82,25 +66,14 @@ class Evaluator:
         key = (eng.ema.data_ptr(), eng.flat.data_ptr(), eng.dtype)
         if self._ema is not None and self._ema[0] == key:
             return self._ema[1], self._ema[2]
-        by_name = {n: (o, k) for n, o, k in eng.offsets}
-        names = {id(p): n for n, p in m.named_parameters()}
-        first_w = m._body[0].weight
-        tensors = []
-        for p in m._body_params():
-            o, k = by_name[names[id(p)]]
-            v = eng.ema[o:o + k]
-            tensors.append(v.view(p.shape[1], p.shape[0]) if p is first_w else v.view(p.shape))
+        lay = eng.layout
+        tensors = [lay.view(eng.ema, p) for p in m._body_params()]
         pairs, table = None, None
         if eng._shadow_regions:
             # bf16 mode: operand copies of the EMA values in buffers of our own, re-rounded at the start of every pass
-            lins = m._linears()
-            pairs, regions = [None] * len(lins), []
-            for l in range(1, len(m.hidden_dims)):
-                h, hp = lins[l].weight.shape
-                wb = torch.empty(h, hp, device=self.dev, dtype=torch.bfloat16)
-                wt = torch.empty(hp, h, device=self.dev, dtype=torch.bfloat16)
-                pairs[l] = (wb, wt)
-                regions.append((by_name[names[id(lins[l].weight)]][0], h, hp, wb, wt))
+            pairs, regions = lay.hidden_copies(
+                lambda h, hp: (torch.empty(h, hp, device=self.dev, dtype=torch.bfloat16),
+                               torch.empty(hp, h, device=self.dev, dtype=torch.bfloat16)))
             table = N.make_bf16_shadow(regions)
         params = m._pack(tensors, bf16=pairs)
         params._views = (tensors, pairs)          # the descriptors hold raw addresses: keep the tensors alive
@@ -163,12 +136,12 @@ class Evaluator:
         for idx in batches:
             B = idx.numel()
             N.eval_indexed(basis, desc, ptab, dataset.coords, t_all, X_all, y_all,
-                           idx if idx.is_contiguous() else idx.contiguous(), ldesc, metric_col, 1.0 / (B * Q), acc,
+                           N._contig(idx), ldesc, metric_col, 1.0 / (B * Q), acc,
                            None, ws, flags)
-        if self.nc_lambda > 0.0 and len(batches):
+        if self.objective.nc_lambda > 0.0 and len(batches):
             # parameter-level penalty of the delta head: the same value in every batch's objective
             p_nc = losses.compute_p_nc_delta_penalty(list(m.delta_params))
-            acc[N.EVAL_OBJECTIVE] += (self.nc_lambda * len(batches)) * p_nc.double()
+            acc[N.EVAL_OBJECTIVE] += (self.objective.nc_lambda * len(batches)) * p_nc.double()
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.pg) > 1:
             dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=self.pg)
         self.sums = acc.tolist()                                   # the call's ONE host sync
@@ -181,7 +154,7 @@ class Evaluator:
         mse = sums[N.EVAL_SSE] / rows
         out = {"mse": mse, "mae": sums[N.EVAL_SAE] / rows, "rmse": mse ** 0.5,
                "loss": sums[N.EVAL_OBJECTIVE] / nb, "rows": int(sums[N.EVAL_ROWS])}
-        if self.loss_kind == "pinball":
+        if self.objective.kind == "pinball":
             checks = [sums[N.EVAL_CHECK + q] / rows for q in range(Q)]
             if Q == 1:
                 out["check_loss"] = checks[0]

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .flat import Cached
 
 
 def _sum(desc, y_pred, y):
@@ -102,3 +103,31 @@ def compute_crps_multi_quantile(preds, y_true, quantile_levels, weights=None):
     if y_true.ndim > 1:
         y_true = y_true.flatten()
     return compute_crps({q: preds[:, i] for i, q in enumerate(quantile_levels)}, y_true, weights=weights)
+
+
+class Objective(Cached):
+    """The objective's settings as TrainStep and Evaluator take them -- loss "mse" or "pinball" with `quantile_levels`,
+    the prediction-level non-crossing penalty (weight, power; not with the delta head) or the delta head's
+    parameter-level one (`nc_lambda`) -- validated once, and the ABI loss descriptors made from them."""
+
+    def __init__(self, model, loss="mse", quantile_levels=None, non_crossing_weight=0.0, non_crossing_power=1,
+                 non_crossing_lambda=0.0):
+        if loss not in ("mse", "pinball"):
+            raise ValueError(f"unknown loss '{loss}'; use 'mse' or 'pinball'")
+        self.kind, self.Q = loss, model.output_dim
+        self.quantile_levels = [float(q) for q in quantile_levels] if quantile_levels is not None else None
+        if loss == "pinball" and (self.quantile_levels is None or len(self.quantile_levels) != self.Q):
+            raise ValueError(f"pinball loss needs output_dim={self.Q} quantile levels")
+        self.nc_weight = 0.0 if model._has_delta else float(non_crossing_weight)
+        self.nc_power = int(non_crossing_power)
+        self.nc_lambda = float(non_crossing_lambda) if model._has_delta else 0.0
+        self._cache = {}
+
+    def desc(self, y_cols):
+        """ABI loss descriptor for targets with `y_cols` columns (None = the plain MSE fast path)."""
+        if y_cols not in (1, self.Q):
+            raise RuntimeError(f"targets have {y_cols} columns; expected 1 or output_dim={self.Q}")
+        if self.kind == "mse" and y_cols == self.Q:
+            return None
+        return self._cached(y_cols, None, N.make_loss, self.kind, self.Q, y_cols, self.quantile_levels,
+                            self.nc_weight, self.nc_power)      # (the settings are fixed: the slot is the key)

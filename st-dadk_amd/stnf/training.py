@@ -22,6 +22,7 @@ import torch
 
 from .engine import TrainStep
 from .evaluation import Evaluator
+from .flat import _bump_engine_version
 
 
 def loss_settings(model, config):
@@ -151,7 +152,7 @@ def _ema_full(eng):
 def _load_flat(eng, flat_values):
     """Overwrite the live parameters with `flat_values` (flat layout); derived copies follow."""
     eng.flat.copy_(flat_values)
-    eng.model._engine_version = getattr(eng.model, "_engine_version", 0) + 1
+    _bump_engine_version(eng.model)
     eng.refresh_bf16()
 
 

@@ -6,6 +6,8 @@ instead of a Python loop of three kernels per parameter."""
 import torch
 import torch.nn as nn
 
+from ..flat import _bump_engine_version
+
 
 class ModelEMA:
     def __init__(self, model: nn.Module, decay: float = 0.999):
@@ -50,7 +52,7 @@ class ModelEMA:
     def _touched(self):
         """Everything derived from the weights (a Predictor's cached output layer / transposed W0, an engine's bf16
         operand copies) keys on the parameters' versions and on this counter: both move with every swap."""
-        self.model._engine_version = getattr(self.model, "_engine_version", 0) + 1
+        _bump_engine_version(self.model)
 
     def state_dict(self):
         return {'decay': self.decay, 'shadow': self.shadow}
