@@ -176,6 +176,9 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
   if (has_ema) ema = fmaf(ema_decay, ema, (1.f - ema_decay) * p);
 }
 
+// partials of the clip norm a thread requests at once: 6 x 256 cover the headline step's ~1 300 in one round trip
+constexpr int PARTS_U = 6;
+
 // `block` of `nblocks` groups of 256 threads; `tid` = the thread's index in its group, `red4` = four floats of LDS of
 // the group (a group is a whole workgroup in adamw_ema_kernel, a quarter of one in adamw_bin_kernel: the barrier in
 // the middle is the workgroup's, which every group of the workgroup reaches)
@@ -211,9 +214,20 @@ __device__ __forceinline__ void adamw_ema_block(const AdamArgs &a, const int blo
   }
   float coef = 1.f;
   if (a.max_norm > 0.f && a.sumsq) {
-    // sum of the partials by the group's 256 threads, same order in every group (L2-resident, a few hundred floats)
+    // sum of the partials by the group's 256 threads, same order in every group (L2-resident, a few hundred floats):
+    // thread t adds entries t, t + 256, ... in that order and skips what lies beyond n_parts.  PARTS_U of them are
+    // requested at once (index clamped: unconditional loads) and then added: one round trip per PARTS_U entries --
+    // added one by one as they were loaded, each entry was a round trip of its own BEHIND the groups' HBM burst, six
+    // of them in every block of the headline step (~1 300 partials), 2 us of its 19.5 (profiles/adamw_stream.md)
     float ss = 0.f;
-    for (int i = tid; i < a.n_parts; i += 256) ss += a.sumsq[i];
+    for (int base = 0; base < a.n_parts; base += 256 * PARTS_U) {
+      float q[PARTS_U];
+#pragma unroll
+      for (int u = 0; u < PARTS_U; ++u) q[u] = a.sumsq[min(base + tid + 256 * u, a.n_parts - 1)];
+#pragma unroll
+      for (int u = 0; u < PARTS_U; ++u)
+        if (base + tid + 256 * u < a.n_parts) ss += q[u];
+    }
     ss = wave_sum(ss);
     if ((tid & 63) == 0) red4[tid >> 6] = ss;
     __syncthreads();
@@ -253,15 +267,14 @@ __device__ __forceinline__ void adamw_ema_block(const AdamArgs &a, const int blo
       __builtin_nontemporal_store((nt4){m.x, m.y, m.z, m.w}, reinterpret_cast<nt4 *>(a.m) + j);
       __builtin_nontemporal_store((nt4){v.x, v.y, v.z, v.w}, reinterpret_cast<nt4 *>(a.v) + j);
       if (a.ema) __builtin_nontemporal_store((nt4){e.x, e.y, e.z, e.w}, reinterpret_cast<nt4 *>(a.ema) + j);
+      // operand copies (bf16, or the fragment-order fp32 ones) of a group inside the regions' range: from the
+      // registers it was just computed in.  (A pass of its own behind the loop, re-reading what the thread had
+      // stored, was one more dependent round trip at the end of the launch -- the hidden weights lie last in the
+      // flat buffer, their groups are a thread's last.  The table walk in here once cost the stream 40 VGPRs; with
+      // the walk rolled (shadow_store) it costs one, 73: six waves per SIMD, what the grid uses.)
+      if (a.sh.n > 0 && 4 * j >= a.sh.lo && 4 * j < a.sh.hi) shadow_store(a.sh, 4 * j, p);
     }
     done = n4 * 4;
-    // bf16 operand copies (STDADK_FLAG_BF16): a pass of its own over this thread's float4 groups inside the
-    // regions' range, re-reading what the thread itself has just stored -- inside the loop above the table walk
-    // cost the whole stream 40 VGPRs (5 instead of 8 waves per SIMD)
-    if (a.sh.n > 0) {
-      for (int64_t j = i0; j < n4; j += stride)
-        if (4 * j >= a.sh.lo && 4 * j < a.sh.hi) shadow_store(a.sh, 4 * j, reinterpret_cast<const float4 *>(a.p)[j]);
-    }
   }
   for (int64_t j = done + i0; j < a.n; j += stride) {
     float p = a.p[j], m = a.m[j], v = a.v[j];
@@ -362,7 +375,7 @@ static int fill_adam(AdamArgs &a, const char *what, const stdadk_adam_group *gr,
 
 // The one place that launches them: `ng` (1 or 2) filled groups; `bin` (one group only): the next batch to bin with them.
 static int launch_adam(const AdamArgs *a, int ng, const BinSmallArgs *bin, hipStream_t st) {
-  // grid: at most 6 workgroups per CU = ONE resident round of the chip (72 VGPRs: 7 fit), each thread walking
+  // grid: at most 6 workgroups per CU = ONE resident round of the chip (73 VGPRs: 6 fit), each thread walking
   // its float4 groups with a grid stride -- a second, partly filled round of one-group threads cost 3 us of the
   // 20 (MI355X, 2.76 M parameters, tools/sweep_knobs.sh: 2 695 blocks 20.6 us, 1 536 blocks 17.6 us = 5.6 TB/s)
   int64_t nb[2] = {0, 0};
