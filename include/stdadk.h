@@ -574,6 +574,66 @@ int stdadk_train_step_knots_f32(const stdadk_basis_desc *basis, const stdadk_mlp
                                 float *d_centers, float *d_log_bw, const stdadk_adam_group *knots,
                                 stdadk_stream_t stream);
 
+/* The one-call step of a model with the delta-reparameterised head (multi-quantile regression with
+ * use_delta_reparameterization, the configuration of the reference's Table 4.4), fixed OR learnable knots.  Added
+ * under ABI 10 as a new entry point with a struct nobody else uses: no existing struct, signature or default changes,
+ * so STDADK_ABI_VERSION stays 10.
+ * = stdadk_delta_head_f32 + stdadk_train_fwd_bwd(_indexed)_f32 + stdadk_delta_head_backward_f32 [+
+ * stdadk_knot_backward_f32] + clip norm(s) + AdamW/EMA, as one call.  The arguments of stdadk_train_step_knots_f32 plus
+ * `head`:
+ *   delta, ldd             [Q, ldd] the head's parameter rows (column 0 the bias share, 1..d the weights), inside
+ *                          [opt->p, opt->p + opt->n); ldd >= d + 1 with d = the last hidden width, Q = mlp->out_dim >= 2
+ *   d_delta, ldg           the same rows of the gradient, overwritten: inside [opt->g, opt->g + opt->n) at the offset
+ *                          `delta` has in the parameters, ldg == ldd.  Columns beyond d + 1 are padding, kept zero by
+ *                          the caller
+ *   lambda_grad, lambda_loss   as stdadk_delta_head_backward_f32 takes them: lambda_grad * dP_nc/d delta is added to
+ *                          d_delta, lambda_loss * P_nc(delta) into loss_sum (0: nothing is added)
+ * The output layer is DERIVED: params->W[L], b[L] (L = mlp->n_hidden) are rebuilt from `delta` by delta_head_kernel in
+ * front of the forward (the first launch of the call's chain behind the validation; only the batch's own
+ * preparation may precede it) in every call, so whatever else rewrites the parameters between calls (EMA swaps, a loaded state,
+ * evaluation) needs no refresh.  grads->W[L], b[L] are scratch that holds the output layer's gradient after the call, as
+ * after stdadk_train_fwd_bwd_f32; they are the one exception to "every tensor of `grads` lies in [opt->g, opt->g + n)":
+ * they must lie OUTSIDE it.  The MLP group's clip norm is the norm of the flat gradient: the d_delta entries count, the
+ * scratch does not.
+ * Knots: kt, d_centers, d_log_bw, knots all NULL = fixed knots, ONE parameter group, and the next batch is carried by
+ * stdadk_train_step_next_f32's rules (packed fp32 copies, STDADK_FLAG_PACK_F32, exactly where that door keeps them);
+ * all given (kt itself may still be NULL as there) = the two-group step of stdadk_train_step_knots_f32, whose rules apply
+ * unchanged, STDADK_FLAG_PACK_F32 refused; d_centers / d_log_bw / knots given only in part is STDADK_E_ARG.
+ * A delta step always ends in the finishing launch (step_finish_kernel), which has three kinds of workgroup: the
+ * step's fixed-order sums, the knot tiles (none with fixed knots) and ONE head workgroup.  The head workgroup folds
+ * (dWo, dbo) into d_delta with the gradient and value of P_nc(delta), in the arithmetic and order of
+ * stdadk_delta_head_backward_f32, and leaves ONE clip-norm partial, the squares of what it wrote.  Where a launch in
+ * front of the finishing launch runs fixed-order sums anyway (the weight-gradient launch from 49 152 rows, the
+ * reductions launch of a learnable step on the materialising route) it finishes the output layer's two sums too and
+ * the head workgroup reads them, clearing their slots of squares.  Where the finishing launch itself carries the
+ * reductions (window route below 49 152 rows, fixed knots on the materialising route) the head workgroup runs those
+ * two sums itself, in the reductions launch's per-element order, before it folds: no workgroup of the launch waits
+ * for another.  With fixed knots the launch stands where the reductions launch of the
+ * same step without the head stands; where that step has none (window route from 49 152 rows) it is one added launch.
+ * opt->step_dev advances exactly once per call, in the finishing launch.
+ * Refusals, each STDADK_E_ARG before anything is enqueued (a refused call leaves parameters, moments, EMA, step counter
+ * and loss sum untouched): head NULL or Q < 2; ldd < d + 1; delta outside the parameter range or d_delta outside the
+ * gradient range or at another offset; ldg != ldd; grads->W[L] / b[L] inside the gradient range; a partial knot
+ * description; STDADK_FLAG_PACK_F32 with knots; a shadow on the knot group.  Under STDADK_DRY_RUN=1 the door validates
+ * and plans like every other. */
+typedef struct stdadk_delta_step {
+  const float *delta;
+  int64_t ldd;
+  float *d_delta;
+  int64_t ldg;
+  float lambda_grad, lambda_loss;
+} stdadk_delta_step;
+int stdadk_train_step_delta_f32(const stdadk_basis_desc *basis, const stdadk_mlp_desc *mlp,
+                                const stdadk_mlp_tensors *params, const stdadk_mlp_tensors *grads,
+                                const float *coords_all, const float *t_all, const float *X_all, const float *y_all,
+                                const int64_t *idx, int64_t B, float grad_scale, const stdadk_loss_desc *loss,
+                                const stdadk_sparsity_desc *sparsity, float *loss_sum, void *workspace,
+                                size_t workspace_bytes, uint64_t drop_seed, int32_t flags, const stdadk_optim_desc *opt,
+                                const int64_t *next_idx, int64_t next_B, int32_t next_y_cols, void *next_workspace,
+                                size_t next_workspace_bytes, int32_t *next_binned, const stdadk_knot_train *kt,
+                                float *d_centers, float *d_log_bw, const stdadk_adam_group *knots,
+                                const stdadk_delta_step *head, stdadk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Validation (ABI 9): evaluate_model and the validation half of train_model's epoch
  * (scripts/train_st_interp.py:737-806,884-961) on rows idx[b] (int64, device) of the RESIDENT arrays, forward only.

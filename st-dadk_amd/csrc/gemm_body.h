@@ -370,11 +370,9 @@ __device__ __forceinline__ float block4_sum(float v, float *red) {
 constexpr int REDUCE_TALL_COLS = 16;
 // One workgroup of a table of fixed-order sums dst_j[i] = sum_s src_j[s*stride_j + i] (see reduce_jobs_kernel);
 // returns (every thread) the squares of what this thread wrote.  smem: >= 4 * 64 floats.
-__device__ __forceinline__ float reduce_job_block(const ReduceGroup &grp, int block, float *smem) {
-  int j = 0;
-  while (j + 1 < grp.n && block >= grp.first_block[j + 1]) ++j;
-  const ReduceJob &jb = grp.job[j];
-  const int blk = block - grp.first_block[j];
+// (reduce_one_job_block: workgroup `blk` of the one job `jb`, for callers that keep jobs outside a table -- the head
+// workgroup of step_finish_kernel)
+__device__ __forceinline__ float reduce_one_job_block(const ReduceJob &jb, const int blk, float *smem) {
   float sq = 0.f;
   if (jb.wide) {
     const int c = (blk * 256 + threadIdx.x) * 4;
@@ -432,6 +430,11 @@ __device__ __forceinline__ float reduce_job_block(const ReduceGroup &grp, int bl
     }
   }
   return sq;
+}
+__device__ __forceinline__ float reduce_job_block(const ReduceGroup &grp, int block, float *smem) {
+  int j = 0;
+  while (j + 1 < grp.n && block >= grp.first_block[j + 1]) ++j;
+  return reduce_one_job_block(grp.job[j], block - grp.first_block[j], smem);
 }
 
 // Finishing step of one K slice of a grouped job's output tile (FinArgs): once the slice's slab stores

@@ -21,6 +21,9 @@ inline bool loss_is_plain_mse(const LossDev &L, int Q) { return L.kind == STDADK
 int launch_loss(const LossDev &L, const float *yp, const float *y, int64_t B, int Q, float scale, float *dY,
                 float *loss_sum, hipStream_t st);
 
+// the derived output layer of the delta head (stdadk_delta_head_f32): Wo [Q,d], bo [Q] from delta [Q, ldd]
+int launch_delta_head(const float *delta, int64_t ldd, int Q, int d, float *Wo, float *bo, hipStream_t st);
+
 // tau of output q without indexing the kernel-argument array by a vector register
 __device__ __forceinline__ float loss_tau(const LossDev &L, int q) {
   float t = L.tau[0];

@@ -1,6 +1,7 @@
 // N3: batch objectives (stdadk_loss_f32) and the delta-reparameterised head
 // (stdadk_delta_head_f32 / stdadk_delta_head_backward_f32).  See include/stdadk.h.
 #include "loss.h"
+#include "delta_body.h"
 
 namespace stdadk {
 
@@ -83,6 +84,12 @@ __global__ void delta_head_kernel(const float *__restrict__ delta, int64_t ldd, 
   }
 }
 
+int launch_delta_head(const float *delta, int64_t ldd, int Q, int d, float *Wo, float *bo, hipStream_t st) {
+  STDADK_LAUNCH(delta_head_kernel, dim3((unsigned)ceil_div(d + 1, 256)), dim3(256), 0, st, delta, ldd, Q, d, Wo, bo);
+  STDADK_CHECK_LAUNCH("delta_head");
+  return 0;
+}
+
 // one workgroup: S_k by block reduction, then the reverse cumulative sums per column
 __global__ __launch_bounds__(256) void delta_head_bwd_kernel(const float *__restrict__ delta,
                                                             const float *__restrict__ dWo,
@@ -90,37 +97,8 @@ __global__ __launch_bounds__(256) void delta_head_bwd_kernel(const float *__rest
                                                             int Q, int d, float lam_g, float lam_l,
                                                             float *__restrict__ d_delta,
                                                             float *__restrict__ loss_sum) {
-  __shared__ float red[4];
-  __shared__ float wS[STDADK_MAX_Q];     // share of max(delta_k0, S_k) that flows into S_k
-  __shared__ float Psum;
-  const int tid = threadIdx.x;
-  if (tid == 0) Psum = 0.f;
-  if (tid < STDADK_MAX_Q) wS[tid] = 0.f;
-  __syncthreads();
-  for (int k = 1; k < Q; ++k) {
-    float s = 0.f;
-    for (int j = 1 + tid; j <= d; j += 256) s += fmaxf(-delta[k * ldd + j], 0.f);
-    s = wave_sum(s);
-    if ((tid & 63) == 0) red[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) {
-      const float S = red[0] + red[1] + red[2] + red[3];
-      const float d0 = delta[k * ldd];
-      wS[k] = S > d0 ? 1.0f : (S == d0 ? 0.5f : 0.f);
-      Psum += d0 - fmaxf(d0, S);
-    }
-    __syncthreads();
-  }
-  for (int j = tid; j <= d; j += 256) {
-    float acc = 0.f;
-    for (int k = Q - 1; k >= 0; --k) {
-      acc += j == 0 ? dbo[k] : dWo[(int64_t)k * d + j - 1];
-      float gp = 0.f;
-      if (k >= 1) gp = j == 0 ? wS[k] : (delta[k * ldd + j] <= 0.f ? wS[k] : 0.f);
-      d_delta[k * ldd + j] = fmaf(lam_g, gp, acc);
-    }
-  }
-  if (tid == 0 && loss_sum && lam_l != 0.f) atomicAdd(loss_sum, lam_l * Psum);
+  __shared__ DeltaHeadShared sh;
+  delta_head_bwd_body<false>(delta, dWo, dbo, ldd, Q, d, lam_g, lam_l, d_delta, loss_sum, sh);
 }
 
 }  // namespace stdadk
@@ -144,10 +122,7 @@ extern "C" int stdadk_delta_head_f32(const float *delta, int64_t ldd, int32_t Q,
   STDADK_REQUIRE(Q >= 1 && Q <= STDADK_MAX_Q && d >= 1 && ldd >= d + 1, STDADK_E_ARG,
                  "delta_head: bad sizes Q=%d d=%d ldd=%lld", Q, d, (long long)ldd);
   STDADK_REQUIRE(delta && Wo && bo, STDADK_E_ARG, "delta_head: NULL pointer");
-  STDADK_LAUNCH(delta_head_kernel, dim3((unsigned)ceil_div(d + 1, 256)), dim3(256), 0, (hipStream_t)stream,
-                delta, ldd, Q, d, Wo, bo);
-  STDADK_CHECK_LAUNCH("delta_head");
-  return 0;
+  return launch_delta_head(delta, ldd, Q, d, Wo, bo, (hipStream_t)stream);
 }
 
 extern "C" int stdadk_delta_head_backward_f32(const float *delta, const float *dWo, const float *dbo,

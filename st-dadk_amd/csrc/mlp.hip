@@ -527,6 +527,10 @@ struct StepRide {
   const stdadk_knot_train *kt = nullptr;
   float *d_centers = nullptr, *d_log_bw = nullptr, *knot_sq = nullptr;
   int32_t *finish_inc = nullptr;
+  // the delta head (stdadk_train_step_delta_f32): the derived output layer is rebuilt in front of the forward and the
+  // head workgroup of the finishing launch folds its gradient into the delta rows (close_step fills sq_part / pending /
+  // job); with fixed knots too the step then ends in that launch (finish_inc)
+  const HeadFinishArgs *head = nullptr;
 };
 struct StepOut { const float *sq_parts = nullptr; int sq_n = 0; bool binned_next = false; };
 struct NextBatch {   // the batch a one-call step announces (stdadk_train_step_next_f32)
@@ -607,6 +611,8 @@ struct DwJobs {
   ReduceGroup rg;
   bool all_grouped = true;      // false: a product was not groupable and went out as a stand-alone GEMM
   bool dw0_in_group = false;    // materialising path: dW0^T joined the group
+  bool head_apart = false;      // delta step: the output layer's two sums are head_job, not in rg -- the head workgroup
+  ReduceJob head_job[2];        // of the finishing launch runs them (and their squares stay out of the clip norm)
 };
 
 // fork/join between the main and the auxiliary stream (events are created once per thread)
@@ -839,8 +845,9 @@ static int tail_row_launch(const Ctx &c, const float *dY, bool layer0_dense, int
 // launches nothing -- except a product that cannot join the group, which goes out as a stand-alone GEMM right here.
 // `extra`: products with dZ_0 that ride along; `features` (materialising path, else NULL): dW0^T joins while it is a
 // split-K product; `fin` 2: the slabs of the products are summed by the merged launch itself, not by a reduce job.
+// `head_apart` (delta step): the output layer's two sums go to j.head_job, not into the table.
 static int collect_dw_jobs(const Ctx &c, int64_t n_part, int fin, const ExtraProduct *extra, int n_extra,
-                           const float *features, int64_t ldf, DwJobs &j) {
+                           const float *features, int64_t ldf, DwJobs &j, bool head_apart = false) {
   const stdadk_mlp_desc *d = c.d;
   const stdadk_mlp_tensors *G = c.G;
   float *ws = c.ws;
@@ -877,8 +884,14 @@ static int collect_dw_jobs(const Ctx &c, int64_t n_part, int fin, const ExtraPro
     j.all_grouped = false;
     return gemm_run(A, lda, true, Bm, ldb, true, M, N, (int)B, nullptr, C, N, slab + slab_off, false, nullptr, c.st);
   };
-  add_reduce(part, G->W[L], Q * hL, (int)n_part, (int64_t)Q * (hL + 1));
-  add_reduce(part + Q * hL, G->b[L], Q, (int)n_part, (int64_t)Q * (hL + 1));
+  if (head_apart) {
+    j.head_apart = true;
+    j.head_job[0] = ReduceJob{part, G->W[L], Q * hL, (int)n_part, (int64_t)Q * (hL + 1)};
+    j.head_job[1] = ReduceJob{part + Q * hL, G->b[L], Q, (int)n_part, (int64_t)Q * (hL + 1)};
+  } else {
+    add_reduce(part, G->W[L], Q * hL, (int)n_part, (int64_t)Q * (hL + 1));
+    add_reduce(part + Q * hL, G->b[L], Q, (int)n_part, (int64_t)Q * (hL + 1));
+  }
   for (int l = L - 1; l >= 0; --l) {
     const int h = d->hidden[l];
     const float *pp = ws + pl.partl[l];
@@ -913,10 +926,11 @@ static int collect_dw_jobs(const Ctx &c, int64_t n_part, int fin, const ExtraPro
 }
 
 // (c) the two grouped launches; materialising path (`features`): then dW0 as a stand-alone GEMM unless it joined the group
-static int launch_dw_jobs(const Ctx &c, DwJobs &j, const float *features, int64_t ldf) {
+// (`reduce` false: the reductions are left to the caller's finishing launch)
+static int launch_dw_jobs(const Ctx &c, DwJobs &j, const float *features, int64_t ldf, bool reduce = true) {
   int rc = launch_gemm_tn_grouped(j.gg, c.st);
   if (rc) return rc;
-  rc = launch_reduce_jobs(j.rg, c.st);
+  if (reduce) rc = launch_reduce_jobs(j.rg, c.st);
   if (rc || !features || j.dw0_in_group) return rc;
   const stdadk_mlp_desc *d = c.d;
   const int h = d->hidden[0];
@@ -1481,6 +1495,11 @@ static int finishing_mode(const Ctx &c) {
 //                                           region workgroups stay a reductions launch of their own)
 //   learnable, nothing pending (mode 2,     the finishing launch with zero reduce workgroups, last
 //     separate launches, generic kernels)
+//   delta head (ride.head)                  always ends in the finishing launch, learnable or not, whose LAST workgroup is
+//                                           the head's: it runs the output layer's two sums itself where the fused tail
+//                                           left them as column partials (they are in no reduce table then and leave no
+//                                           squares) and adds ONE slot behind the others.  Fixed knots: the launch also
+//                                           stands in for the reductions launch of the separate launches' row
 static int close_step(const Ctx &c, DwJobs *jobs, bool merged, int fin, const float *coords, StepOut &out) {
   const StepRide &r = *c.ride;
   float *ws = c.ws;
@@ -1488,6 +1507,14 @@ static int close_step(const Ctx &c, DwJobs *jobs, bool merged, int fin, const fl
   const bool forked = jobs && c.aux;      // window path: the per-knot gather already runs on the auxiliary stream
   const bool sq = jobs && r.gradsq_parts && jobs->all_grouped;
   const int nrb = jobs ? reduce_jobs_block_count(jobs->rg) : 0;
+  const bool fin_launch = r.knots || r.head;    // the step ends in the finishing launch
+  const int hs = r.head ? 1 : 0;                // the head workgroup's ONE slot behind the others
+  float *head_slot = nullptr;
+  // the output layer's jobs where they stayed in the table (head_sums_pending false): the first two, their squares in
+  // the first nhb slots of the reduce / tall workgroups
+  const bool head_in_table = r.head && jobs && !jobs->head_apart;
+  const int nhb = head_in_table ? jobs->rg.first_block[2] : 0;
+  float *head_zero = nullptr;
   bool reductions_pending = false;
   int rc = 0;
   if (merged && fin == 2) {
@@ -1497,44 +1524,52 @@ static int close_step(const Ctx &c, DwJobs *jobs, bool merged, int fin, const fl
     f.slots = sq ? ws + c.pl.fin_slots : nullptr;
     f.step_inc = sq ? r.step_inc : nullptr;
     int n_slots = 0;
-    rc = window_dw_all(c, *jobs, &f, &n_slots, c.pl.fin_cap);
-    if (sq) { out.sq_parts = f.slots; out.sq_n = n_slots; }
+    rc = window_dw_all(c, *jobs, &f, &n_slots, c.pl.fin_cap - hs);
+    if (sq) { out.sq_parts = f.slots; out.sq_n = n_slots + hs; head_slot = f.slots + n_slots; }
+    if (sq && head_in_table) {      // the tall workgroups' slots start behind the output tiles'
+      int nt = 0;
+      for (int i = 0; i < jobs->gg.n; ++i) nt += (int)(ceil_div(jobs->gg.job[i].M, 64) * ceil_div(jobs->gg.job[i].N, 64));
+      head_zero = f.slots + nt;
+    }
   } else if (merged && fin == 1 && sq && nrb > 0) {
     // the knot workgroups leave the squares of the rows they write (no second pass over dW0^T), the reductions
     // launch adds the partials of what it writes behind them
     FinArgs f;
     f.slots = ws + c.pl.fin_slots;
     int n_knot = 0;
-    rc = window_dw_all(c, *jobs, &f, &n_knot, c.pl.fin_cap - nrb);
+    rc = window_dw_all(c, *jobs, &f, &n_knot, c.pl.fin_cap - nrb - hs);
     jobs->rg.sq_parts = f.slots + n_knot;
     jobs->rg.step_inc = r.step_inc;
-    out.sq_parts = f.slots; out.sq_n = n_knot + nrb;
+    out.sq_parts = f.slots; out.sq_n = n_knot + nrb + hs; head_slot = f.slots + n_knot + nrb;
     reductions_pending = true;
   } else if (merged) {
     rc = window_dw_all(c, *jobs);
     if (rc) return rc;
-    if (sq && nrb > 0 && nrb <= STDADK_GRADSQ_PARTS - 256) {
+    if (sq && nrb > 0 && nrb <= STDADK_GRADSQ_PARTS - 256 - hs) {
       // every gradient of the step is either an output of the reductions launch or a spatial row of dW0^T (final
       // after the launch above): their squared norm comes out of the same launch
       ReduceGroup own;
-      ReduceGroup &region = r.knots ? own : jobs->rg;
+      ReduceGroup &region = fin_launch ? own : jobs->rg;
       region.sq_region_parts = r.gradsq_parts;
       region.sq_src = c.G->W[0] + (size_t)b->p * c.d->hidden[0];
       region.sq_n = (int64_t)b->Ks * c.d->hidden[0];
-      if (r.knots) rc = launch_reduce_jobs(region, c.st);
+      if (fin_launch) rc = launch_reduce_jobs(region, c.st);
       jobs->rg.sq_parts = r.gradsq_parts + 256;
       jobs->rg.step_inc = r.step_inc;
-      out.sq_parts = r.gradsq_parts; out.sq_n = 256 + nrb;
+      out.sq_parts = r.gradsq_parts; out.sq_n = 256 + nrb + hs; head_slot = r.gradsq_parts + 256 + nrb;
     }
     reductions_pending = true;
   } else if (jobs) {
-    if (sq && !c.window && jobs->dw0_in_group && nrb > 0 && nrb <= STDADK_GRADSQ_PARTS) {
+    if (sq && !c.window && jobs->dw0_in_group && nrb > 0 && nrb <= STDADK_GRADSQ_PARTS - hs) {
       // one-call step: every gradient of the step is an output of this reductions launch, which then also
       // leaves the squared-norm partials for the clip (no region beside them)
       jobs->rg.sq_parts = r.gradsq_parts; jobs->rg.step_inc = r.step_inc;
-      out.sq_parts = r.gradsq_parts; out.sq_n = nrb;
+      out.sq_parts = r.gradsq_parts; out.sq_n = nrb + hs; head_slot = r.gradsq_parts + nrb;
+      if (head_in_table) head_zero = r.gradsq_parts;
     }
-    rc = launch_dw_jobs(c, *jobs, c.window ? nullptr : ws + c.pl.feats, c.pl.ldf);
+    // (a fixed-knot delta step: the finishing launch stands where the reductions launch stood and carries its jobs)
+    reductions_pending = r.head && !r.knots;
+    rc = launch_dw_jobs(c, *jobs, c.window ? nullptr : ws + c.pl.feats, c.pl.ldf, !reductions_pending);
   }
   if (rc) return rc;
   if (merged) out.binned_next = r.bin_next != nullptr;
@@ -1542,16 +1577,39 @@ static int close_step(const Ctx &c, DwJobs *jobs, bool merged, int fin, const fl
     rc = forked ? stream_depends(c.st, c.aux, 3) : window_gather(c, c.st);      // join | the gather, last
     if (rc) return rc;
   }
-  if (reductions_pending && !r.knots) return launch_reduce_jobs(jobs->rg, c.st);
-  if (!r.knots) return 0;
+  if (reductions_pending && !fin_launch) return launch_reduce_jobs(jobs->rg, c.st);
+  if (!fin_launch) return 0;
   // the per-knot sums are final: once the dW launch is (window path), or from dZ of layer 0 here (materialising path)
-  if (!c.window) {
+  if (r.knots && !c.window) {
     rc = knot_dense_sums(c, b, c.P, coords);
     if (rc) return rc;
   }
+  HeadFinishArgs hf;
+  if (r.head) {
+    // the output layer's sums: still column partials behind the fused tail kernels (the head workgroup runs them),
+    // final behind the generic kernels (head_reduce / GEMM + colsum)
+    hf = *r.head;
+    hf.sq_part = head_slot;
+    hf.pending = jobs && jobs->head_apart ? 1 : 0;
+    if (hf.pending) { hf.job[0] = jobs->head_job[0]; hf.job[1] = jobs->head_job[1]; }
+    hf.zero_slots = head_zero; hf.n_zero = head_zero ? nhb : 0;
+  }
+  KnotFinishArgs fa{};
+  if (r.knots) fa = knot_finish_args(c, b, r.kt, r.d_centers, r.d_log_bw, c.mse_loss);
   ReduceGroup none;
-  return launch_step_finish(reductions_pending ? jobs->rg : none, knot_finish_args(c, b, r.kt, r.d_centers, r.d_log_bw, c.mse_loss),
-                            r.knot_sq, r.finish_inc, c.st);
+  return launch_step_finish(reductions_pending ? jobs->rg : none, fa, r.knots ? r.knot_sq : nullptr, r.finish_inc, c.st,
+                            r.head ? &hf : nullptr);
+}
+
+// Delta step behind the fused tail kernels: are the output layer's two fixed-order sums still pending when the
+// finishing launch starts?  No where a launch in front of it runs reduce jobs anyway -- the weight-gradient launch in
+// finishing mode 2 (its tall workgroups), the reductions launch of a learnable step's separate launches (materialising
+// route) -- : the sums stay in the table there, the head workgroup reads them and clears their slots of squares.  Yes
+// where the finishing launch itself carries the reductions (window modes 0 / 1, fixed-knot separate launches): there
+// they leave the table and the head workgroup runs them (close_step).
+static bool head_sums_pending(const Ctx &c, bool merged, int fin) {
+  if (!c.ride->head) return false;
+  return merged ? fin != 2 : !c.ride->knots;
 }
 
 // backward of the batch whose training forward left its state in the workspace; dY in caller order
@@ -1574,7 +1632,7 @@ static int step_backward(const Ctx &c, const float *dY, bool dY_sorted, Held *h,
     }
     rc = tail_row_launch(c, dY, true, 0, h, &n_part);
     if (rc) return rc;
-    rc = collect_dw_jobs(c, n_part, 0, nullptr, 0, ws + c.pl.feats, c.pl.ldf, jobs);
+    rc = collect_dw_jobs(c, n_part, 0, nullptr, 0, ws + c.pl.feats, c.pl.ldf, jobs, head_sums_pending(c, false, 0));
     if (rc) return rc;
     return close_step(c, &jobs, false, 0, coords, out);
   }
@@ -1613,7 +1671,7 @@ static int step_backward(const Ctx &c, const float *dY, bool dY_sorted, Held *h,
     rc = window_gather(c, c.aux);
     if (rc) return rc;
   }
-  rc = collect_dw_jobs(c, n_part, fin, extra, n_extra, nullptr, 0, jobs);
+  rc = collect_dw_jobs(c, n_part, fin, extra, n_extra, nullptr, 0, jobs, head_sums_pending(c, merged, fin));
   if (rc) return rc;
   return close_step(c, &jobs, merged, fin, coords, out);
 }
@@ -1831,6 +1889,11 @@ static int train_fwd_bwd_impl(const StepCall &s, const StepRide *ride, StepOut *
   // ---- from here on `c` is read-only: forward -> (loss) -> backward, what they hand on by value
   Held held;
   StepOut left;
+  if (c.ride->head) {     // delta step: the output layer of this step's delta, the call's first launch
+    const HeadFinishArgs &hd = *c.ride->head;
+    rc = launch_delta_head(hd.delta, hd.ldd, hd.Q, hd.d, s.P->W[s.d->n_hidden], s.P->b[s.d->n_hidden], c.st);
+    if (rc) return rc;
+  }
   rc = step_forward(c, s.coords, s.t, s.X, s.y, c.window ? s.y_pred : yp, &held);
   if (rc) return rc;
   if (!held.loss_fused) {
@@ -1853,43 +1916,80 @@ struct KnotStep {
 };
 
 // what the knots door refuses before anything is planned: flags, the knot group, where its gradients go, the penalties
-static int check_knot_step(const StepCall &s, const KnotStep &k) {
+static int check_knot_step(const char *door, const StepCall &s, const KnotStep &k) {
   const stdadk_basis_desc *b = s.b; const stdadk_mlp_desc *d = s.d;
-  STDADK_REQUIRE(b && d, STDADK_E_ARG, "train_step_knots: basis / mlp descriptor is NULL");
+  STDADK_REQUIRE(b && d, STDADK_E_ARG, "%s: basis / mlp descriptor is NULL", door);
   STDADK_REQUIRE((s.flags & STDADK_FLAG_LOG_BW), STDADK_E_ARG,
-                 "train_step_knots: flags need STDADK_FLAG_LOG_BW (learnable knots: basis->s_bw holds log-bandwidths)");
+                 "%s: flags need STDADK_FLAG_LOG_BW (learnable knots: basis->s_bw holds log-bandwidths)", door);
   STDADK_REQUIRE(!(s.flags & STDADK_FLAG_PACK_F32), STDADK_E_ARG,
-                 "train_step_knots: flags carry STDADK_FLAG_PACK_F32; packed fp32 copies are not kept on this path");
+                 "%s: flags carry STDADK_FLAG_PACK_F32; packed fp32 copies are not kept on this path", door);
   STDADK_REQUIRE(b->Ks > 0 && b->Ks < (1ll << 31) && d->n_hidden >= 1, STDADK_E_ARG,
-                 "train_step_knots: no spatial knots / no hidden layer");
+                 "%s: no spatial knots / no hidden layer", door);
   const stdadk_adam_group *g = k.group;
-  STDADK_REQUIRE(g && g->p && g->g && g->m && g->v && g->n > 0, STDADK_E_ARG, "train_step_knots: knots group incomplete");
-  STDADK_REQUIRE(!g->shadow, STDADK_E_ARG, "train_step_knots: knots->shadow must be NULL (the knot group has no operand copies)");
+  STDADK_REQUIRE(g && g->p && g->g && g->m && g->v && g->n > 0, STDADK_E_ARG, "%s: knots group incomplete", door);
+  STDADK_REQUIRE(!g->shadow, STDADK_E_ARG, "%s: knots->shadow must be NULL (the knot group has no operand copies)", door);
   STDADK_REQUIRE(g->max_norm <= 0.f || g->sumsq_parts, STDADK_E_ARG,
-                 "train_step_knots: knots->max_norm > 0 needs knots->sumsq_parts (STDADK_SUMSQ_PARTS floats)");
-  STDADK_REQUIRE(k.d_centers && k.d_log_bw, STDADK_E_ARG, "train_step_knots: d_centers / d_log_bw is NULL");
+                 "%s: knots->max_norm > 0 needs knots->sumsq_parts (STDADK_SUMSQ_PARTS floats)", door);
+  STDADK_REQUIRE(k.d_centers && k.d_log_bw, STDADK_E_ARG, "%s: d_centers / d_log_bw is NULL", door);
   const float *lo = g->g, *hi = g->g + g->n;
   STDADK_REQUIRE(k.d_centers >= lo && k.d_centers + 2 * b->Ks <= hi, STDADK_E_ARG,
-                 "train_step_knots: d_centers [Ks,2] lies outside the knot group's gradient range [knots->g, knots->g + n)");
+                 "%s: d_centers [Ks,2] lies outside the knot group's gradient range [knots->g, knots->g + n)", door);
   STDADK_REQUIRE(k.d_log_bw >= lo && k.d_log_bw + b->Ks <= hi, STDADK_E_ARG,
-                 "train_step_knots: d_log_bw [Ks] lies outside the knot group's gradient range [knots->g, knots->g + n)");
-  STDADK_REQUIRE(s.P && s.P->W[0], STDADK_E_ARG, "train_step_knots: params->W[0] is NULL");
-  return check_knot_train("train_step_knots: kt", k.kt);
+                 "%s: d_log_bw [Ks] lies outside the knot group's gradient range [knots->g, knots->g + n)", door);
+  STDADK_REQUIRE(s.P && s.P->W[0], STDADK_E_ARG, "%s: params->W[0] is NULL", door);
+  char what[64];
+  snprintf(what, sizeof what, "%s: kt", door);
+  return check_knot_train(what, k.kt);
+}
+
+// what the delta door refuses on top: the head's rows, where its gradient goes, the output layer's scratch
+static int check_delta_step(const StepCall &s, const stdadk_optim_desc *o, const stdadk_delta_step *h) {
+  const stdadk_mlp_desc *d = s.d;
+  STDADK_REQUIRE(s.b && d, STDADK_E_ARG, "train_step_delta: basis / mlp descriptor is NULL");
+  STDADK_REQUIRE(h && h->delta && h->d_delta, STDADK_E_ARG, "train_step_delta: head is NULL / incomplete");
+  STDADK_REQUIRE(d->n_hidden >= 1 && d->n_hidden <= STDADK_MAX_HIDDEN, STDADK_E_ARG, "train_step_delta: no hidden layer");
+  const int L = d->n_hidden, Q = d->out_dim, dl = d->hidden[L - 1];
+  STDADK_REQUIRE(Q >= 2 && Q <= STDADK_MAX_Q, STDADK_E_ARG, "train_step_delta: Q=%d outside 2..%d (the delta head has Q >= 2 rows)",
+                 Q, STDADK_MAX_Q);
+  STDADK_REQUIRE(h->ldd >= dl + 1, STDADK_E_ARG, "train_step_delta: ldd=%lld below d + 1 = %d", (long long)h->ldd, dl + 1);
+  STDADK_REQUIRE(h->ldg == h->ldd, STDADK_E_ARG, "train_step_delta: the strides of delta (%lld) and d_delta (%lld) differ",
+                 (long long)h->ldd, (long long)h->ldg);
+  const int64_t span = (int64_t)(Q - 1) * h->ldd + dl + 1;
+  STDADK_REQUIRE(h->delta >= o->p && h->delta + span <= o->p + o->n, STDADK_E_ARG,
+                 "train_step_delta: delta [Q,ldd] lies outside the parameter range [opt->p, opt->p + n)");
+  STDADK_REQUIRE(h->d_delta >= o->g && h->d_delta + span <= o->g + o->n, STDADK_E_ARG,
+                 "train_step_delta: d_delta [Q,ldd] lies outside the gradient range [opt->g, opt->g + n)");
+  STDADK_REQUIRE(h->d_delta - o->g == h->delta - o->p, STDADK_E_ARG,
+                 "train_step_delta: d_delta sits at another offset of the gradient than delta of the parameters");
+  STDADK_REQUIRE(s.P && s.G && s.P->W[L] && s.P->b[L] && s.G->W[L] && s.G->b[L], STDADK_E_ARG,
+                 "train_step_delta: the derived output layer (params->W[L], b[L]) or its gradient scratch is NULL");
+  const float *gw = s.G->W[L], *gb = s.G->b[L], *lo = o->g, *hi = o->g + o->n;
+  STDADK_REQUIRE((gw + (int64_t)Q * dl <= lo || gw >= hi) && (gb + Q <= lo || gb >= hi), STDADK_E_ARG,
+                 "train_step_delta: grads->W[L] / b[L] (scratch of the derived output layer) lie inside the gradient range "
+                 "[opt->g, opt->g + n)");
+  return 0;
 }
 
 // forward / backward of `s`, sparsity penalty, clip norm, AdamW + EMA; `nb`, when complete, is binned along the way.
 // `ks`: the step has a second parameter group, the learnable knots -- their finish rides in the step's finishing
 // launch (step_finish.hip), both groups are stepped by one two-group AdamW launch, and the next batch is binned by
 // the weight-gradient launch or not at all.
+// `ds`: the delta head -- the derived output layer is rebuilt in front, the head workgroup of the finishing launch
+// folds its gradient into the delta rows of the flat gradient; with or without `ks`.
 static int train_step_impl(StepCall s, const stdadk_sparsity_desc *sparsity, const stdadk_optim_desc *o,
-                           const NextBatch &nb, const KnotStep *ks = nullptr) {
+                           const NextBatch &nb, const KnotStep *ks = nullptr, const stdadk_delta_step *ds = nullptr,
+                           const char *door = "train_step_knots") {
   const stdadk_basis_desc *b = s.b; const stdadk_mlp_desc *d = s.d;
   if (nb.binned) *nb.binned = 0;
   STDADK_REQUIRE(o && o->p && o->g && o->m && o->v && o->n > 0 && o->step_dev, STDADK_E_ARG,
                  "train_step: optimiser descriptor incomplete");
   STDADK_REQUIRE(o->max_norm <= 0.f || o->sumsq_parts, STDADK_E_ARG, "train_step: max_norm > 0 needs sumsq_parts");
   if (ks) {
-    const int rc = check_knot_step(s, *ks);
+    const int rc = check_knot_step(door, s, *ks);
+    if (rc) return rc;
+  }
+  if (ds) {
+    const int rc = check_delta_step(s, o, ds);
     if (rc) return rc;
   }
   if (s.B == 0) return 0;
@@ -1933,6 +2033,18 @@ static int train_step_impl(StepCall s, const stdadk_sparsity_desc *sparsity, con
     ride.knot_sq = ks->group->max_norm > 0.f ? const_cast<float *>(ks->group->sumsq_parts) : nullptr;
     ride.finish_inc = o->step_dev;
   }
+  HeadFinishArgs head;
+  if (ds) {
+    // a delta step ends in the finishing launch too, which then advances the counter
+    const int L = d->n_hidden;
+    head.d_delta = ds->d_delta; head.delta = ds->delta; head.dWo = s.G->W[L]; head.dbo = s.G->b[L];
+    head.ldd = ds->ldd; head.Q = d->out_dim; head.d = d->hidden[L - 1];
+    head.lam_g = ds->lambda_grad; head.lam_l = ds->lambda_loss; head.loss_sum = s.loss_sum;
+    ride.head = &head;
+    ride.step_inc = nullptr;
+    ride.finish_inc = o->step_dev;
+  }
+  const bool fin_launch = ks || ds;
   StepOut out;     // where the step's own launches left the squared-norm partials, if they did
   int rc = train_fwd_bwd_impl(s, &ride, &out);
   // (a failure behind the weight-gradient launch: the next batch may be binned, but the caller is not told so and
@@ -1950,10 +2062,10 @@ static int train_step_impl(StepCall s, const stdadk_sparsity_desc *sparsity, con
   if (clip && out.sq_parts) {
     parts = out.sq_parts; n_parts = out.sq_n;      // partials (and the step advance) came out of the step's launches
   } else if (clip) {
-    rc = stdadk_sumsq_f32(o->g, o->n, o->sumsq_parts, ks ? nullptr : o->step_dev, s.stream);
+    rc = stdadk_sumsq_f32(o->g, o->n, o->sumsq_parts, fin_launch ? nullptr : o->step_dev, s.stream);
     if (rc) return rc;
     n_parts = STDADK_SUMSQ_PARTS;
-  } else if (!ks) {
+  } else if (!fin_launch) {
     rc = stdadk_step_advance(o->step_dev, s.stream);
     if (rc) return rc;
   }
@@ -1968,7 +2080,7 @@ static int train_step_impl(StepCall s, const stdadk_sparsity_desc *sparsity, con
     stdadk_adam_group kg = *ks->group;
     kg.n_parts = kg.max_norm > 0.f ? STDADK_SUMSQ_PARTS : 0;
     if (!(kg.max_norm > 0.f)) kg.sumsq_parts = nullptr;
-    rc = adamw_launch("train_step_knots", 2, &gr, &kg, h, nullptr, s.stream);
+    rc = adamw_launch(door, 2, &gr, &kg, h, nullptr, s.stream);
     if (rc == 0 && out.binned_next) *nb.binned = 1;
     return rc;
   }
@@ -2028,6 +2140,35 @@ extern "C" int stdadk_train_step_knots_f32(const stdadk_basis_desc *b, const std
   ks.kt = kt; ks.d_centers = d_centers; ks.d_log_bw = d_log_bw; ks.group = knots;
   return train_step_impl(s, sparsity, o, {next_idx, next_B, next_y_cols, next_workspace, next_workspace_bytes, next_binned},
                          &ks);
+}
+
+extern "C" int stdadk_train_step_delta_f32(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,
+                                           const stdadk_mlp_tensors *P, const stdadk_mlp_tensors *G,
+                                           const float *coords_all, const float *t_all, const float *X_all,
+                                           const float *y_all, const int64_t *idx, int64_t B, float grad_scale,
+                                           const stdadk_loss_desc *loss, const stdadk_sparsity_desc *sparsity,
+                                           float *loss_sum, void *workspace, size_t workspace_bytes,
+                                           uint64_t drop_seed, int32_t flags, const stdadk_optim_desc *o,
+                                           const int64_t *next_idx, int64_t next_B, int32_t next_y_cols,
+                                           void *next_workspace, size_t next_workspace_bytes, int32_t *next_binned,
+                                           const stdadk_knot_train *kt, float *d_centers, float *d_log_bw,
+                                           const stdadk_adam_group *knots, const stdadk_delta_step *head,
+                                           stdadk_stream_t stream) {
+  const bool no_next = !next_idx && next_B == 0 && !next_workspace;
+  STDADK_REQUIRE(next_binned || no_next, STDADK_E_ARG, "train_step_delta: next_binned is NULL with a next batch given");
+  STDADK_REQUIRE(head, STDADK_E_ARG, "train_step_delta: head is NULL / incomplete");
+  const bool learnable = knots != nullptr;
+  STDADK_REQUIRE(learnable ? (d_centers && d_log_bw) : (!kt && !d_centers && !d_log_bw), STDADK_E_ARG,
+                 "train_step_delta: kt / d_centers / d_log_bw / knots given in part (all NULL: fixed knots; d_centers, "
+                 "d_log_bw and knots all given: learnable knots)");
+  StepCall s = step_call(b, d, P, G, coords_all, t_all, X_all, y_all, B, grad_scale, loss, loss_sum, workspace, workspace_bytes,
+                         drop_seed, flags, stream);
+  s.idx = idx;
+  const NextBatch nb = {next_idx, next_B, next_y_cols, next_workspace, next_workspace_bytes, next_binned};
+  if (!learnable) return train_step_impl(s, sparsity, o, nb, nullptr, head, "train_step_delta");
+  KnotStep ks;
+  ks.kt = kt; ks.d_centers = d_centers; ks.d_log_bw = d_log_bw; ks.group = knots;
+  return train_step_impl(s, sparsity, o, nb, &ks, head, "train_step_delta");
 }
 
 extern "C" int stdadk_bin_batch_f32(const stdadk_basis_desc *b, const stdadk_mlp_desc *d,

@@ -90,6 +90,12 @@ class KnotTrain(C.Structure):
                 ("penalty_grad_scale", C.c_float), ("penalty_loss_scale", C.c_float)]
 
 
+class DeltaStep(C.Structure):
+    """stdadk_delta_step: the head of the one-call delta step (stdadk_train_step_delta_f32)."""
+    _fields_ = [("delta", C.c_void_p), ("ldd", C.c_int64), ("d_delta", C.c_void_p), ("ldg", C.c_int64),
+                ("lambda_grad", C.c_float), ("lambda_loss", C.c_float)]
+
+
 FLAG_DENSE = 1
 FLAG_W0_T = 2
 FLAG_LOG_BW = 4
@@ -155,6 +161,14 @@ _SIGNATURES = {
                                               C.c_int32, C.POINTER(OptimDesc), C.c_void_p, C.c_int64, C.c_int32,
                                               C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(KnotTrain),
                                               C.c_void_p, C.c_void_p, C.POINTER(AdamGroup), C.c_void_p]),
+    "stdadk_train_step_delta_f32": (C.c_int, [C.POINTER(BasisDesc), C.POINTER(MlpDesc), C.POINTER(MlpTensors),
+                                              C.POINTER(MlpTensors), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int64, C.c_float, C.POINTER(LossDesc),
+                                              C.POINTER(SparsityDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64,
+                                              C.c_int32, C.POINTER(OptimDesc), C.c_void_p, C.c_int64, C.c_int32,
+                                              C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(KnotTrain),
+                                              C.c_void_p, C.c_void_p, C.POINTER(AdamGroup), C.POINTER(DeltaStep),
+                                              C.c_void_p]),
     "stdadk_sumsq2_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "stdadk_adamw_ema2_f32": (C.c_int, [C.POINTER(AdamGroup), C.POINTER(AdamGroup), C.c_float, C.c_float,
@@ -978,6 +992,31 @@ def train_step_knots(basis, desc, params, grads, coords, t, X, y, idx, B, grad_s
     tail, done = _next_batch(nxt, y, workspace, "train_step_knots")
     tail += (_ref(knot_train), _dev(d_centers, "d_centers"), _dev(d_log_bw, "d_log_bw"), C.byref(knots))
     _train("stdadk_train_step_knots_f32", basis, desc, params, grads, coords, t, X, y, rows, grad_scale, loss_desc,
+           loss_sum, workspace, seed, flags, optim, sparsity_desc, tail)
+    return bool(done.value)
+
+
+def make_delta_step(delta, d_delta, lambda_grad, lambda_loss):
+    """stdadk_delta_step for the delta matrix [Q, ldd] and its rows of the flat gradient (same stride)."""
+    h = DeltaStep()
+    h.delta, h.ldd = _rows(delta, "delta", delta.shape[1])
+    h.d_delta, h.ldg = _rows(d_delta, "d_delta", delta.shape[1])
+    h.lambda_grad, h.lambda_loss = float(lambda_grad), float(lambda_loss)
+    return h
+
+
+def train_step_delta(basis, desc, params, grads, coords, t, X, y, idx, B, grad_scale, loss_sum, workspace, flags, optim,
+                     head, knot_train=None, d_centers=None, d_log_bw=None, knots=None, nxt=None, seed=0, loss_desc=None,
+                     sparsity_desc=None):
+    """The whole single-GPU step of a model with the delta head in one call (stdadk_train_step_delta_f32): derived
+    output layer, forward, objective, backward, the head's fold with P_nc(delta), [knot gradients + penalties,] clip
+    norm(s), AdamW + EMA.  `head` (make_delta_step); `knots` None: fixed knots, one parameter group, else the two-group
+    form of train_step_knots.  `nxt` and the return value as there."""
+    rows = (_idx(idx, "train_step_delta: idx")[0] if idx is not None else None, B)
+    tail, done = _next_batch(nxt, y, workspace, "train_step_delta")
+    tail += (_ref(knot_train), _dev(d_centers, "d_centers"), _dev(d_log_bw, "d_log_bw"),
+             C.byref(knots) if knots is not None else None, _ref(head))
+    _train("stdadk_train_step_delta_f32", basis, desc, params, grads, coords, t, X, y, rows, grad_scale, loss_desc,
            loss_sum, workspace, seed, flags, optim, sparsity_desc, tail)
     return bool(done.value)
 

@@ -163,6 +163,12 @@ class TrainStep(Cached):
     weight-gradient launch.  Same arithmetic as the split calls; with clipping off bit-identical to them.
     `fused_knot_step=True` where the call does not apply raises ValueError.
 
+    One-call delta step (`fused_delta_step`, default off; None reads STNF_FUSED_DELTA_STEP, "1" = on): a single-GPU step
+    of a model with the delta head -- fixed knots (one parameter group) or learnable knots (two) -- as ONE library call
+    (stdadk_train_step_delta_f32) instead of five or six: the derived output layer is rebuilt by the call's first launch,
+    the head's fold with P_nc(delta) is one workgroup of the step's finishing launch.  Same arithmetic as the split calls;
+    with clipping off bit-identical to them.  `fused_delta_step=True` where the call does not apply raises ValueError.
+
     Packed weights (`pack_weights`, default on; `STNF_NO_PACK_WEIGHTS=1` turns it off): fp32 one-call steps with hidden
     widths of 128 / 256 stream the hidden weights after the first from fragment-order copies (N.FLAG_PACK_F32) that
     the step's optimiser launch keeps current and `refresh_bf16` rebuilds after any other write of the parameters.
@@ -180,7 +186,8 @@ class TrainStep(Cached):
                  domain_penalty_weight=0.0, movement_penalty_weight=0.0, sparsity_penalty_type="none",
                  sparsity_lambda_l1=0.001, sparsity_lambda_group=0.01, sparsity_apply_to_spatial=True,
                  sparsity_apply_to_temporal=True, seed=None, world_size=None, dtype="f32", shard_optimizer=False,
-                 sync_init=True, nonfinite_guard=True, inline_prep=True, pack_weights=True, fused_knot_step=None):
+                 sync_init=True, nonfinite_guard=True, inline_prep=True, pack_weights=True, fused_knot_step=None,
+                 fused_delta_step=None):
         self.model = model
         if dtype not in ("f32", "bf16"):
             raise ValueError(f"unknown dtype '{dtype}'; use 'f32' or 'bf16'")
@@ -194,7 +201,7 @@ class TrainStep(Cached):
             raise RuntimeError("TrainStep needs the model on a HIP device; there is no CPU path")
         # (the order of these is the order of the allocations, of the draw from torch's generator and of the broadcasts)
         self._setup_distributed(process_group, distributed, world_size, shard_optimizer, sync_init, fused_knot_step,
-                                two_streams)
+                                two_streams, fused_delta_step)
         self._setup_flat_buffers(lr, weight_decay, betas, eps, grad_clip, ema_decay, max_batch)
         self._setup_operand_copies(force_dense)
         self._setup_gradient_views(sparsity_penalty_type, sparsity_lambda_l1, sparsity_lambda_group,
@@ -208,7 +215,7 @@ class TrainStep(Cached):
         return dist.get_global_rank(self.pg, 0) if self.pg is not None else 0
 
     def _setup_distributed(self, process_group, distributed, world_size, shard_optimizer, sync_init, fused_knot_step,
-                           two_streams):
+                           two_streams, fused_delta_step=None):
         model = self.model
         if distributed is None:
             distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1
@@ -221,6 +228,19 @@ class TrainStep(Cached):
             # (split path, 1/world shares of the parameter-level penalties); see set_virtual_rank
             self.world = int(world_size)
         self.shard = bool(shard_optimizer) and self.world > 1
+        # the delta head as ONE library call per step (stdadk_train_step_delta_f32), fixed or learnable knots, off by
+        # default: None reads STNF_FUSED_DELTA_STEP ("1" = on) and quietly keeps the split path where the call does not
+        # apply, True insists
+        want_delta_step = os.environ.get("STNF_FUSED_DELTA_STEP", "") == "1" if fused_delta_step is None \
+            else bool(fused_delta_step)
+        missing = [why for bad, why in (
+            (not model._has_delta, "a model with the delta head (use_delta_reparameterization=True)"),
+            (self.distributed or self.world != 1, "a single process (world size 1): data-parallel steps keep the split "
+                                                  "calls around their all-reduce"),
+            (bool(two_streams), "two_streams=False (no auxiliary stream)")) if bad]
+        if missing and fused_delta_step is not None and want_delta_step:
+            raise ValueError(f"fused_delta_step=True needs {missing[0]}")
+        self._delta_step = want_delta_step and not missing
         # learnable knots as ONE library call per step (stdadk_train_step_knots_f32), off by default: None reads
         # STNF_FUSED_KNOT_STEP ("1" = on) and quietly keeps the split path where the call does not apply, True insists
         want_knot_step = os.environ.get("STNF_FUSED_KNOT_STEP", "") == "1" if fused_knot_step is None \
@@ -231,7 +251,8 @@ class TrainStep(Cached):
                                                   "calls around their all-reduce"),
             (model._has_delta, "a model without the delta head (use_delta_reparameterization=False)"),
             (bool(two_streams), "two_streams=False (no auxiliary stream)")) if bad]
-        if missing and fused_knot_step is not None and want_knot_step:
+        # (a learnable delta model on the delta door is the two-group form already: fused_delta_step=True alone selects it)
+        if missing and fused_knot_step is not None and want_knot_step and not (self._delta_step and fused_delta_step):
             raise ValueError(f"fused_knot_step=True needs {missing[0]}")
         self._knot_step = want_knot_step and not missing
         if self.distributed and sync_init:
@@ -409,7 +430,8 @@ class TrainStep(Cached):
         were measured (profiles/tail_packed_weights.md).  The library takes the copies at every width of the tail
         kernels; split-path steps, eval and Predictor read the weights themselves."""
         m = self.model
-        return (self.dtype == "f32" and self._whole_step and len(m.hidden_dims) >= 2
+        one_group_call = self._whole_step or (self._delta_step and not self.learnable)
+        return (self.dtype == "f32" and one_group_call and len(m.hidden_dims) >= 2
                 and all(h in (128, 256) for h in m.hidden_dims) and m.output_dim <= 8
                 and os.environ.get("STDADK_NO_FUSED_TAIL", "") != "1")
 
@@ -503,6 +525,23 @@ class TrainStep(Cached):
             self._step_call(N.train_step, coords, t, X, y, (idx if not prebinned else None, B), global_rows, ws, flags,
                             (self._optim,), params)
             return False
+        if self._delta_step:
+            # single GPU, the delta head: ONE library call -- the derived output layer in front, the head's fold and
+            # P_nc(delta) in the finishing launch; learnable knots ride as the second group, as on the door below
+            if B == 0:
+                raise RuntimeError("an empty batch cannot carry the parameter-level penalties of a delta-head step")
+            plan = self._cached("one_call", self._plan_key(), self._one_call_plan)
+            Q, lam = self.model.output_dim, self.objective.nc_lambda
+            head = self._cached("delta_step", (self.state.delta.data_ptr(), self.d_delta.data_ptr(), lam, B * Q),
+                                N.make_delta_step, self.state.delta, self.d_delta, lam, lam * B * Q)
+            knots = (self._knot_train_desc(B * Q), self.g_centers, self.g_log_bw, plan[1]) if self.learnable \
+                else (None, None, None, None)
+            params = self._pack_params
+            if params is not None:
+                flags |= N.FLAG_PACK_F32
+            return self._step_call(N.train_step_delta, coords, t, X, y,
+                                   (idx if (nxt is not None or not prebinned) else None, B), global_rows, ws, flags,
+                                   (plan[0], head) + knots + (nxt,), params)
         if self._knot_step:
             # single GPU, learnable knots: the two-group step as ONE library call -- the knot finish and both clip
             # norms come out of the step's finishing launch, the next batch is binned by the weight-gradient launch
@@ -914,7 +953,7 @@ class TrainStep(Cached):
         # one-call step on a small batch: the NEXT batch is binned by extra workgroups of this step's optimiser launch
         # (no side stream, no cross-stream packets in the main queue: DESIGN.md section 8, "the bubble between steps")
         # (the one-call learnable step takes it in its weight-gradient launch, or declines)
-        if (nxt is not None and (self._whole_step or self._knot_step) and self.inline_prep and not self.distributed
+        if (nxt is not None and (self._whole_step or self._knot_step or self._delta_step) and self.inline_prep and not self.distributed
                 and nxt.numel() <= 8192 and nxt.dtype == torch.int64):
             # (`idx` is contiguous: step_indexed hands on `src`)
             if self._enqueue(Xa, coords_all, t_all, y_all, B, global_rows, idx=idx, ws=pp["ws"][wsi],

@@ -136,7 +136,8 @@ def make_engine(model, config, batch_size, batches_per_epoch):
                      sparsity_apply_to_spatial=config.get("sparsity_apply_to_spatial", True),
                      sparsity_apply_to_temporal=config.get("sparsity_apply_to_temporal", True),
                      seed=config.get("dropout_seed", None), dtype=config.get("dtype", "f32"),
-                     fused_knot_step=config.get("fused_knot_step", None))
+                     fused_knot_step=config.get("fused_knot_step", None),
+                     fused_delta_step=config.get("fused_delta_step", None))
 
 
 def _ema_full(eng):
