@@ -276,6 +276,7 @@ class TrainStep(Cached):
         self.v = torch.zeros(self.chunk, device=self.dev)
         self.ema = self.flat[self.lo:self.hi].clone() if ema_decay is not None else None
         self._ema_backup = None
+        self._ema_swapped = False  # replicated optimiser: True between the two swap_in_ema calls of a pair
         self._vstate = {}          # tests (set_virtual_rank with the sharded optimiser): rank -> (m, v, ema) slices
         self.ema_decay = 0.0 if ema_decay is None else float(ema_decay)
         self.lr, self.wd, self.betas, self.eps = float(lr), float(weight_decay), betas, float(eps)
@@ -313,6 +314,9 @@ class TrainStep(Cached):
         # sparsity penalties on the first layer (config keys of train_st_interp.py:674-691): their gradient
         # is added to dW0^T by stdadk_sparsity_f32 between backward and clipping
         self._sparsity = None
+        # (the settings as given: state_dict() records them, the descriptor below is opaque)
+        self._sparsity_settings = [str(penalty_type)] + ([float(lambda_l1), float(lambda_group), bool(apply_spatial),
+                                                           bool(apply_temporal)] if penalty_type != "none" else [])
         if penalty_type != "none":
             self._sparsity = N.make_sparsity(penalty_type, lambda_l1, lambda_group, apply_spatial, apply_temporal)
             self._w0t, self._g_w0t = lay.view(self.flat, lay.first_w), lay.view(self.grad, lay.first_w)
@@ -330,7 +334,8 @@ class TrainStep(Cached):
             self.g_log_bw = self.layout.view(self.grad, sb.log_bandwidths)
             self.knot_end = self.offsets[2][1]
             self.basis_lr = self.lr * float(basis_lr_ratio)
-            self.basis_clip = self.grad_clip * float(basis_clip_ratio)
+            self.basis_clip_ratio = float(basis_clip_ratio)
+            self.basis_clip = self.grad_clip * self.basis_clip_ratio
             self.basis_lr_dev = torch.full((1,), self.basis_lr, device=self.dev)
             self.sumsq_basis = torch.zeros(N.SUMSQ_PARTS, device=self.dev)
             self.domain_w, self.movement_w = float(domain_penalty_weight), float(movement_penalty_weight)
@@ -1042,6 +1047,7 @@ class TrainStep(Cached):
             tmp = self.flat.clone()
             self.flat.copy_(self.ema)
             self.ema.copy_(tmp)
+            self._ema_swapped = not self._ema_swapped
         _bump_engine_version(self.model)
         self.refresh_bf16()
 
@@ -1052,6 +1058,134 @@ class TrainStep(Cached):
             raise RuntimeError("the engine was built with nonfinite_guard=False")
         v = int(self.nonfinite.item())
         return v if v > 0 else None
+
+    # ---- everything a later process needs to continue this run bit for bit ----------------------------------------
+    def _fingerprint(self):
+        """What a saved state must agree with before any of it is written into this engine: the flat layout, the
+        engine's kind, and every setting the step kernels take by value."""
+        lay, m, ob = self.layout, self.model, self.objective
+        first = [n for n, p in m.named_parameters() if p is lay.first_w]
+        out = {"layout": {"offsets": [[n, int(o), int(k)] for n, o, k in lay.offsets], "numel": int(lay.numel),
+                          "transposed_first": first[0] if first else None},
+               "kind": {"dtype": self.dtype, "world": int(self.world), "learnable": self.learnable,
+                        "delta": bool(m._has_delta), "flags": int(self.state.flags),
+                        # which door the step takes: with clipping on, a one-call step and the split calls sum the
+                        # clip norm in another order (packed weights and graph replay are bit-identical either way)
+                        "step_call": "whole" if self._whole_step else "delta" if self._delta_step
+                        else "knots" if self._knot_step else "split"},
+               "hyper": {"weight_decay": self.wd, "betas": [float(b) for b in self.betas], "eps": self.eps,
+                         "grad_clip": self.grad_clip, "ema_decay": self.ema_decay, "dropout": float(m.dropout_p),
+                         "objective": {"kind": ob.kind, "quantile_levels": ob.quantile_levels,
+                                       "non_crossing_weight": ob.nc_weight, "non_crossing_power": ob.nc_power,
+                                       "non_crossing_lambda": ob.nc_lambda},
+                         "sparsity": list(self._sparsity_settings)}}
+        if self.learnable:
+            sb = m.spatial_basis
+            out["hyper"]["knots"] = {"basis_clip_ratio": self.basis_clip_ratio, "domain_penalty_weight": self.domain_w,
+                                     "movement_penalty_weight": self.movement_w,
+                                     "gradient_damping": bool(sb.gradient_damping),
+                                     "damping_threshold": float(sb.damping_threshold),
+                                     "damping_strength": float(sb.damping_strength)}
+        return out
+
+    def _refuse_sharded_state(self):
+        if self.shard:
+            raise NotImplementedError("state_dict / load_state_dict with shard_optimizer=True: the Adam moments and the "
+                                      "EMA shadow exist in per-rank slices, which no checkpoint format covers yet")
+
+    def state_dict(self):
+        """The engine's whole training state as CPU tensors, numbers, strings, lists and dicts (it loads under
+        torch.load(..., weights_only=True)): exact copies of the parameter, moment and shadow buffers, the device step
+        counter (AdamW's bias correction and the dropout stream read it), the loss accumulator, the non-finite guard,
+        the dropout base seed, the current rates, the model's buffers (knot tables, centers_init) and the fingerprint
+        `load_state_dict` checks.  Valid at any step boundary outside a `swap_in_ema` pair; the copies are enqueued
+        behind the steps so far and awaited together (ONE host sync).  Reads only: the engine continues unchanged."""
+        self._refuse_sharded_state()
+        if self._ema_swapped:
+            raise RuntimeError("state_dict() inside a swap_in_ema pair: the parameter buffer holds the EMA values")
+
+        def host(t):
+            if t is None:
+                return None
+            if not t.is_cuda:
+                return t.detach().clone()
+            out = torch.empty(t.shape, dtype=t.dtype, device="cpu", pin_memory=True)
+            return out.copy_(t.detach(), non_blocking=True)
+        state = dict(self._fingerprint(), format=1)
+        state.update(flat=host(self.flat), m=host(self.m), v=host(self.v), ema=host(self.ema),
+                     step_dev=host(self.step_dev), loss_sum=host(self.loss_sum), nonfinite=host(self.nonfinite),
+                     buffers={n: host(b) for n, b in self.model.named_buffers()},
+                     step_count=int(self.step_count), rows_seen=int(self.rows_seen), base_seed=int(self.base_seed),
+                     lr=float(self.lr), basis_lr=float(self.basis_lr) if self.learnable else None)
+        if self.dev.type == "cuda":
+            torch.cuda.current_stream(self.dev).synchronize()
+        return state
+
+    def _check_state(self, state):
+        """ValueError naming the first field of `state` this engine cannot continue from; nothing is written."""
+        if state.get("format") != 1:
+            raise ValueError(f"format: {state.get('format')!r} is not a state format this version reads (1)")
+        mine = self._fingerprint()
+        for field in ("offsets", "numel", "transposed_first"):
+            if state["layout"][field] != mine["layout"][field]:
+                raise ValueError(f"layout.{field}: the state was saved from a model with another parameter layout")
+        for field, own in mine["kind"].items():
+            if state["kind"].get(field) != own:
+                # (`flags`: the route of the step -- grid or scattered knot tables, window or materialising kernels,
+                #  W0 layout --; the same arithmetic on another route is not the same bits)
+                raise ValueError(f"{field}: the state has {state['kind'].get(field)!r}, this engine {own!r}")
+        for field, own in (("ema", self.ema), ("nonfinite", self.nonfinite)):
+            if (state[field] is None) != (own is None):
+                raise ValueError(f"{field}: present on one side only (state: {state[field] is not None}, "
+                                 f"engine: {own is not None})")
+        for field, own in mine["hyper"].items():
+            got = state["hyper"].get(field)
+            pairs = [(f"{field}.{k}", got.get(k) if isinstance(got, dict) else None, v) for k, v in own.items()] \
+                if isinstance(own, dict) else [(field, got, own)]
+            for name, theirs, ours in pairs:
+                if theirs != ours:
+                    raise ValueError(f"{name}: the state was trained with {theirs!r}, this engine has {ours!r}")
+        own_buffers = dict(self.model.named_buffers())
+        if sorted(own_buffers) != sorted(state["buffers"]):
+            raise ValueError(f"buffers: the state has {sorted(state['buffers'])}, the model {sorted(own_buffers)}")
+        for name, own in [(f"buffers.{n}", b) for n, b in own_buffers.items()] + [
+                ("flat", self.flat), ("m", self.m), ("v", self.v), ("ema", self.ema), ("step_dev", self.step_dev),
+                ("loss_sum", self.loss_sum), ("nonfinite", self.nonfinite)]:
+            got = state["buffers"][name[len("buffers."):]] if name.startswith("buffers.") else state[name]
+            if own is not None and (tuple(got.shape) != tuple(own.shape) or got.dtype != own.dtype):
+                raise ValueError(f"{name}: {tuple(got.shape)} {got.dtype} in the state, {tuple(own.shape)} {own.dtype} here")
+
+    def load_state_dict(self, state):
+        """Continue from `state` (a `state_dict()` of an engine of the same layout, kind and settings: anything else is
+        refused with a ValueError that names the field, before anything is written).  Every buffer is written in place,
+        so descriptors, operand tables and views keep their addresses; the operand copies are rebuilt, the rates
+        applied, the dropout seed re-derived from the restored base seed and THIS engine's rank, an announced batch
+        is dropped and captured graphs (which hold the seed by value) are captured again on their next use."""
+        self._refuse_sharded_state()
+        if self._ema_swapped:
+            raise RuntimeError("load_state_dict() inside a swap_in_ema pair: the shadow sits in the parameter buffer")
+        self._check_state(state)
+        prep = self._prepared
+        if prep is not None and not prep.inline:
+            # the side stream may still be binning the announced batch into the workspace the next step bins into
+            _wait(torch.cuda.current_stream(self.dev), self._pipe["binned"])
+        self._prepared = None
+        self._graph.graph = self._ix_graph.graph = None
+        with torch.no_grad():
+            for name, own in [("flat", self.flat), ("m", self.m), ("v", self.v), ("ema", self.ema),
+                              ("step_dev", self.step_dev), ("loss_sum", self.loss_sum), ("nonfinite", self.nonfinite)]:
+                if own is not None:
+                    own.copy_(state[name])
+            for name, own in self.model.named_buffers():
+                own.copy_(state["buffers"][name])
+        self.step_count, self.rows_seen = int(state["step_count"]), int(state["rows_seen"])
+        self.base_seed = int(state["base_seed"])
+        self.seed = _rank_seed(self.base_seed, self.rank)
+        self.set_lr(state["lr"])
+        if self.learnable:
+            self.set_basis_lr(state["basis_lr"])
+        _bump_engine_version(self.model)
+        self.refresh_bf16()
 
 
 class Predictor:

@@ -12,14 +12,20 @@ Host syncs per epoch: one read for the training loss, one for validation.
 the accumulator before the last, ragged batch gives both partial sums with the epoch's one read).
 
 The best state is a copy of the EMA buffer on the device; `model_best.pt` (the reference's `state_dict` keys, EMA
-values) and `training_history.csv` are written once, at the end, when `output_dir` is given."""
+values) and `training_history.csv` are written once, at the end, when `output_dir` is given.
+
+`checkpoint=path` saves the engine's state and the driver's own (schedule, best state, patience, history, permutation
+RNG) at epoch ends (`stnf.checkpoint`); `resume=True` continues from that file as the same run: parameters, moments,
+shadow and every history column but `train_loss` (a float-atomic sum) are the bits the uninterrupted run has."""
 import csv
+import json
 import math
 import os
 import warnings
 
 import torch
 
+from .checkpoint import read_checkpoint, save_checkpoint
 from .engine import TrainStep
 from .evaluation import Evaluator
 from .flat import _bump_engine_version
@@ -157,8 +163,43 @@ def _load_flat(eng, flat_values):
     eng.refresh_bf16()
 
 
+_NOT_COMPARED = ("verbose", "checkpoint", "checkpoint_every", "resume")     # config keys a resumed run may change
+
+
+def _json_items(config):
+    """The items of `config` that JSON can write, each as its JSON text (tuples and lists, 1 and 1.0 compare as the
+    reference's YAML would read them back)."""
+    out = {}
+    for k, v in config.items():
+        try:
+            out[str(k)] = json.dumps(v, sort_keys=True)
+        except (TypeError, ValueError):
+            pass
+    return out
+
+
+def _rng_state(generator, dev):
+    """State of whatever draws the epoch permutations: the caller's generator, else torch's default generators (the
+    device's draws randperm; the host's is kept with it).  Reads only."""
+    if generator is not None:
+        return {"generator": generator.get_state()}
+    out = {"cpu": torch.get_rng_state()}
+    if dev.type == "cuda":
+        out["device"] = torch.cuda.get_rng_state(dev)
+    return out
+
+
+def _set_rng_state(state, generator, dev):
+    if generator is not None:
+        generator.set_state(state["generator"])
+        return
+    torch.set_rng_state(state["cpu"])
+    if dev.type == "cuda" and "device" in state:
+        torch.cuda.set_rng_state(state["device"], dev)
+
+
 def train_model(model, train_data, val_data, config, device=None, output_dir=None, generator=None, shuffle=True,
-                engine=None, evaluator=None):
+                engine=None, evaluator=None, checkpoint=None, checkpoint_every=1, resume=False):
     """scripts/train_st_interp.py:463-881 on device-resident data.  Returns (model, history, basis_centers_history);
     the model ends up holding the best EMA state (or the final EMA state when no epoch was ever best).
     `engine` / `evaluator`: ready-made TrainStep (`make_engine`) / Evaluator-like object, for callers who want to keep
@@ -168,7 +209,15 @@ def train_model(model, train_data, val_data, config, device=None, output_dir=Non
     Non-finite training loss: the reference leaves the epoch at the first NaN batch (:724-733), after that batch's
     optimiser step has already made the parameters NaN.  Here the epoch runs through by default (no host sync per
     step) and ends in the same state: NaN parameters and shadow, NaN `train_loss`, a validation loss that is never
-    best.  `config["nan_check_every"] = k` polls the device guard every k steps and leaves the epoch there."""
+    best.  `config["nan_check_every"] = k` polls the device guard every k steps and leaves the epoch there.
+
+    `checkpoint` (a path): the run is saved there at the end of every `checkpoint_every`-th epoch and of the last one,
+    after the best / patience update and the scheduler step (`stnf.checkpoint.save_checkpoint`: the engine's state plus
+    the driver's; the previous file survives an interrupted write).  `resume=True` continues from that file when it
+    exists -- on a fresh model and engine of the same configuration, the same data and the same kind of `generator` --
+    at the saved epoch; a file of a run that had already stopped goes straight to the final state without a step.  A
+    config key that differs (other than `verbose`) is a ValueError naming it.  Epoch ends only: a run killed inside an
+    epoch repeats that epoch."""
     if device is not None:
         model.to(device)
     learnable = bool(config.get("spatial_learnable", False)) and bool(model.spatial_basis.learnable)
@@ -202,7 +251,55 @@ def train_model(model, train_data, val_data, config, device=None, output_dir=Non
             applied["basis"] = groups[1]["lr"]
         sch.after_step()
 
-    for epoch in range(epochs):
+    def driver_state(next_epoch, stopped):
+        """The driver's half of a checkpoint (tensors on the host, numbers, strings, lists, dicts)."""
+        return {"epoch": next_epoch, "stopped": bool(stopped), "rows": len(train_data), "shuffle": bool(shuffle),
+                "groups": [{k: g[k] for k in ("lr", "initial_lr", "target_lr") if k in g} for g in sch.groups],
+                "sched": sch.sched.state_dict() if sch.sched is not None else None,
+                "global_step": sch.global_step, "warmup_steps": sch.warmup_steps,
+                "best_val": best_val, "patience_counter": patience_counter, "has_best": has_best,
+                "best_state": best_state.cpu() if has_best else None,
+                "history": {k: list(v) for k, v in history.items()},
+                "centers_history": [[e, torch.from_numpy(c)] for e, c in centers_history],
+                "applied": dict(applied), "rng": _rng_state(generator, eng.dev), "config": _json_items(config)}
+
+    first_epoch = 0
+    if resume and checkpoint is None:
+        raise ValueError("checkpoint: resume=True needs the path of the checkpoint")
+    if resume and os.path.exists(str(checkpoint)):
+        ck = read_checkpoint(checkpoint)
+        saved = ck["extra"]
+        theirs, ours = saved["config"], _json_items(config)
+        for k in sorted(set(theirs) | set(ours)):
+            if k not in _NOT_COMPARED and theirs.get(k) != ours.get(k):
+                raise ValueError(f"config['{k}']: the checkpoint was written with {theirs.get(k)}, this call has "
+                                 f"{ours.get(k)}")
+        for k, own in (("rows", len(train_data)), ("shuffle", bool(shuffle))):
+            if saved[k] != own:
+                raise ValueError(f"{k}: the checkpoint was written with {saved[k]}, this call has {own}")
+        if (generator is not None) != ("generator" in saved["rng"]):
+            raise ValueError("generator: the checkpoint was written " + ("with" if "generator" in saved["rng"] else "without")
+                             + " a permutation generator, this call is " + ("with" if generator is not None else "without")
+                             + " one")
+        eng.load_state_dict(ck["engine"])              # (every refusal above and in here comes before the first write)
+        _set_rng_state(saved["rng"], generator, eng.dev)
+        if verbose:
+            print(f"Resuming from {checkpoint}: " + ("the run had stopped" if saved["stopped"]
+                                                     else f"epoch {saved['epoch'] + 1}/{epochs}"), flush=True)
+        for g, fields in zip(sch.groups, saved["groups"]):
+            g.update(fields)
+        if sch.sched is not None:
+            sch.sched.load_state_dict(saved["sched"])
+        sch.global_step, sch.warmup_steps = saved["global_step"], saved["warmup_steps"]
+        best_val, patience_counter, has_best = saved["best_val"], saved["patience_counter"], saved["has_best"]
+        if has_best:
+            best_state.copy_(saved["best_state"])
+        history = {k: list(v) for k, v in saved["history"].items()}
+        centers_history = [(e, c.numpy().copy()) for e, c in saved["centers_history"]]
+        applied.update(saved["applied"])
+        first_epoch = epochs if saved["stopped"] else saved["epoch"]
+
+    for epoch in range(first_epoch, epochs):
         sch.start_epoch(epoch)
         model.train()
         # the reference's train_loss: mean of batch means, one read (TrainStep.run_epoch, loss="batches")
@@ -234,6 +331,9 @@ def train_model(model, train_data, val_data, config, device=None, output_dir=Non
             print(line, flush=True)
         if learnable and (epoch + 1) % 100 == 0:
             centers_history.append((epoch + 1, model.spatial_basis.centers.detach().cpu().numpy().copy()))
+        stopping = patience_counter >= patience or epoch + 1 == epochs
+        if checkpoint is not None and (stopping or (epoch + 1) % max(int(checkpoint_every), 1) == 0):
+            save_checkpoint(checkpoint, eng, driver_state(epoch + 1, stopping))
         if patience_counter >= patience:
             if verbose:
                 print(f"\nEarly stopping triggered at epoch {epoch + 1}")

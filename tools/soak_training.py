@@ -2,19 +2,28 @@
 out), C2 model, the reference's optimiser settings with a cosine learning-rate schedule: `stnf.training.train_model`
 (run_epoch + validation under the EMA weights every epoch) over a device-resident dataset.  Prints the driver's line per
 epoch, the best held-out RMSE and the rate; then the shipped multi-quantile shape on plain run_epoch.
-usage (MI355X box): python tools/soak_training.py [epochs]"""
-import math, os, sys, time
+`--checkpoint PATH` saves the run there at the end of every `--checkpoint-every`-th epoch (default 1) and times one save
+at the end; `--resume` continues from that file when it exists.
+usage (MI355X box): python tools/soak_training.py [epochs] [--checkpoint PATH [--checkpoint-every K] [--resume]]"""
+import argparse, math, os, sys, time
 import numpy as np
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "st-dadk_amd"))
 from stnf.models import STInterpMLP
 from stnf.engine import TrainStep
-from stnf.training import train_model, evaluate_model
+from stnf.training import train_model, evaluate_model, make_engine
+from stnf.checkpoint import save_checkpoint
 from stnf.dataio.device_dataset import DeviceDataset
 from stnf.utils import set_seed
 
-epochs = int(sys.argv[1]) if len(sys.argv) > 1 else 60
+ap = argparse.ArgumentParser()
+ap.add_argument("epochs", nargs="?", type=int, default=60)
+ap.add_argument("--checkpoint", default=None)
+ap.add_argument("--checkpoint-every", type=int, default=1)
+ap.add_argument("--resume", action="store_true")
+args = ap.parse_args()
+epochs = args.epochs
 set_seed(0)
 rs = np.random.RandomState(0)
 S, T = 2000, 100
@@ -35,10 +44,25 @@ nb = math.ceil(len(ds) / B)
 config = {"lr": 2e-2, "weight_decay": 5e-4, "grad_clip": 10.0, "batch_size": B, "epochs": epochs, "scheduler": "cosine",
           "patience": epochs + 1}
 g = torch.Generator(device=d).manual_seed(0)
+eng = make_engine(m, config, B, nb)
 t0 = time.perf_counter()
-m, hist, _ = train_model(m, ds, dv, config, generator=g)          # validation under EMA after every epoch
+m, hist, _ = train_model(m, ds, dv, config, generator=g, engine=eng,     # validation under EMA after every epoch
+                         checkpoint=args.checkpoint, checkpoint_every=args.checkpoint_every, resume=args.resume)
 torch.cuda.synchronize()
 el = time.perf_counter() - t0
+print(f"epoch time incl. validation{' and checkpoints' if args.checkpoint else ''}: {1e3 * el / epochs:.2f} ms "
+      f"(wall time of this call / {epochs} epochs)")
+if args.checkpoint:
+    saves = []
+    for _ in range(5):
+        t1 = time.perf_counter()
+        save_checkpoint(args.checkpoint + ".probe", eng)
+        saves.append(1e3 * (time.perf_counter() - t1))
+    probe_size = os.path.getsize(args.checkpoint + ".probe")
+    os.remove(args.checkpoint + ".probe")
+    print(f"one save of the engine's state alone (file of {probe_size / 2 ** 20:.1f} MiB): "
+          f"{sorted(saves)[2]:.1f} ms (median of 5: {', '.join(f'{s:.1f}' for s in saves)}); the driver's file, with "
+          f"its best state: {os.path.getsize(args.checkpoint) / 2 ** 20:.1f} MiB")
 rmse_clean = evaluate_model(m, clean, config)["rmse"]               # the returned model holds the best EMA state
 assert all(math.isfinite(v) for v in hist["train_loss"] + hist["val_rmse"])
 print(f"best held-out RMSE vs noisy {min(hist['val_rmse']):.4f} (noise floor 0.1000)  vs the noise-free field {rmse_clean:.4f}")
