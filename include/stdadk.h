@@ -731,6 +731,50 @@ int stdadk_gmm_em_f64(const double *X, int64_t n, int32_t k, const double *w, co
                       double reg_covar, double *w_out, double *mu_out, double *var_out, double *lower_bound,
                       void *workspace, size_t workspace_bytes, stdadk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Knot initialiser `spatial_init_method: kmeans_balanced` (added under ABI 10: new entry points only, so
+ * STDADK_ABI_VERSION stays 10): ONE iteration of size-constrained k-means in two dimensions.  The reference
+ * (stnf/models/st_interp.py:345-431) fits the k_means_constrained package's KMeansConstrained; this library states a
+ * contract of its own and does NOT claim that package's bits: the knots are a size-constrained k-means fit under
+ * the contract below, nothing more.
+ *
+ * The fit (host side, stnf.knot_init.fit_balanced_kmeans), all float64:
+ *   points   P = at most 10 000 rows of the training coordinates (the reference's global-numpy-RNG draw, :367-375)
+ *   bounds   of a level of k knots on n = len(P) points: lo = max(1, n / k - 1), hi = n / k + n % k (integer division;
+ *            :379-385); k > n is an error, and k lo <= n <= k hi always holds otherwise
+ *   restarts the three seed index arrays of sklearn's kmeans_plusplus on one RandomState(42), in sequence; the centres
+ *            start at the seed rows
+ *   one restart, at most 100 iterations:  tol = 1e-4 mean(var(P, axis 0)), mu = P[seeds], then
+ *            E: labels = the assignment minimising sum_i |x_i - mu_labels[i]|^2 subject to lo <= |cluster j| <= hi for
+ *               every j -- the EXACT optimum; inertia = that minimum
+ *            M: mu_new[j] = mean of the members of j (none is empty: lo >= 1), a fixed summation order
+ *            shift = sum |mu_new - mu|^2; mu = mu_new; stop when shift <= tol
+ *            the result is mu and the inertia of the last E-step
+ *   the restart with the lowest inertia is kept, the first on a tie
+ *   knots    centres = mu as float32; bandwidth = 2.5 x the mean distance to the min(4, k - 1) nearest other centres of
+ *            the level, the grid bandwidth of n_centers[0] for k == 1 (:400-422, the arithmetic of random_site)
+ *
+ * This call is one iteration: E on mu, M into mu_out.  All pointers are device pointers:
+ *   X [n][2] points; mu [k][2] centres; mu_out [k][2]; labels [n] (int32, out); stats [2] = {inertia, shift};
+ *   status [2] (int32) = {0 or which bound stopped the assignment, unit augmentations made}.
+ * Costs: c_ij = (x_i - mu_jx)^2 + (y_i - mu_jy)^2 in float64, every operation rounded once (no fused multiply-add).
+ * The E-step works on q_ij = rint(c_ij 2^s) as 64-bit integers, s = 52 - e where max c = f 2^e, 0.5 <= f < 1 (s = 0
+ * when max c = 0): one binary grid of spacing at most max c 2^-51, on which path sums are exact, so that the cycles of
+ * exact weight 0 that duplicated points produce cannot round to negative ones.  The labels are an exact optimum for
+ * q (successive shortest paths, one unit at a time, from the nearest-centre assignment, lowest index on every tie;
+ * csrc/kmeans.hip), hence within n max c 2^-51 of the optimum for c.  inertia = sum_i c_i,labels[i].
+ * Every loop of the kernels is bounded (augmentations <= n, Bellman-Ford rounds <= k + 1); a bound hit -- which the
+ * method rules out -- writes status[0] != 0 and stops, and mu_out is then meaningless.
+ * 1 <= k <= 1023, k <= n, n k < 2^31 (STDADK_E_ARG / STDADK_E_SHAPE), 1 <= lo <= hi, lo k <= n <= hi k
+ * (STDADK_E_SHAPE).  Outputs must not alias inputs, each other or the workspace (STDADK_E_ARG).  Deterministic (no
+ * float atomics, fixed orders).  Workspace: stdadk_kmeans_workspace_bytes(n, k) (0 = bad sizes), 8-byte aligned.  No
+ * host read of device memory, no allocation, capturable.
+ * ------------------------------------------------------------------------------------------ */
+size_t stdadk_kmeans_workspace_bytes(int64_t n, int32_t k);
+int stdadk_kmeans_balanced_iter_f64(const double *X, int64_t n, int32_t k, const double *mu, int32_t lo, int32_t hi,
+                                    double *mu_out, int32_t *labels, double *stats, int32_t *status, void *workspace,
+                                    size_t workspace_bytes, stdadk_stream_t stream);
+
 /* A10 on a site x time prediction grid (the dense inference callers loop over time slices with the SAME S
  * sites in each, scripts/train_st_interp.py:1091-1107,1232-1248,1378-1409).  Layer 0's pre-activation of row
  * (ti, s) is  sum_k phi_k(s) W0^T[p+k,:]  +  sum_j psi_j(t_ti) W0^T[p+Ks+j,:]  +  b0 : a per-site row plus a per-time

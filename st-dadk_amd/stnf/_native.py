@@ -217,6 +217,10 @@ _SIGNATURES = {
     "stdadk_gmm_em_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                     C.c_void_p]),
+    "stdadk_kmeans_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "stdadk_kmeans_balanced_iter_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p]),
     "stdadk_bin_batch_f32": (C.c_int, [C.POINTER(BasisDesc), C.POINTER(MlpDesc), C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                        C.c_size_t, C.c_int32, C.c_void_p]),
@@ -813,6 +817,48 @@ def gmm_em(X, w, mu, var, reg_covar, w_out, mu_out, var_out, lower_bound, worksp
         float(reg_covar), _f64(w_out, "w_out", (k,)), _f64(mu_out, "mu_out", (k, 2)), _f64(var_out, "var_out", (k,)),
         _f64(lower_bound, "lower_bound", (1,)), _f64(workspace, "workspace", None), workspace.numel() * 8, _stream())
     _check(rc, "stdadk_gmm_em_f64")
+
+
+KMEANS_MAX_K = 1023        # KM_MAX_K of csrc/kmeans.hip
+KMEANS_STATUS = {1: "more augmentations than points", 2: "Bellman-Ford did not settle in k + 1 rounds",
+                 3: "no deficit node reachable", 4: "the predecessors form a cycle", 5: "a path arc without a point"}
+
+
+def kmeans_workspace_bytes(n, k):
+    nbytes = lib().stdadk_kmeans_workspace_bytes(n, k)
+    if nbytes == 0:
+        raise RuntimeError(f"stdadk_kmeans_workspace_bytes: bad sizes n={n}, k={k} (n >= 1, 1 <= k <= {KMEANS_MAX_K}, "
+                           f"n k < 2^31)")
+    return nbytes
+
+
+def _dev_typed(tensor, name, dtype, shape, what):
+    """Address of a contiguous tensor of `dtype` and `shape` on the current HIP device."""
+    if tensor.dtype != dtype or not _on_device(tensor) or not tensor.is_contiguous() \
+            or (shape is not None and tuple(tensor.shape) != shape):
+        raise RuntimeError(f"{what}: {name} must be a contiguous {dtype} tensor{'' if shape is None else f' of shape {shape}'}"
+                           f" on the device, got {tensor.dtype} {tuple(tensor.shape)} on {tensor.device}")
+    if tensor.is_cuda and tensor.device.index != _current_device():
+        raise RuntimeError(f"{what}: {name} lives on {tensor.device} but the current device is cuda:"
+                           f"{torch.cuda.current_device()}; call under torch.cuda.device({tensor.device.index})")
+    return tensor.data_ptr()
+
+
+def kmeans_balanced_iter(X, mu, lo, hi, mu_out, labels, stats, status, workspace):
+    """stdadk_kmeans_balanced_iter_f64: one iteration of size-constrained k-means in float64 -- the exact assignment
+    of the points X (n, 2) to the centres mu (k, 2) with lo <= |cluster| <= hi into labels (n,) int32, the clusters'
+    means into mu_out (k, 2), {inertia, shift} into stats (2,) float64, {stop code, augmentations} into status (2,)
+    int32.  Nothing is read back here: the caller reads stats and status.  Outputs must not alias inputs."""
+    if X.dim() != 2 or X.shape[1] != 2:
+        raise RuntimeError(f"kmeans_balanced_iter: X must be (n, 2), got {tuple(X.shape)}")
+    n, k = X.shape[0], mu.shape[0] if mu.dim() == 2 else -1
+    f64 = lambda t, name, shape: _dev_typed(t, name, torch.float64, shape, "kmeans_balanced_iter")      # noqa: E731
+    i32 = lambda t, name, shape: _dev_typed(t, name, torch.int32, shape, "kmeans_balanced_iter")        # noqa: E731
+    rc = lib().stdadk_kmeans_balanced_iter_f64(
+        f64(X, "X", (n, 2)), n, k, f64(mu, "mu", (k, 2)), int(lo), int(hi), f64(mu_out, "mu_out", (k, 2)),
+        i32(labels, "labels", (n,)), f64(stats, "stats", (2,)), i32(status, "status", (2,)),
+        f64(workspace, "workspace", None), workspace.numel() * 8, _stream())
+    _check(rc, "stdadk_kmeans_balanced_iter_f64")
 
 
 def make_knot_train(centers_init, gradient_damping=False, damping_threshold=0.3, damping_strength=1.0,

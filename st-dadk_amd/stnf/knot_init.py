@@ -6,6 +6,12 @@ What stays on the host: the draw of the subsample (the same global-numpy-RNG cal
 seeding (sklearn's own public sklearn.cluster.kmeans_plusplus on one RandomState(42), three calls in sequence: exactly
 what GaussianMixture(random_state=42, n_init=3, init_params='k-means++') does), the first M-step from the one-hot
 responsibilities of the seeds (k rows), and the convergence test: one 8-byte read of the lower bound per iteration.
+
+`spatial_init_method: kmeans_balanced` (reference :345-431, which needs the k_means_constrained package) is fitted here
+too, under the contract of include/stdadk.h: size-constrained k-means whose every assignment step is the exact optimum,
+one stdadk_kmeans_balanced_iter_f64 call per iteration.  The knots are such a fit; they are NOT claimed to be the bits
+that package would return.  On the host stay the subsample, the k-means++ seeds (the same three per level as above) and
+the convergence test: one 16-byte read of {inertia, shift} and the 8-byte status per iteration.
 """
 import collections
 import math
@@ -21,6 +27,7 @@ N_INIT = 3
 RANDOM_STATE = 42
 
 GmmFit = collections.namedtuple("GmmFit", "weights means variances lower_bound n_iter best lower_bounds")
+KMeansFit = collections.namedtuple("KMeansFit", "centers labels inertia n_iter best inertias")
 
 
 def seed_parameters(points, idx, reg_covar):
@@ -125,4 +132,99 @@ def gmm_knots(train_coords, n_centers, device):
         c, b = knots_from_fit(fit.means.cpu().numpy(), fit.variances.cpu().numpy(), k)
         cs.append(c)
         bs.append(b)
+    return torch.cat(cs, dim=0), torch.cat(bs, dim=0)
+
+
+def balanced_bounds(n, k):
+    """(lo, hi) cluster sizes of a level of k knots on n points (reference :379-385)."""
+    if k > n:
+        raise ValueError(f"kmeans_balanced: {k} knots need at least {k} points, got {n}")
+    return max(1, n // k - 1), n // k + n % k
+
+
+def fit_balanced_kmeans(points64, k, seed_indices, max_iter=100, tol_factor=1e-4, history=None):
+    """Size-constrained k-means with `k` clusters on points64 ((n, 2) float64 on a HIP device), one restart per index
+    array of `seed_indices` (the k rows the centres start at).  Each iteration is one stdadk_kmeans_balanced_iter_f64
+    call (the exact assignment under lo <= |cluster| <= hi, then the means) and stops when the centres' squared shift is
+    at most tol_factor x mean(var(points, axis 0)); the restart with the lowest inertia is kept, the first on a tie.
+    Returns KMeansFit(centers (k, 2) float64 and labels (n,) int32 device tensors, inertia, per-restart n_iter, the
+    chosen restart, per-restart inertias).  `history`, a list, receives per restart the list of (inertia, shift,
+    augmentations) of every iteration."""
+    if points64.dtype != torch.float64 or points64.dim() != 2 or points64.shape[1] != 2:
+        raise RuntimeError(f"fit_balanced_kmeans: points must be (n, 2) float64, got {points64.dtype} {tuple(points64.shape)}")
+    if not points64.is_cuda:
+        raise RuntimeError(f"fit_balanced_kmeans: points must live on a HIP device (cuda:N), got {points64.device}; "
+                           f"there is no host path (it needs the k_means_constrained package)")
+    if len(seed_indices) == 0:
+        raise ValueError("fit_balanced_kmeans: no restart given")
+    points64 = points64.contiguous()
+    dev, n, k = points64.device, points64.shape[0], int(k)
+    lo, hi = balanced_bounds(n, k)
+    host = points64.cpu().numpy()
+    tol = tol_factor * float(np.mean(np.var(host, axis=0)))
+    ws = torch.empty(N.kmeans_workspace_bytes(n, k) // 8, device=dev, dtype=torch.float64)
+    stats = torch.empty(2, device=dev, dtype=torch.float64)
+    status = torch.empty(2, device=dev, dtype=torch.int32)
+    best, best_inertia, best_out, n_iters, inertias = -1, math.inf, None, [], []
+    with torch.cuda.device(dev):
+        for r, idx in enumerate(seed_indices):
+            idx = np.asarray(idx, np.int64)
+            if idx.shape != (k,):
+                raise ValueError(f"fit_balanced_kmeans: restart {r} has {idx.shape} seeds, {k} clusters expected")
+            cur = torch.from_numpy(host[idx]).to(dev)
+            nxt = torch.empty_like(cur)
+            labels = torch.empty(n, device=dev, dtype=torch.int32)
+            trace, it, inertia = [], 0, math.inf
+            for it in range(1, max_iter + 1):
+                N.kmeans_balanced_iter(points64, cur, lo, hi, nxt, labels, stats, status, ws)
+                cur, nxt = nxt, cur
+                inertia, shift = stats.tolist()
+                code, n_aug = status.tolist()
+                if code != 0:
+                    raise RuntimeError(f"fit_balanced_kmeans: the assignment of restart {r}, iteration {it} stopped on a "
+                                       f"bound (status {code}: {N.KMEANS_STATUS.get(code, '?')}) after {n_aug} augmentations")
+                trace.append((inertia, shift, n_aug))
+                if shift <= tol:
+                    break
+            n_iters.append(it)
+            inertias.append(inertia)
+            if history is not None:
+                history.append(trace)
+            if best < 0 or inertia < best_inertia:
+                best, best_inertia, best_out = r, inertia, (cur, labels)
+    return KMeansFit(best_out[0], best_out[1], best_inertia, n_iters, best, inertias)
+
+
+def neighbour_bandwidths(centers, k, k0):
+    """Bandwidths (k,) of scattered knots, numpy: 2.5 x the mean distance to the min(4, k - 1) nearest other centres of
+    the level; the grid bandwidth of k0 (= n_centers[0]) knots for k == 1 (reference :320-341 and :400-422, the same
+    arithmetic behind random_site and kmeans_balanced)."""
+    from scipy.spatial.distance import cdist
+    dist = cdist(centers, centers)
+    np.fill_diagonal(dist, np.inf)
+    nn = min(4, k - 1) if k > 1 else 1
+    bw = 2.5 * np.sort(dist, axis=1)[:, :nn].mean(axis=1)
+    if k == 1:
+        bw = np.array([grid_bandwidth(k0)])
+    return bw
+
+
+def balanced_kmeans_knots(train_coords, n_centers, device):
+    """The reference's _init_kmeans_balanced with the fit of fit_balanced_kmeans on `device`: (centres (sum k, 2),
+    bandwidths (sum k,)) float32 host tensors, levels concatenated in list order."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"balanced_kmeans_knots: a HIP device (cuda:N) is required, got {device}; without "
+                           f"init_device the initialiser needs the k_means_constrained package")
+    pts = subsample(train_coords)
+    for k in n_centers:
+        balanced_bounds(len(pts), k)
+    seeds = kmeanspp_seeds(pts, n_centers)
+    pts_dev = torch.from_numpy(pts).to(device)
+    cs, bs = [], []
+    for k, level_seeds in zip(n_centers, seeds):
+        fit = fit_balanced_kmeans(pts_dev, k, level_seeds)
+        c = fit.centers.cpu().numpy()
+        cs.append(torch.from_numpy(c).float())
+        bs.append(torch.from_numpy(neighbour_bandwidths(c, k, n_centers[0])).float())
     return torch.cat(cs, dim=0), torch.cat(bs, dim=0)

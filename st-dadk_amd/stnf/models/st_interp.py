@@ -112,7 +112,12 @@ class SpatialBasisEmbedding(nn.Module):
             centers, bandwidths = self._init_random_site(train_coords)
         elif init_method == 'kmeans_balanced':
             assert train_coords is not None, "train_coords required for kmeans_balanced initialization"
-            raise NotImplementedError(f"spatial_init_method='kmeans_balanced' {_SCOPE_MSG}")
+            # init_device: None = the reference's host path, which needs a package that is not here; a HIP device =
+            # size-constrained k-means under this project's own contract (stnf.knot_init, include/stdadk.h)
+            if init_device is None:
+                raise NotImplementedError(f"spatial_init_method='kmeans_balanced' {_SCOPE_MSG}")
+            from ..knot_init import balanced_kmeans_knots
+            centers, bandwidths = balanced_kmeans_knots(train_coords, n_centers, init_device)
         else:
             raise ValueError(f"Unknown init_method: {init_method}")
         if learnable:
@@ -185,18 +190,13 @@ class SpatialBasisEmbedding(nn.Module):
         """Knots drawn from the training coordinates themselves (reference :266-343): per level k
         rows picked with the global numpy RNG (without replacement when there are enough), bandwidth
         = 2.5 x the mean distance to the (up to) 4 nearest other knots of the level."""
-        from scipy.spatial.distance import cdist
+        from ..knot_init import neighbour_bandwidths
         pts = np.asarray(train_coords)
         cs, bs = [], []
         for k in self.n_centers:
             pick = np.random.choice(len(pts), k, replace=k > len(pts))
             c = pts[pick]
-            dist = cdist(c, c)
-            np.fill_diagonal(dist, np.inf)
-            nn = min(4, k - 1) if k > 1 else 1
-            bw = 2.5 * np.sort(dist, axis=1)[:, :nn].mean(axis=1)
-            if k == 1:
-                bw = np.array([self._grid_bandwidth(self.n_centers[0])])
+            bw = neighbour_bandwidths(c, k, self.n_centers[0])
             cs.append(torch.from_numpy(c).float())
             bs.append(torch.from_numpy(bw).float())
         return torch.cat(cs, dim=0), torch.cat(bs, dim=0)
