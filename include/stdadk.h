@@ -775,6 +775,42 @@ int stdadk_kmeans_balanced_iter_f64(const double *X, int64_t n, int32_t k, const
                                     double *mu_out, int32_t *labels, double *stats, int32_t *status, void *workspace,
                                     size_t workspace_bytes, stdadk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * k-means++ seeding for the gmm and kmeans_balanced knot initialisers (added under ABI 10: new entry points only, so
+ * STDADK_ABI_VERSION stays 10): `runs` independent runs of sklearn's greedy k-means++ (_kmeans_plusplus, unit sample
+ * weights) in two dimensions, entirely in float64.  The random stream does not depend on the data, so the caller draws
+ * it in advance; this call does the data-dependent part.  All pointers are device pointers:
+ *   X [n][2] points; first [runs] (int32) each run's first seed row, clamped to [0, n); u [runs][k-1][L] uniforms in
+ *   [0, 1); idx_out [runs][k] (int32) the chosen seed rows; pot_out [runs] each run's final potential.
+ * Distances are direct, every operation rounded once (no fused multiply-add):
+ *   d_i = min over the chosen centres of (x_i0 - c0)^2 + (x_i1 - c1)^2; a point equal to a chosen centre has d_i == 0
+ *   exactly; pot = sum_i d_i.
+ * One step, for c = 1 .. k-1:
+ *   thresholds   r_j = u[c-1][j] pot,  j = 0 .. L-1
+ *   candidates   cand_j = the smallest i with P_i >= r_j, where P_i = d_0 + ... + d_i; n - 1 when there is none
+ *   potentials   pot_j = sum_i min(d_i, |x_i - x_cand_j|^2)
+ *   choice       the candidate with the smallest pot_j, the lowest j on ties: its row is idx_out[c], its minima become
+ *                d and its pot_j becomes pot
+ * P_i, pot and pot_j are sums of non-negative terms in one fixed order of the kernel's choosing (csrc/kmeanspp.hip:
+ * chunks of rows, 32 chunks to a group, 32 groups, each level added left to right); P_i is non-decreasing in i, P_n-1
+ * is pot bit for bit, and the order does not depend on j, so that two candidates with the same coordinates get the
+ * same pot_j.  A pick can differ from the one strict left-to-right sums give only where rounding decides it: r_j within
+ * the rounding of a prefix sum, or two candidates whose pot_j differ by less than the rounding of the sums (mutually
+ * nearest candidates tie in exact arithmetic; frequent only when k nears the number of distinct points).  With pot == 0 (every point on a chosen centre) every r_j is 0 and the pick is row 0; outputs stay
+ * finite and every loop has a fixed trip count.
+ * 1 <= n < 2^31, 1 <= k <= min(n, 65536), 1 <= runs <= 64, 1 <= L <= 16 (STDADK_E_ARG); k == 1 reads no u (u may be
+ * NULL).  X, u, pot_out and the workspace 8-byte aligned, first and idx_out 4-byte aligned (STDADK_E_ALIGN).  Outputs
+ * must not alias the inputs, each other or the workspace (STDADK_E_ARG).  One workgroup per run, no atomics, nothing
+ * waits on another workgroup; deterministic: the same call gives the same bits.  Up to n = 10 240 the points and d stay
+ * in registers; beyond that d lives in the workspace (any n gives correct results, only the register path is fast).
+ * Workspace: stdadk_kmeanspp_workspace_bytes(n, k, runs) (0 = bad sizes; STDADK_E_WORKSPACE).  No host read of device
+ * memory, no allocation, capturable.
+ * ------------------------------------------------------------------------------------------ */
+size_t stdadk_kmeanspp_workspace_bytes(int64_t n, int32_t k, int32_t runs);
+int stdadk_kmeanspp_f64(const double *X, int64_t n, int32_t k, int32_t runs, int32_t L, const int32_t *first,
+                        const double *u, int32_t *idx_out, double *pot_out, void *workspace, size_t workspace_bytes,
+                        stdadk_stream_t stream);
+
 /* A10 on a site x time prediction grid (the dense inference callers loop over time slices with the SAME S
  * sites in each, scripts/train_st_interp.py:1091-1107,1232-1248,1378-1409).  Layer 0's pre-activation of row
  * (ti, s) is  sum_k phi_k(s) W0^T[p+k,:]  +  sum_j psi_j(t_ti) W0^T[p+Ks+j,:]  +  b0 : a per-site row plus a per-time

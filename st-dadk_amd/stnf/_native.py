@@ -221,6 +221,9 @@ _SIGNATURES = {
     "stdadk_kmeans_balanced_iter_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                   C.c_void_p]),
+    "stdadk_kmeanspp_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "stdadk_kmeanspp_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "stdadk_bin_batch_f32": (C.c_int, [C.POINTER(BasisDesc), C.POINTER(MlpDesc), C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                        C.c_size_t, C.c_int32, C.c_void_p]),
@@ -859,6 +862,37 @@ def kmeans_balanced_iter(X, mu, lo, hi, mu_out, labels, stats, status, workspace
         i32(labels, "labels", (n,)), f64(stats, "stats", (2,)), i32(status, "status", (2,)),
         f64(workspace, "workspace", None), workspace.numel() * 8, _stream())
     _check(rc, "stdadk_kmeans_balanced_iter_f64")
+
+
+KMEANSPP_MAX_K, KMEANSPP_MAX_RUNS, KMEANSPP_MAX_L = 65536, 64, 16        # KPP_MAX_* of csrc/kmeanspp.hip
+
+
+def kmeanspp_workspace_bytes(n, k, runs):
+    nbytes = lib().stdadk_kmeanspp_workspace_bytes(n, k, runs)
+    if nbytes == 0:
+        raise RuntimeError(f"stdadk_kmeanspp_workspace_bytes: bad sizes n={n}, k={k}, runs={runs} (1 <= n < 2^31, "
+                           f"1 <= k <= min(n, {KMEANSPP_MAX_K}), 1 <= runs <= {KMEANSPP_MAX_RUNS})")
+    return nbytes
+
+
+def kmeanspp(X, first, u, idx_out, pot_out, workspace):
+    """stdadk_kmeanspp_f64: `runs` independent greedy k-means++ runs in float64 on the points X (n, 2) -- first (runs,)
+    int32 the first seed rows, u (runs, k - 1, L) float64 the uniforms behind the L candidates of every further centre
+    (both drawn by the caller), the chosen rows into idx_out (runs, k) int32, the final potentials into pot_out (runs,).
+    Nothing is read back here.  Outputs must not alias inputs."""
+    if X.dim() != 2 or X.shape[1] != 2:
+        raise RuntimeError(f"kmeanspp: X must be (n, 2), got {tuple(X.shape)}")
+    if idx_out.dim() != 2 or u.dim() != 3:
+        raise RuntimeError(f"kmeanspp: idx_out must be (runs, k) and u (runs, k - 1, L), got {tuple(idx_out.shape)} and "
+                           f"{tuple(u.shape)}")
+    n, (runs, k), L = X.shape[0], idx_out.shape, u.shape[2]
+    f64 = lambda t, name, shape: _dev_typed(t, name, torch.float64, shape, "kmeanspp")      # noqa: E731
+    i32 = lambda t, name, shape: _dev_typed(t, name, torch.int32, shape, "kmeanspp")        # noqa: E731
+    rc = lib().stdadk_kmeanspp_f64(
+        f64(X, "X", (n, 2)), n, k, runs, L, i32(first, "first", (runs,)), f64(u, "u", (runs, k - 1, L)),
+        i32(idx_out, "idx_out", (runs, k)), f64(pot_out, "pot_out", (runs,)), f64(workspace, "workspace", None),
+        workspace.numel() * 8, _stream())
+    _check(rc, "stdadk_kmeanspp_f64")
 
 
 def make_knot_train(centers_init, gradient_damping=False, damping_threshold=0.3, damping_strength=1.0,

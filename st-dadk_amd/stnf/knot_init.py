@@ -7,11 +7,18 @@ seeding (sklearn's own public sklearn.cluster.kmeans_plusplus on one RandomState
 what GaussianMixture(random_state=42, n_init=3, init_params='k-means++') does), the first M-step from the one-hot
 responsibilities of the seeds (k rows), and the convergence test: one 8-byte read of the lower bound per iteration.
 
+With seeding='device' the seeding moves too: the host draws only sklearn's random stream, which does not depend on the
+data (kmeanspp_stream), and one stdadk_kmeanspp_f64 call per level runs the three restarts side by side
+(kmeanspp_seeds_device).  The seeds are sklearn's in coordinates unless a pick is decided by the rounding of a sum -- a
+threshold on a prefix-sum boundary, or two mutually nearest candidates whose potentials tie in exact arithmetic, which
+becomes common only when k nears the number of distinct points (include/stdadk.h); seeding='host',
+the default, stays bit for bit what it was.
+
 `spatial_init_method: kmeans_balanced` (reference :345-431, which needs the k_means_constrained package) is fitted here
 too, under the contract of include/stdadk.h: size-constrained k-means whose every assignment step is the exact optimum,
 one stdadk_kmeans_balanced_iter_f64 call per iteration.  The knots are such a fit; they are NOT claimed to be the bits
 that package would return.  On the host stay the subsample, the k-means++ seeds (the same three per level as above) and
-the convergence test: one 16-byte read of {inertia, shift} and the 8-byte status per iteration.
+the convergence test: one 16-byte read of {inertia, shift} and the 8-byte status per iteration; seeding='device' as above.
 """
 import collections
 import math
@@ -117,15 +124,71 @@ def kmeanspp_seeds(points, n_centers):
     return out
 
 
-def gmm_knots(train_coords, n_centers, device):
+def kmeanspp_trials(k):
+    """Candidates per further centre: sklearn's n_local_trials = 2 + floor(ln k)."""
+    return 2 + int(np.log(k))
+
+
+def kmeanspp_stream(n, n_centers):
+    """The random numbers behind kmeanspp_seeds, which do not depend on the points: per level (first (N_INIT,) int32,
+    u (N_INIT, k - 1, L) float64) with L = kmeanspp_trials(k).  Every level opens a fresh RandomState(42); per restart,
+    in sequence, the first row is drawn as sklearn's _kmeans_plusplus draws it for unit weights, then L uniforms for each
+    of the k - 1 further centres."""
+    out = []
+    p = np.ones(n, dtype=np.float64) / float(n)
+    for k in n_centers:
+        rs = np.random.RandomState(RANDOM_STATE)
+        L = kmeanspp_trials(k)
+        first, u = np.empty(N_INIT, np.int32), np.empty((N_INIT, k - 1, L), np.float64)
+        for r in range(N_INIT):
+            first[r] = rs.choice(n, p=p)
+            u[r] = rs.uniform(size=(k - 1, L))         # the same numbers as k - 1 draws of L, in one call
+        out.append((first, u))
+    return out
+
+
+def kmeanspp_seeds_device(points64, n_centers):
+    """kmeanspp_seeds with the data-dependent part on the device: points64 (n, 2) float64 on a HIP device; per level one
+    stdadk_kmeanspp_f64 call with runs = N_INIT on the stream of kmeanspp_stream and one read of the N_INIT x k rows."""
+    if points64.dtype != torch.float64 or points64.dim() != 2 or points64.shape[1] != 2 or not points64.is_cuda:
+        raise RuntimeError(f"kmeanspp_seeds_device: points must be (n, 2) float64 on a HIP device, got {points64.dtype} "
+                           f"{tuple(points64.shape)} on {points64.device}")
+    points64 = points64.contiguous()
+    dev, n = points64.device, points64.shape[0]
+    for k in n_centers:
+        if not 1 <= k <= min(n, N.KMEANSPP_MAX_K):
+            raise ValueError(f"kmeanspp_seeds_device: {k} seeds on {n} points (1 <= k <= min(n, {N.KMEANSPP_MAX_K}))")
+    out = []
+    with torch.cuda.device(dev):
+        for k, (first, u) in zip(n_centers, kmeanspp_stream(n, n_centers)):
+            idx = torch.empty(N_INIT, k, device=dev, dtype=torch.int32)
+            pot = torch.empty(N_INIT, device=dev, dtype=torch.float64)
+            ws = torch.empty(N.kmeanspp_workspace_bytes(n, k, N_INIT) // 8, device=dev, dtype=torch.float64)
+            N.kmeanspp(points64, torch.from_numpy(first).to(dev), torch.from_numpy(u).to(dev), idx, pot, ws)
+            out.append(list(idx.cpu().numpy().astype(np.int64)))
+    return out
+
+
+SEEDINGS = ('host', 'device')
+
+
+def seeds_by_level(pts, pts_dev, n_centers, seeding):
+    """The N_INIT seed index arrays of every level, by sklearn on the host or by the kernel on the points' device."""
+    return kmeanspp_seeds(pts, n_centers) if seeding == 'host' else kmeanspp_seeds_device(pts_dev, n_centers)
+
+
+def gmm_knots(train_coords, n_centers, device, seeding='host'):
     """The reference's _init_gmm with the mixture fitted on `device`: (centres (sum k, 2), bandwidths (sum k,)) float32
-    host tensors, levels concatenated in list order."""
+    host tensors, levels concatenated in list order.  seeding: 'host' = sklearn's kmeans_plusplus, 'device' = the same
+    random stream through stdadk_kmeanspp_f64."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"gmm_knots: a HIP device (cuda:N) is required, got {device}; init_device=None is the host path")
+    if seeding not in SEEDINGS:
+        raise ValueError(f"gmm_knots: seeding must be one of {SEEDINGS}, got {seeding!r}")
     pts = subsample(train_coords)
-    seeds = kmeanspp_seeds(pts, n_centers)
     pts_dev = torch.from_numpy(pts).to(device)
+    seeds = seeds_by_level(pts, pts_dev, n_centers, seeding)
     cs, bs = [], []
     for k, level_seeds in zip(n_centers, seeds):
         fit = fit_spherical_gmm(pts_dev, k, level_seeds, max_iter=100, tol=1e-3, reg_covar=1e-6)
@@ -209,18 +272,20 @@ def neighbour_bandwidths(centers, k, k0):
     return bw
 
 
-def balanced_kmeans_knots(train_coords, n_centers, device):
+def balanced_kmeans_knots(train_coords, n_centers, device, seeding='host'):
     """The reference's _init_kmeans_balanced with the fit of fit_balanced_kmeans on `device`: (centres (sum k, 2),
-    bandwidths (sum k,)) float32 host tensors, levels concatenated in list order."""
+    bandwidths (sum k,)) float32 host tensors, levels concatenated in list order.  seeding as in gmm_knots."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"balanced_kmeans_knots: a HIP device (cuda:N) is required, got {device}; without "
                            f"init_device the initialiser needs the k_means_constrained package")
+    if seeding not in SEEDINGS:
+        raise ValueError(f"balanced_kmeans_knots: seeding must be one of {SEEDINGS}, got {seeding!r}")
     pts = subsample(train_coords)
     for k in n_centers:
         balanced_bounds(len(pts), k)
-    seeds = kmeanspp_seeds(pts, n_centers)
     pts_dev = torch.from_numpy(pts).to(device)
+    seeds = seeds_by_level(pts, pts_dev, n_centers, seeding)
     cs, bs = [], []
     for k, level_seeds in zip(n_centers, seeds):
         fit = fit_balanced_kmeans(pts_dev, k, level_seeds)

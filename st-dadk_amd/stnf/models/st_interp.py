@@ -85,7 +85,8 @@ class SpatialBasisEmbedding(nn.Module):
     def __init__(self, n_centers: list = [25, 81, 121], learnable: bool = False,
                  init_method: str = 'uniform', train_coords: np.ndarray = None,
                  basis_function: str = 'wendland', gradient_damping: bool = False,
-                 damping_threshold: float = 0.3, damping_strength: float = 1.0, init_device=None):
+                 damping_threshold: float = 0.3, damping_strength: float = 1.0, init_device=None,
+                 init_seeding: str = 'host'):
         super().__init__()
         self.n_centers = n_centers
         self.learnable = learnable
@@ -97,6 +98,12 @@ class SpatialBasisEmbedding(nn.Module):
         if basis_function not in self.CALIBRATION_FACTORS:
             raise ValueError(f"Unknown basis function: {basis_function}. "
                              f"Choose from {list(self.CALIBRATION_FACTORS.keys())}")
+        # init_seeding: where the k-means++ seeds of gmm / kmeans_balanced come from: 'host' = sklearn's kmeans_plusplus,
+        # 'device' = the same random stream through stdadk_kmeanspp_f64 on init_device.  Other initialisers ignore it.
+        if init_seeding not in ('host', 'device'):
+            raise ValueError(f"Unknown init_seeding: {init_seeding!r}. Choose from ['host', 'device']")
+        if init_seeding == 'device' and init_device is None and init_method in ('gmm', 'kmeans_balanced'):
+            raise ValueError(f"init_seeding='device' needs init_device (spatial_init_device) for init_method={init_method!r}")
         if init_method == 'uniform':
             centers, bandwidths = self._init_uniform()
         elif init_method == 'gmm':
@@ -106,7 +113,7 @@ class SpatialBasisEmbedding(nn.Module):
                 centers, bandwidths = self._init_gmm(train_coords)
             else:
                 from ..knot_init import gmm_knots
-                centers, bandwidths = gmm_knots(train_coords, n_centers, init_device)
+                centers, bandwidths = gmm_knots(train_coords, n_centers, init_device, seeding=init_seeding)
         elif init_method == 'random_site':
             assert train_coords is not None, "train_coords required for random_site initialization"
             centers, bandwidths = self._init_random_site(train_coords)
@@ -117,7 +124,7 @@ class SpatialBasisEmbedding(nn.Module):
             if init_device is None:
                 raise NotImplementedError(f"spatial_init_method='kmeans_balanced' {_SCOPE_MSG}")
             from ..knot_init import balanced_kmeans_knots
-            centers, bandwidths = balanced_kmeans_knots(train_coords, n_centers, init_device)
+            centers, bandwidths = balanced_kmeans_knots(train_coords, n_centers, init_device, seeding=init_seeding)
         else:
             raise ValueError(f"Unknown init_method: {init_method}")
         if learnable:
@@ -349,7 +356,8 @@ class STInterpMLP(nn.Module):
                  spatial_init_method: str = 'uniform', spatial_basis_function: str = 'wendland',
                  train_coords: np.ndarray = None, gradient_damping: bool = False,
                  damping_threshold: float = 0.3, damping_strength: float = 1.0,
-                 output_dim: int = 1, use_delta_reparameterization: bool = False, spatial_init_device=None):
+                 output_dim: int = 1, use_delta_reparameterization: bool = False, spatial_init_device=None,
+                 spatial_init_seeding: str = 'host'):
         super().__init__()
         self.p = p
         self.k_spatial_centers = k_spatial_centers
@@ -362,7 +370,7 @@ class STInterpMLP(nn.Module):
             init_method=spatial_init_method, train_coords=train_coords,
             basis_function=spatial_basis_function, gradient_damping=gradient_damping,
             damping_threshold=damping_threshold, damping_strength=damping_strength,
-            init_device=spatial_init_device)
+            init_device=spatial_init_device, init_seeding=spatial_init_seeding)
         self.temporal_basis = TemporalBasisEmbedding(n_centers=k_temporal_centers)
         self.k_spatial = self.spatial_basis.k
         self.k_temporal = self.temporal_basis.k_time
@@ -709,4 +717,5 @@ def create_model(config: dict, train_coords: np.ndarray = None) -> STInterpMLP:
         damping_strength=config.get('damping_strength', 1.0),
         output_dim=output_dim,
         use_delta_reparameterization=config.get('use_delta_reparameterization', False),
-        spatial_init_device=config.get('spatial_init_device'))
+        spatial_init_device=config.get('spatial_init_device'),
+        spatial_init_seeding=config.get('spatial_init_seeding', 'host'))
