@@ -707,6 +707,58 @@ int stdadk_grid_score_f32(const float *y_pred, const float *z, const uint8_t *sp
                           size_t workspace_bytes, stdadk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Quantile diagnostics (added under ABI 10: new entry points only, so STDADK_ABI_VERSION stays 10): how good the
+ * QUANTILES of a multi-quantile model are on a site x time grid -- reliability of every level, the PIT histogram,
+ * how often and how deep the predicted quantiles cross (what the prediction-level penalty, losses.py
+ * non_crossing_penalty, and the delta head exist to prevent), CRPS (Eq. 4.6, uniform weights) per site and time --
+ * as a reduction on the device beside stdadk_grid_score_f32, with exactly its layout and conventions: one CHUNK of nT
+ * consecutive time slices per call,
+ *   y_pred [nT*S][Q]  predictions, time-major: row = ti*S + s; finite by contract
+ *   z      [nT][S]    the field's slice; a non-finite entry counts NOWHERE
+ *   split  [nT][S]    codes 0..3, NULL = all 0; an entry with another code counts nowhere
+ *   taus_host [Q]     the levels, a HOST array of float32 read during the call, NULL = 0.5 each
+ *   lo_col, hi_col    the interval's columns, lo_col < hi_col, or -1 / -1 for none
+ * All sums are float64 on the device.  Every predicate and term is formed in double from operands converted to double,
+ * every operation rounded once.  For a counted entry with predictions p_0 .. p_Q-1 and value z:
+ *   split_acc [4][STDADK_QD_SLOTS]  += per split:
+ *     N               the count of entries
+ *     BELOW + q       q < Q: the count of z <= p_q -- the reliability of level q (calibrated: BELOW_q / N ~ tau_q)
+ *     PIT + j         j <= Q: the count of entries with #{q : p_q < z} == j -- the histogram over the row's own
+ *                     quantile ladder, defined whatever the order of the p_q
+ *     CROSS_ROWS      the count of entries with at least one adjacent pair p_q > p_q+1 (strict: equal neighbours do
+ *                     not cross)
+ *     PAIR + q        q < Q - 1: the count of entries where that adjacent pair crosses
+ *     DEPTH1, DEPTH2  the sum over entries and adjacent pairs of max(0, p_q - p_q+1) and of its square; divided by N
+ *                     the reference's non_crossing_penalty(y_pred, "mean", power = 1 or 2)
+ *     CRPS            the sum over entries of (2 / Q) * (rho_0 + rho_1 + ... + rho_Q-1), added left to right,
+ *                     rho_q = max((tau_q - 1) e, tau_q e), e = z - p_q
+ *     INSIDE          with an interval, the count of p_lo <= z <= p_hi
+ *     (Q == 1: no pairs, the crossing slots stay 0 and PIT has two bins; slots past the used ones are not touched)
+ *   site_acc  [4][S][4]   (n, crps, cross_rows, inside) += per split and site, or NULL: a site's slices are added one
+ *                     by one in time order, starting from the value already there, so chunked calls give the bits of
+ *                     one call (the three counts are integers and are added as such)
+ *   time_acc  [4][nT][4]  (n, crps, cross_rows, inside) =  per split and time slice of THIS chunk (assigned), or NULL
+ * Deterministic (no atomics, fixed orders).  Workspace: stdadk_quantile_diag_workspace_bytes(S, nT) (0 = bad sizes),
+ * 8-byte aligned.  1 <= Q <= STDADK_MAX_Q, S*nT < 2^31.  Errors as stdadk_grid_score_f32: STDADK_E_ARG, _SHAPE,
+ * _WORKSPACE, _ALIGN.  No host read of device memory, no allocation, capturable.
+ * ------------------------------------------------------------------------------------------ */
+#define STDADK_QD_N 0
+#define STDADK_QD_BELOW 1
+#define STDADK_QD_PIT 9
+#define STDADK_QD_CROSS_ROWS 18
+#define STDADK_QD_PAIR 19
+#define STDADK_QD_DEPTH1 26
+#define STDADK_QD_DEPTH2 27
+#define STDADK_QD_CRPS 28
+#define STDADK_QD_INSIDE 29
+#define STDADK_QD_SLOTS 32
+size_t stdadk_quantile_diag_workspace_bytes(int64_t S, int64_t nT);
+int stdadk_quantile_diag_f32(const float *y_pred, const float *z, const uint8_t *split, int64_t S, int64_t nT,
+                             int32_t Q, const float *taus_host, int32_t lo_col, int32_t hi_col,
+                             double *split_acc, double *site_acc, double *time_acc,
+                             void *workspace, size_t workspace_bytes, stdadk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Knot initialiser (added under ABI 10: new entry points only, nothing existing changes, so STDADK_ABI_VERSION stays
  * 10): ONE EM iteration of the spherical Gaussian mixture in two dimensions behind `spatial_init_method: gmm`
  * (stnf/models/st_interp.py:187-266 fits sklearn.mixture.GaussianMixture(covariance_type='spherical') on the host),

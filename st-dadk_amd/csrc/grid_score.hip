@@ -15,12 +15,11 @@
 //   grid_score_split_kernel  n, sse, sae of every split = the chunk's time_acc summed over its slices, added into split_acc.
 // Every element term is formed in double from operands converted to double; no atomics anywhere: the same call on the
 // same data gives the same bits.  The kernel reads 4Q + 5 bytes per grid entry and is bound by that.
+#include "grid_reduce.h"
 #include "loss.h"
 
 namespace stdadk {
 
-constexpr int GS_T = 256;                   // sites per workgroup
-constexpr int GS_W = GS_T / kWave;          // waves per workgroup
 constexpr int GS_TT = 16;                   // slices per LDS tile
 constexpr int GS_TV = 12;                   // values per slice: 4 splits x (sse, sae, n)
 constexpr int GS_X = STDADK_MAX_Q + 2;      // chunk-long values per split: check[q], cover, width
@@ -35,27 +34,6 @@ struct GridScoreArgs {
   float tau[STDADK_MAX_Q];
   double *site_acc, *tpart, *xpart;
 };
-
-// wave_sum (common.h) on a double: the same DPP tree on both halves of the value
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ double dpp_f64(double v) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  const uint32_t l = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, ROW_MASK, 0xF, false);
-  const uint32_t h = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, ROW_MASK, 0xF, false);
-  return __builtin_bit_cast(double, ((uint64_t)h << 32) | l);
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  v += dpp_f64<0xB1>(v);
-  v += dpp_f64<0x4E>(v);
-  v += dpp_f64<0x141>(v);
-  v += dpp_f64<0x140>(v);
-  v += dpp_f64<0x142, 0xA>(v);
-  v += dpp_f64<0x143, 0xC>(v);
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, 63);
-  const uint32_t h = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), 63);
-  return __builtin_bit_cast(double, ((uint64_t)h << 32) | l);
-}
 
 template <int Q>
 __global__ __launch_bounds__(GS_T) void grid_score_kernel(GridScoreArgs a) {
@@ -161,24 +139,6 @@ __global__ __launch_bounds__(GS_T) void grid_score_kernel(GridScoreArgs a) {
         (xr[tid] + xr[GS_XV + tid]) + (xr[2 * GS_XV + tid] + xr[3 * GS_XV + tid]);
 }
 
-// NV values per partial row, G = GS_T / NV groups of threads stride over the rows, then one thread per value adds the
-// groups' sums in order.  row(i) = the i-th partial row of this reduction.
-template <int NV, typename RowFn>
-__device__ __forceinline__ double sum_partials(double *red, int nrows, RowFn row) {
-  constexpr int G = GS_T / NV;
-  const int tid = threadIdx.x, k = tid % NV, g = tid / NV;
-  if (g < G) {
-    double s = 0.0;
-    for (int i = g; i < nrows; i += G) s += row(i)[k];
-    red[g * NV + k] = s;
-  }
-  __syncthreads();
-  double s = 0.0;
-  if (tid < NV)
-    for (int j = 0; j < G; ++j) s += red[j * NV + tid];
-  return s;
-}
-
 __global__ __launch_bounds__(GS_T) void grid_score_time_kernel(const double *__restrict__ tpart,
                                                               const double *__restrict__ xpart, int nblk, int nT, int Q,
                                                               int interval, double *__restrict__ time_acc,
@@ -210,8 +170,6 @@ __global__ __launch_bounds__(kWave) void grid_score_split_kernel(const double *_
   for (int ti = 0; ti < nT; ++ti) s += time_acc[((size_t)c * nT + ti) * 3 + v];
   split_acc[(size_t)c * STDADK_GRID_SLOTS + (v == 0 ? STDADK_GRID_SSE : (v == 1 ? STDADK_GRID_SAE : STDADK_GRID_N))] += s;
 }
-
-static inline int64_t grid_score_blocks(int64_t S) { return ceil_div(S > 0 ? S : 1, GS_T); }
 
 }  // namespace stdadk
 

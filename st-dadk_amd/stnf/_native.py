@@ -213,6 +213,10 @@ _SIGNATURES = {
     "stdadk_grid_score_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                         C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
+    "stdadk_quantile_diag_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "stdadk_quantile_diag_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                           C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "stdadk_gmm_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "stdadk_gmm_em_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -787,6 +791,50 @@ def grid_score(y_pred, z, split, metric_col, taus, lo_col, hi_col, split_acc, si
         int(hi_col), _f64_acc(split_acc, "split_acc", (4, GRID_SLOTS)), _f64_acc(site_acc, "site_acc", (4, S, 3)),
         _f64_acc(time_acc, "time_acc", (4, nT, 3)), workspace.data_ptr(), workspace.numel() * 8, _stream())
     _check(rc, "stdadk_grid_score_f32")
+
+
+# slots per split of the float64 accumulator stdadk_quantile_diag_f32 adds into (include/stdadk.h)
+QD_N, QD_BELOW, QD_PIT, QD_CROSS_ROWS, QD_PAIR, QD_DEPTH1, QD_DEPTH2, QD_CRPS, QD_INSIDE, QD_SLOTS = \
+    0, 1, 9, 18, 19, 26, 27, 28, 29, 32
+
+
+def quantile_diag_workspace_bytes(S, nT):
+    n = lib().stdadk_quantile_diag_workspace_bytes(S, nT)
+    if n == 0:
+        raise RuntimeError(f"stdadk_quantile_diag_workspace_bytes: bad grid {S} x {nT} (S*nT must stay below 2^31)")
+    return n
+
+
+def quantile_diag(y_pred, z, split, taus, lo_col, hi_col, split_acc, site_acc, time_acc, workspace):
+    """stdadk_quantile_diag_f32 on one chunk of time slices, laid out as grid_score's: y_pred (nT*S, Q) time-major,
+    z (nT, S) float32 with NaN = no value, split (nT, S) uint8 codes 0..3 or None; the quantile diagnostics are ADDED
+    into split_acc (4, QD_SLOTS) and site_acc (4, S, 4) and ASSIGNED to time_acc (4, nT, 4), all float64 on the
+    device; site_acc and time_acc may each be None (skipped).  taus: Q levels or None (0.5 each); lo_col / hi_col: the
+    interval's columns or -1 / -1."""
+    if z.dim() != 2 or y_pred.dim() != 2:
+        raise RuntimeError("quantile_diag: z must be (nT, S) and y_pred (nT*S, Q)")
+    nT, S = z.shape
+    Q = y_pred.shape[1]
+    if y_pred.shape[0] != nT * S:
+        raise RuntimeError(f"quantile_diag: y_pred has {y_pred.shape[0]} rows, z is {nT} x {S}")
+    for name, x in (("y_pred", y_pred), ("z", z)):
+        if x.dtype != torch.float32:
+            raise RuntimeError(f"quantile_diag: {name} must be float32, got {x.dtype}")
+    if split is not None and (split.dtype != torch.uint8 or tuple(split.shape) != (nT, S)):
+        raise RuntimeError(f"quantile_diag: split must be uint8 of shape {(nT, S)}, got {split.dtype} "
+                           f"{tuple(split.shape)}")
+    if taus is not None and len(taus) != Q:
+        raise RuntimeError(f"quantile_diag: {Q} quantile levels expected, got {len(taus)}")
+    if workspace.dtype != torch.float64 or not _on_device(workspace) or not workspace.is_contiguous():
+        raise RuntimeError("quantile_diag: workspace must be a contiguous float64 tensor on the device")
+    arr = (C.c_float * Q)(*[float(q) for q in taus]) if taus is not None else None
+    rc = lib().stdadk_quantile_diag_f32(
+        _dev(y_pred, "y_pred"), _dev(z, "z"), _dev(split, "split"), S, nT, Q, arr, int(lo_col), int(hi_col),
+        _f64_acc(split_acc, "split_acc", (4, QD_SLOTS)),
+        None if site_acc is None else _f64_acc(site_acc, "site_acc", (4, S, 4)),
+        None if time_acc is None else _f64_acc(time_acc, "time_acc", (4, nT, 4)),
+        workspace.data_ptr(), workspace.numel() * 8, _stream())
+    _check(rc, "stdadk_quantile_diag_f32")
 
 
 def gmm_workspace_bytes(n, k):

@@ -1319,16 +1319,8 @@ class Predictor:
             pass
         return out.view(T, S, Q)
 
-    @torch.no_grad()
-    def score_grid(self, coords, t_values, z, split=None, quantile_levels=None, interval=None, max_rows=None):
-        """predict_grid scored against the field on the device, without the grid: coords (S,2), t_values (T,),
-        z (T,S) float32 with NaN where the field has no value, split (T,S) uint8 codes 0..3 or None (all 0).  The
-        predictions of every chunk of time slices (at most `max_rows` rows, default as predict_grid) go into one
-        reused buffer and are reduced at once by stdadk_grid_score_f32; the (T*S, Q) tensor is never allocated.
-        Returns (split_acc (4, GRID_SLOTS), site_acc (4, S, 3), time_acc (4, T, 3)): float64 sums on the device, slots
-        as in include/stdadk.h, of the metric column Q // 2.  `quantile_levels` (Q levels) weigh the check-loss
-        slots (default 0.5 each); `interval=(lo_level, hi_level)` picks the cover / width columns from them.
-        The three tensors and the scratch belong to the predictor and are overwritten by its next score_grid call."""
+    def _grid_args(self, who, coords, t_values, z, split, quantile_levels, interval):
+        """The checked arguments of the scoring passes: (coords, t_values, z, levels, lo, hi)."""
         if self.model.p != 0:
             raise RuntimeError("Predictor: covariates (p>0) are not wired into the dense-grid path")
         self._refresh()
@@ -1337,33 +1329,78 @@ class Predictor:
         t_values = t_values.contiguous().float().view(-1)
         Q = self.model.output_dim
         if tuple(z.shape) != (T, S) or (split is not None and tuple(split.shape) != (T, S)):
-            raise RuntimeError(f"score_grid: z and split must be (T, S) = {(T, S)}")
+            raise RuntimeError(f"{who}: z and split must be (T, S) = {(T, S)}")
         z = z.contiguous().float()
         levels = [float(q) for q in quantile_levels] if quantile_levels is not None else None
         if levels is not None and len(levels) != Q:
-            raise ValueError(f"score_grid: output_dim={Q} quantile levels expected, got {len(levels)}")
+            raise ValueError(f"{who}: output_dim={Q} quantile levels expected, got {len(levels)}")
         lo = hi = -1
         if interval is not None:
             if levels is None or any(float(v) not in levels for v in interval):
-                raise ValueError(f"score_grid: interval {interval} must name two of quantile_levels {levels}")
+                raise ValueError(f"{who}: interval {interval} must name two of quantile_levels {levels}")
             lo, hi = levels.index(float(interval[0])), levels.index(float(interval[1]))
-        split_acc = self._reused("split_acc", (4, N.GRID_SLOTS), torch.float64).zero_()
-        site_acc = self._reused("site_acc", (4, S, 3), torch.float64).zero_()
-        time_acc = self._reused("time_acc", (4, T, 3), torch.float64).zero_()
+        return coords, t_values, z, levels, lo, hi
+
+    def _score_chunks(self, coords, t_values, z, split, levels, lo, hi, max_rows, scores, quantile):
+        """One pass over the grid's chunks of time slices -- ONE forward per chunk into a reused buffer -- reduced by
+        stdadk_grid_score_f32 (`scores`) and / or stdadk_quantile_diag_f32 (`quantile`) on that buffer.  Returns the
+        accumulators of the reductions asked for, (split_acc, site_acc, time_acc) each, in that order."""
+        S, T = coords.shape[0], t_values.numel()
+        Q = self.model.output_dim
+        # (name prefix, slots per split, values per site / time, workspace bytes, the chunk's reduction)
+        kinds = []
+        if scores:
+            kinds.append(("", N.GRID_SLOTS, 3, N.grid_score_workspace_bytes,
+                          lambda y, zc, sc, accs, ws: N.grid_score(y, zc, sc, Q // 2, levels, lo, hi, *accs, ws)))
+        if quantile:
+            kinds.append(("q_", N.QD_SLOTS, 4, N.quantile_diag_workspace_bytes,
+                          lambda y, zc, sc, accs, ws: N.quantile_diag(y, zc, sc, levels, lo, hi, *accs, ws)))
+        out = [(self._reused(k + "split_acc", (4, slots), torch.float64).zero_(),
+                self._reused(k + "site_acc", (4, S, v), torch.float64).zero_(),
+                self._reused(k + "time_acc", (4, T, v), torch.float64).zero_()) for k, slots, v, _, _ in kinds]
         if S == 0 or T == 0:
-            return split_acc, site_acc, time_acc
+            return out
         per = min(self._slices_per_call(S, max_rows), T)
         buf = self._reused("y", (per * S, Q))
-        ws = self._reused("grid_ws", (N.grid_score_workspace_bytes(S, per) // 8,), torch.float64)
+        wss = [self._reused(k + "grid_ws", (nbytes(S, per) // 8,), torch.float64) for k, _, _, nbytes, _ in kinds]
         for t0, n, y in self._grid_chunks(coords, t_values, max_rows, lambda t0, n: buf[:n * S], self._reused):
-            # the kernel ASSIGNS its chunk's time sums: straight into time_acc when one chunk is the grid
-            tacc = time_acc if per == T else self._reused("time_part" if n == per else "time_tail", (4, n, 3),
-                                                          torch.float64)
-            N.grid_score(y, z[t0:t0 + n], None if split is None else split[t0:t0 + n], Q // 2, levels, lo, hi,
-                         split_acc, site_acc, tacc, ws)
-            if per < T:
-                time_acc[:, t0:t0 + n] = tacc
-        return split_acc, site_acc, time_acc
+            for (k, _, v, _, reduce), (split_acc, site_acc, time_acc), ws in zip(kinds, out, wss):
+                # the kernel ASSIGNS its chunk's time sums: straight into time_acc when one chunk is the grid
+                tacc = time_acc if per == T else self._reused(k + ("time_part" if n == per else "time_tail"),
+                                                              (4, n, v), torch.float64)
+                reduce(y, z[t0:t0 + n], None if split is None else split[t0:t0 + n], (split_acc, site_acc, tacc), ws)
+                if per < T:
+                    time_acc[:, t0:t0 + n] = tacc
+        return out
+
+    @torch.no_grad()
+    def score_grid(self, coords, t_values, z, split=None, quantile_levels=None, interval=None, max_rows=None,
+                   quantile=False):
+        """predict_grid scored against the field on the device, without the grid: coords (S,2), t_values (T,),
+        z (T,S) float32 with NaN where the field has no value, split (T,S) uint8 codes 0..3 or None (all 0).  The
+        predictions of every chunk of time slices (at most `max_rows` rows, default as predict_grid) go into one
+        reused buffer and are reduced at once by stdadk_grid_score_f32; the (T*S, Q) tensor is never allocated.
+        Returns (split_acc (4, GRID_SLOTS), site_acc (4, S, 3), time_acc (4, T, 3)): float64 sums on the device, slots
+        as in include/stdadk.h, of the metric column Q // 2.  `quantile_levels` (Q levels) weigh the check-loss
+        slots (default 0.5 each); `interval=(lo_level, hi_level)` picks the cover / width columns from them.
+        `quantile=True`: stdadk_quantile_diag_f32 reduces the same chunk buffer too (still one forward per chunk) and
+        the three tensors of quantile_grid follow the usual three.
+        The tensors and the scratch belong to the predictor and are overwritten by its next scoring call."""
+        coords, t_values, z, levels, lo, hi = self._grid_args("score_grid", coords, t_values, z, split,
+                                                              quantile_levels, interval)
+        out = self._score_chunks(coords, t_values, z, split, levels, lo, hi, max_rows, True, bool(quantile))
+        return out[0] + out[1] if quantile else out[0]
+
+    @torch.no_grad()
+    def quantile_grid(self, coords, t_values, z, split=None, quantile_levels=None, interval=None, max_rows=None):
+        """The quantile diagnostics of predict_grid against the field, on the device and without the grid (arguments as
+        score_grid): reliability, PIT histogram, crossings and their depth, CRPS, interval membership.  Returns
+        (split_acc (4, QD_SLOTS), site_acc (4, S, 4), time_acc (4, T, 4)): float64 sums on the device, slots as in
+        include/stdadk.h (stdadk_quantile_diag_f32); site and time values are (n, crps, cross_rows, inside).
+        The tensors and the scratch belong to the predictor and are overwritten by its next scoring call."""
+        coords, t_values, z, levels, lo, hi = self._grid_args("quantile_grid", coords, t_values, z, split,
+                                                              quantile_levels, interval)
+        return self._score_chunks(coords, t_values, z, split, levels, lo, hi, max_rows, False, True)[0]
 
     @torch.no_grad()
     def predict(self, coords, t, out=None):

@@ -22,7 +22,12 @@ class Evaluator:
     `check_loss`, `crps` (multi-quantile), plus `loss`: the mean over batches of the batch objective, the
     reference's `val_loss` (with the delta head and `non_crossing_lambda > 0` the parameter-level P_nc(delta) is part
     of every batch's objective, as scripts/train_st_interp.py:770-777 has it).  `batch_size` is one size (last batch
-    ragged) or a list of sizes summing to len(dataset), the data-parallel schedule of `DeviceDataset.epoch_batches`."""
+    ragged) or a list of sizes summing to len(dataset), the data-parallel schedule of `DeviceDataset.epoch_batches`.
+    `diagnostics=True` (pinball objectives; ignored without quantile levels): the batches keep their predictions in one
+    (N, Q) buffer in dataset order (`self.predictions` afterwards), one stdadk_quantile_diag_f32 call reduces it against
+    the targets into a second accumulator -- all-reduced and read in the same host sync as the first -- and the dict
+    gains `quantile`: levels, reliability, pit, cross_rate, pair_cross_rate, nc_penalty_p1, nc_penalty_p2, crps, rows
+    (stnf.utils.predictions.quantile_diagnostics; `self.quantile_sums` holds the sums)."""
 
     def __init__(self, model, loss="mse", quantile_levels=None, non_crossing_weight=0.0, non_crossing_power=1,
                  non_crossing_lambda=0.0, max_batch=65536, force_dense=False, process_group=None):
@@ -37,6 +42,8 @@ class Evaluator:
             raise RuntimeError("Evaluator needs the model on a HIP device; there is no CPU path")
         self.acc = torch.zeros(N.EVAL_SLOTS, dtype=torch.float64, device=self.dev)
         self.sums = None               # the accumulator of the last call as host floats
+        self.quantile_sums = None      # diagnostics=True: the QD_SLOTS sums of the last call as host floats
+        self.predictions = None        # diagnostics=True: the (N, Q) predictions of the last call, dataset order
         self._desc = None
         self._ws = {}
         self._ema = None               # (key, parameter table over engine.ema, bf16 refresh table or None)
@@ -82,7 +89,7 @@ class Evaluator:
 
     # ------------------------------------------------------------------------------------
     @torch.no_grad()
-    def evaluate(self, dataset, batch_size, params="live", engine=None):
+    def evaluate(self, dataset, batch_size, params="live", engine=None, diagnostics=False):
         if params not in ("live", "ema"):
             raise ValueError(f"params='{params}'; use 'live' or 'ema'")
         m = self.model
@@ -98,12 +105,13 @@ class Evaluator:
         try:
             # (a list of sizes summing to len(dataset): the data-parallel schedule, DeviceDataset.epoch_batches)
             sizes = [int(b) for b in batch_size] if isinstance(batch_size, (list, tuple)) else int(batch_size)
-            return self._evaluate(dataset, sizes, engine, ema_views=(params == "ema" and not swapped))
+            return self._evaluate(dataset, sizes, engine, ema_views=(params == "ema" and not swapped),
+                                  diagnostics=bool(diagnostics) and self.objective.kind == "pinball")
         finally:
             if swapped:
                 engine.swap_in_ema()
 
-    def _evaluate(self, dataset, batch_size, engine, ema_views):
+    def _evaluate(self, dataset, batch_size, engine, ema_views, diagnostics=False):
         m = self.model
         if self._desc is None:
             self._desc = m._native_desc(False)
@@ -133,19 +141,51 @@ class Evaluator:
         ws = self._workspace(basis, desc, max((b.numel() for b in batches), default=1), flags)
         acc = self.acc
         acc.zero_()
+        n_rows = len(dataset)
+        preds = self._buffer("preds", (n_rows, Q), torch.float32) if diagnostics else None
+        row = 0
         for idx in batches:
             B = idx.numel()
             N.eval_indexed(basis, desc, ptab, dataset.coords, t_all, X_all, y_all,
                            N._contig(idx), ldesc, metric_col, 1.0 / (B * Q), acc,
-                           None, ws, flags)
+                           None if preds is None else preds[row:row + B], ws, flags)
+            row += B
         if self.objective.nc_lambda > 0.0 and len(batches):
             # parameter-level penalty of the delta head: the same value in every batch's objective
             p_nc = losses.compute_p_nc_delta_penalty(list(m.delta_params))
             acc[N.EVAL_OBJECTIVE] += (self.objective.nc_lambda * len(batches)) * p_nc.double()
+        accs = [acc]
+        if diagnostics:
+            # the set as a 1 x N "grid" without splits: no site or time sums (the batches are consecutive slices of
+            # the set, so the buffer is in dataset order and the targets are read where they are)
+            qacc = self._buffer("qacc", (4, N.QD_SLOTS), torch.float64).zero_()
+            if n_rows:
+                target = y_all if y_all.shape[1] == 1 else y_all[:, metric_col].contiguous()
+                qws = self._buffer("qws", (N.quantile_diag_workspace_bytes(n_rows, 1) // 8,), torch.float64)
+                N.quantile_diag(preds, target.view(1, n_rows), None, self.objective.quantile_levels, -1, -1, qacc,
+                                None, None, qws)
+            accs.append(qacc[0])
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.pg) > 1:
-            dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=self.pg)
-        self.sums = acc.tolist()                                   # the call's ONE host sync
-        return self.metrics(self.sums)
+            for a in accs:
+                dist.all_reduce(a, op=dist.ReduceOp.SUM, group=self.pg)
+        host = (torch.cat(accs) if diagnostics else acc).tolist()  # the call's ONE host sync
+        self.sums = host[:N.EVAL_SLOTS]
+        out = self.metrics(self.sums)
+        if diagnostics:
+            import numpy as np
+            from .utils.predictions import quantile_diagnostics
+            self.quantile_sums, self.predictions = host[N.EVAL_SLOTS:], preds
+            sums = np.zeros((4, N.QD_SLOTS))
+            sums[0] = self.quantile_sums
+            out["quantile"] = quantile_diagnostics(sums, None, None, self.objective.quantile_levels, False)["all"]
+        return out
+
+    def _buffer(self, name, shape, dtype):
+        """Scratch of the diagnostics, kept between calls."""
+        buf = self._ws.get(name)
+        if buf is None or tuple(buf.shape) != tuple(shape) or buf.dtype != dtype:
+            buf = self._ws[name] = torch.empty(shape, device=self.dev, dtype=dtype)
+        return buf
 
     def metrics(self, sums):
         """The reference's metric dict from the accumulator's sums."""

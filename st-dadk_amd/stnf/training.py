@@ -63,10 +63,12 @@ def val_batch_size(batch_size, n):
 
 def evaluate_model(model, data, config=None):
     """The reference's metric dict (`mse, mae, rmse` [+ `check_loss`, `mean_check_loss`, `crps`]) of the model's
-    current parameters on a `DeviceDataset`, plus `loss` (mean batch objective); one host sync."""
+    current parameters on a `DeviceDataset`, plus `loss` (mean batch objective); one host sync.  With
+    `quantile_diagnostics: true` in the config a quantile model's dict gains `quantile` (Evaluator.evaluate)."""
     config = config or {}
     bs = int(config.get("val_batch_size", 0)) or val_batch_size(config.get("batch_size", 256), len(data))
-    out = make_evaluator(model, config, max_batch=bs).evaluate(data, bs)
+    out = make_evaluator(model, config, max_batch=bs).evaluate(
+        data, bs, diagnostics=config.get("quantile_diagnostics", False))
     out.pop("rows", None)
     return out
 

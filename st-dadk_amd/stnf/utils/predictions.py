@@ -16,6 +16,9 @@ NPZ_KEYS = ("predictions", "true", "coords", "train_mask", "valid_mask", "test_m
 SPLIT_NAMES = ("other", "train", "valid", "test")          # split codes 0..3 of grid_scores
 # slots per split of the sums behind grid_scores (the STDADK_GRID_* slots of include/stdadk.h)
 _G_N, _G_SSE, _G_SAE, _G_COVER, _G_WIDTH, _G_CHECK, _G_SLOTS = 0, 1, 2, 3, 4, 5, 16
+# slots per split of the sums behind the `quantile` entry of grid_scores (the STDADK_QD_* slots of include/stdadk.h)
+_Q_N, _Q_BELOW, _Q_PIT, _Q_CROSS, _Q_PAIR, _Q_DEPTH1, _Q_DEPTH2, _Q_CRPS, _Q_INSIDE, _Q_SLOTS = \
+    0, 1, 9, 18, 19, 26, 27, 28, 29, 32
 
 
 @torch.no_grad()
@@ -135,6 +138,72 @@ def _grid_sums_host(pred, z, code, levels, lo, hi):
     return split_acc, site_acc, time_acc
 
 
+def _quantile_sums_host(pred, z, code, levels, lo, hi):
+    """The sums of stdadk_quantile_diag_f32 in numpy float64: pred (T, S, Q), z (T, S) with NaN = no value, code (T, S).
+    Returns split_acc (4, slots), site_acc (4, S, 4), time_acc (4, T, 4); site and time hold (n, crps, cross_rows,
+    inside)."""
+    T, S, Q = pred.shape
+    pred = pred.astype(np.float64)
+    z = z.astype(np.float64)
+    fin = np.isfinite(z)
+    zz = np.where(fin, z, 0.0)[:, :, None]
+    tau = np.asarray([0.5] * Q if levels is None else levels, dtype=np.float64)
+    e = zz - pred
+    crps = (2.0 / Q) * np.maximum((tau - 1.0) * e, tau * e).sum(axis=2)
+    below = zz <= pred
+    rank = (pred < zz).sum(axis=2)
+    pair = pred[:, :, :-1] > pred[:, :, 1:]
+    depth = np.maximum(pred[:, :, :-1] - pred[:, :, 1:], 0.0)
+    cross = pair.any(axis=2)
+    inside = (pred[:, :, lo] <= zz[:, :, 0]) & (zz[:, :, 0] <= pred[:, :, hi]) if lo >= 0 else np.zeros((T, S), bool)
+    split_acc, site_acc, time_acc = np.zeros((4, _Q_SLOTS)), np.zeros((4, S, 4)), np.zeros((4, T, 4))
+    for c in range(4):
+        m = fin & (code == c)
+        terms = np.stack([m.astype(np.float64), np.where(m, crps, 0.0), (m & cross).astype(np.float64),
+                          (m & inside).astype(np.float64)], axis=2)
+        site_acc[c], time_acc[c] = terms.sum(axis=0), terms.sum(axis=1)
+        split_acc[c, [_Q_N, _Q_CRPS, _Q_CROSS, _Q_INSIDE]] = terms.sum(axis=(0, 1))
+        split_acc[c, _Q_BELOW:_Q_BELOW + Q] = (below & m[:, :, None]).sum(axis=(0, 1))
+        split_acc[c, _Q_PIT:_Q_PIT + Q + 1] = np.bincount(rank[m], minlength=Q + 1)
+        split_acc[c, _Q_PAIR:_Q_PAIR + Q - 1] = (pair & m[:, :, None]).sum(axis=(0, 1))
+        split_acc[c, _Q_DEPTH1] = np.where(m[:, :, None], depth, 0.0).sum()
+        split_acc[c, _Q_DEPTH2] = np.where(m[:, :, None], depth * depth, 0.0).sum()
+    return split_acc, site_acc, time_acc
+
+
+def _quantile_split_metrics(sums, levels, interval):
+    Q = len(levels)
+    n = sums[_Q_N]
+    out = {"levels": np.asarray(levels, dtype=np.float64),
+           "reliability": _ratio(sums[_Q_BELOW:_Q_BELOW + Q], n), "pit": _ratio(sums[_Q_PIT:_Q_PIT + Q + 1], n),
+           "cross_rate": float(_ratio(sums[_Q_CROSS], n)), "pair_cross_rate": _ratio(sums[_Q_PAIR:_Q_PAIR + Q - 1], n),
+           "nc_penalty_p1": float(_ratio(sums[_Q_DEPTH1], n)), "nc_penalty_p2": float(_ratio(sums[_Q_DEPTH2], n)),
+           "crps": float(_ratio(sums[_Q_CRPS], n)), "rows": int(n)}
+    if interval:
+        out["coverage"] = float(_ratio(sums[_Q_INSIDE], n))
+    return out
+
+
+def quantile_diagnostics(split_acc, site_acc, time_acc, levels, interval):
+    """The `quantile` entry of grid_scores from the sums of stdadk_quantile_diag_f32 (host arrays): per split (all,
+    train, valid, test, other) levels, reliability (Q,), pit (Q+1,), cross_rate, pair_cross_rate (Q-1,), nc_penalty_p1,
+    nc_penalty_p2, crps, rows and, with an interval, coverage; and, when the site and time sums are given, the maps
+    over all finite entries site_crps, site_cross_rate, site_coverage, site_count (S,), time_* (T,),
+    site_crps_by_split, time_crps_by_split (4, .).  NaN / 0 where a split, site or time has no finite entry."""
+    out = {"all": _quantile_split_metrics(split_acc.sum(axis=0), levels, interval)}
+    for k in (1, 2, 3, 0):
+        out[SPLIT_NAMES[k]] = _quantile_split_metrics(split_acc[k], levels, interval)
+    for name, acc in (("site", site_acc), ("time", time_acc)):
+        if acc is None:
+            continue
+        tot = acc.sum(axis=0)
+        out[f"{name}_crps"], out[f"{name}_cross_rate"] = _ratio(tot[:, 1], tot[:, 0]), _ratio(tot[:, 2], tot[:, 0])
+        out[f"{name}_coverage"] = _ratio(tot[:, 3], tot[:, 0]) if interval else np.full(tot.shape[0], np.nan)
+        out[f"{name}_count"] = tot[:, 0].astype(np.int64)
+        out[f"{name}_crps_by_split"] = _ratio(acc[:, :, 1], acc[:, :, 0])
+    return out
+
+
 def _ratio(num, den):
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.where(den > 0, num / np.where(den > 0, den, 1.0), np.nan)
@@ -176,7 +245,11 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
                         coverage, mean_width; NaN where a split has no finite entry
       site_mse, site_mae, site_count   (S,) over all finite entries (the reference's nanmean), NaN / 0 for an empty site
       time_mse, time_mae, time_count   (T,)
-      site_mse_by_split, time_mse_by_split   (4, .), rows in the order of the codes: other, train, valid, test"""
+      site_mse_by_split, time_mse_by_split   (4, .), rows in the order of the codes: other, train, valid, test
+    With `quantile_diagnostics: true` in the config and a model that has quantile levels, the dict gains `quantile`
+    (see quantile_diagnostics): reliability, PIT histogram, crossing rates and depths, CRPS per split, and the per-site
+    and per-time CRPS / crossing / coverage maps.  On the device that is one more reduction of the same chunk buffer
+    (one forward per chunk) and still one host read; without the key nothing changes."""
     if getattr(model, "p", 0) != 0:
         raise ValueError("grid_scores: the dense grid has no covariates (p must be 0)")
     z = np.asarray(z_full.detach().cpu() if torch.is_tensor(z_full) else z_full)
@@ -202,6 +275,8 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
         raise ValueError(f"grid_scores: the model has {Q} outputs, config names {len(levels)} quantile levels")
     if kind == "quantile" and levels is None:
         kind = "mean"
+    # quantile diagnostics: asked for by the config and only of a model that has quantile levels
+    diag = bool(config.get("quantile_diagnostics", False)) and levels is not None
     interval = config.get("interval")
     lo = hi = -1
     if interval is not None:
@@ -222,14 +297,17 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
             from ..engine import Predictor
             accs = Predictor(model).score_grid(c, tv.to(dev), torch.from_numpy(z.astype(np.float32)).to(dev),
                                                torch.from_numpy(code).to(dev), quantile_levels=levels,
-                                               interval=interval, max_rows=max_rows)
+                                               interval=interval, max_rows=max_rows, quantile=diag)
             flat = torch.cat([a.reshape(-1) for a in accs]).cpu().numpy()              # the ONE host read
-            split_acc = flat[:4 * _G_SLOTS].reshape(4, _G_SLOTS)
-            site_acc = flat[4 * _G_SLOTS:4 * _G_SLOTS + 12 * S].reshape(4, S, 3)
-            time_acc = flat[4 * _G_SLOTS + 12 * S:].reshape(4, T, 3)
+            cuts = np.cumsum([a.numel() for a in accs])[:-1]
+            sums = [part.reshape(a.shape) for part, a in zip(np.split(flat, cuts), accs)]
         else:
             pred = torch.stack([model(torch.zeros(S, 0), c, torch.full((S, 1), float(tv[i]))) for i in range(T)])
-            split_acc, site_acc, time_acc = _grid_sums_host(pred.double().numpy(), z, code, levels, lo, hi)
+            pred = pred.double().numpy()
+            sums = list(_grid_sums_host(pred, z, code, levels, lo, hi))
+            if diag:
+                sums += _quantile_sums_host(pred, z, code, levels, lo, hi)
+        split_acc, site_acc, time_acc = sums[:3]
     finally:
         model.train(was_training)
     out = {"splits": {"all": _split_metrics(split_acc.sum(axis=0), kind, Q, interval is not None)}}
@@ -240,16 +318,26 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
         out[f"{name}_mse"], out[f"{name}_mae"] = _ratio(tot[:, 0], tot[:, 2]), _ratio(tot[:, 1], tot[:, 2])
         out[f"{name}_count"] = tot[:, 2].astype(np.int64)
         out[f"{name}_mse_by_split"] = _ratio(acc[:, :, 0], acc[:, :, 2])
+    if diag:
+        out["quantile"] = quantile_diagnostics(*sums[3:], levels, interval is not None)
     return out
 
 
 def save_grid_scores_npz(output_dir, scores):
     """Writes `<output_dir>/grid_scores.npz` from the dict of grid_scores and returns its path: the per-site and
-    per-time arrays under their own names, every split metric as the 0-d array `splits/<split>/<metric>`."""
-    arrs = {k: np.asarray(v) for k, v in scores.items() if k != "splits"}
+    per-time arrays under their own names, every split metric as the 0-d array `splits/<split>/<metric>`, and the
+    quantile diagnostics, when present, as `quantile/<split>/<metric>` and `quantile/<map>`."""
+    arrs = {k: np.asarray(v) for k, v in scores.items() if k not in ("splits", "quantile")}
     for name, metrics in scores["splits"].items():
         for k, v in metrics.items():
             arrs[f"splits/{name}/{k}"] = np.asarray(v)
+    # the quantile diagnostics, when they were asked for: `quantile/<split>/<metric>` and `quantile/<map>`
+    for name, v in scores.get("quantile", {}).items():
+        if isinstance(v, dict):
+            for k, w in v.items():
+                arrs[f"quantile/{name}/{k}"] = np.asarray(w)
+        else:
+            arrs[f"quantile/{name}"] = np.asarray(v)
     os.makedirs(output_dir, exist_ok=True)
     path = os.path.join(str(output_dir), "grid_scores.npz")
     np.savez(path, **arrs)
