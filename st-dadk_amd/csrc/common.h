@@ -74,6 +74,35 @@ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// The bytes [p, p + bytes) of one buffer of a call, as the alias checks of the float64 entry points see it.
+struct ByteRange {
+  const void *p;
+  size_t bytes;
+};
+// an empty range overlaps nothing (kmeanspp's u when k == 1)
+static inline bool ranges_overlap(const ByteRange &x, const ByteRange &y) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(x.p), b = reinterpret_cast<uintptr_t>(y.p);
+  return x.bytes != 0 && y.bytes != 0 && a < b + y.bytes && b < a + x.bytes;
+}
+// No output aliases an input, no two outputs alias (the workspace counts as an output); `hint` ends the first message.
+template <int NO, int NI>
+static inline int check_no_alias(const char *who, const ByteRange (&out)[NO], const ByteRange (&in)[NI], const char *hint) {
+  for (int o = 0; o < NO; ++o) {
+    for (int i = 0; i < NI; ++i)
+      STDADK_REQUIRE(!ranges_overlap(out[o], in[i]), STDADK_E_ARG, "%s: an output aliases an input%s", who, hint);
+    for (int q = 0; q < o; ++q)
+      STDADK_REQUIRE(!ranges_overlap(out[o], out[q]), STDADK_E_ARG,
+                     "%s: two outputs (or an output and the workspace) alias", who);
+  }
+  return 0;
+}
+// The workspace holds `need` bytes (`sizer` names the function that says how many) and is 8-byte aligned.
+static inline int check_workspace(const char *who, const void *workspace, size_t have, size_t need, const char *sizer) {
+  STDADK_REQUIRE(have >= need, STDADK_E_WORKSPACE, "%s: workspace %zu < %zu bytes (%s)", who, have, need, sizer);
+  STDADK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, STDADK_E_ALIGN, "%s: workspace not 8-byte aligned", who);
+  return 0;
+}
+
 constexpr int kWave = 64;
 
 typedef unsigned short u16;            // a bf16 value as stored (weight copies, LDS images)

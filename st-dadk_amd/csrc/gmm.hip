@@ -11,9 +11,10 @@
 //                      of a component forms the same bits; slab 0 writes mu_out), then sum_i r_ij |x_i - mu_out_j|^2
 //                      over the slab -- non-negative terms about the NEW mean, a pass of its own.
 //   gmm_finish_kernel  ONE workgroup: nk_j again, var_out_j, sum_j nk_j in a fixed order, w_out_j, the lower bound.
-// No atomics, fixed orders: the same call on the same data gives the same bits.  Vector fp64 with exp / log; the work is
-// n k pair evaluations per pass and at the sizes of the knot initialiser (10 000 x 121) it is bound by launch latency.
-#include "common.h"
+// No atomics, fixed orders (the tree is block_sum_f64 of f64_block.h): the same call on the same data gives the same
+// bits.  Vector fp64 with exp / log; the work is n k pair evaluations per pass and at the sizes of the knot initialiser
+// (10 000 x 121) it is bound by launch latency.
+#include "f64_block.h"
 
 namespace stdadk {
 
@@ -33,20 +34,6 @@ __device__ __forceinline__ double pair_lp(double x, double y, double mx, double 
   const double dx = x - mx, dy = y - my;
   const double lp = fma(-h, fma(dx, dx, dy * dy), c);
   return lp > -1e300 ? lp : -1e300;         // a weight of 0 (log = -inf) stays out of inf - inf
-}
-
-// fixed tree over the GMM_T threads of a workgroup; the sum comes back in every thread
-__device__ __forceinline__ double block_sum(double *red, double v) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-#pragma unroll
-  for (int o = GMM_T / 2; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  return red[0];
 }
 
 __global__ __launch_bounds__(GMM_T) void gmm_lpn_kernel(const double *__restrict__ X, int n, int k,
@@ -84,7 +71,7 @@ __global__ __launch_bounds__(GMM_T) void gmm_lpn_kernel(const double *__restrict
   }
   const double l = m + log(s);
   if (live) lpn[i] = l;
-  const double tot = block_sum(red, live ? l : 0.0);
+  const double tot = block_sum_f64<GMM_T>(red, live ? l : 0.0);
   if (tid == 0) lb_part[blockIdx.x] = tot;
 }
 
@@ -121,7 +108,8 @@ __global__ __launch_bounds__(GMM_T) void gmm_sums_kernel(const double *__restric
     ax = fma(r, x, ax);
     ay = fma(r, y, ay);
   }
-  const double s0 = block_sum(red, a0), sx = block_sum(red, ax), sy = block_sum(red, ay);
+  const double s0 = block_sum_f64<GMM_T>(red, a0), sx = block_sum_f64<GMM_T>(red, ax);
+  const double sy = block_sum_f64<GMM_T>(red, ay);
   if (tid == 0) {
     double *p = part + ((size_t)j * gridDim.y + sl) * 3;
     p[0] = s0;
@@ -166,7 +154,7 @@ __global__ __launch_bounds__(GMM_T) void gmm_var_kernel(const double *__restrict
     const double ex = x - nx, ey = y - ny;
     a = fma(r, fma(ex, ex, ey * ey), a);
   }
-  const double s = block_sum(red, a);
+  const double s = block_sum_f64<GMM_T>(red, a);
   if (tid == 0) {
     vpart[(size_t)j * gridDim.y + sl] = s;
     if (sl == 0) {
@@ -194,21 +182,15 @@ __global__ __launch_bounds__(GMM_T) void gmm_finish_kernel(int n, int k, int sla
     w_out[j] = nk;                             // divided by the total below, by the thread that wrote it
     tot += nk;
   }
-  tot = block_sum(red, tot);
+  tot = block_sum_f64<GMM_T>(red, tot);
   for (int j = tid; j < k; j += GMM_T) w_out[j] = w_out[j] / tot;
   double lb = 0.0;
   for (int b = tid; b < nblk; b += GMM_T) lb += lb_part[b];
-  lb = block_sum(red, lb);
+  lb = block_sum_f64<GMM_T>(red, lb);
   if (tid == 0) lower_bound[0] = lb / (double)n;
 }
 
 static inline bool gmm_sizes_ok(int64_t n, int32_t k) { return n >= 1 && n < (1ll << 31) && k >= 1 && k <= 65536; }
-
-// [p, p + bytes) against [q, q + qbytes)
-static inline bool overlaps(const void *p, size_t bytes, const void *q, size_t qbytes) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + qbytes && b < a + bytes;
-}
 
 }  // namespace stdadk
 
@@ -231,20 +213,10 @@ extern "C" int stdadk_gmm_em_f64(const double *X, int64_t n, int32_t k, const do
                  "gmm_em: NULL pointer");
   const size_t kb = (size_t)k * sizeof(double);
   const size_t need = stdadk_gmm_workspace_bytes(n, k);
-  STDADK_REQUIRE(workspace_bytes >= need, STDADK_E_WORKSPACE,
-                 "gmm_em: workspace %zu < %zu bytes (stdadk_gmm_workspace_bytes)", workspace_bytes, need);
-  STDADK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, STDADK_E_ALIGN, "gmm_em: workspace not 8-byte aligned");
-  const struct { const void *p; size_t bytes; } in[] = {{X, (size_t)n * 2 * sizeof(double)}, {w, kb}, {mu, 2 * kb}, {var, kb}},
-                                                out[] = {{w_out, kb}, {mu_out, 2 * kb}, {var_out, kb},
-                                                         {lower_bound, sizeof(double)}, {workspace, need}};
-  for (int o = 0; o < 5; ++o) {
-    for (int i = 0; i < 4; ++i)
-      STDADK_REQUIRE(!overlaps(out[o].p, out[o].bytes, in[i].p, in[i].bytes), STDADK_E_ARG,
-                     "gmm_em: an output aliases an input (the caller ping-pongs two parameter sets)");
-    for (int q = 0; q < o; ++q)
-      STDADK_REQUIRE(!overlaps(out[o].p, out[o].bytes, out[q].p, out[q].bytes), STDADK_E_ARG,
-                     "gmm_em: two outputs (or an output and the workspace) alias");
-  }
+  if (int rc = check_workspace("gmm_em", workspace, workspace_bytes, need, "stdadk_gmm_workspace_bytes")) return rc;
+  const ByteRange in[] = {{X, (size_t)n * 2 * sizeof(double)}, {w, kb}, {mu, 2 * kb}, {var, kb}},
+                  out[] = {{w_out, kb}, {mu_out, 2 * kb}, {var_out, kb}, {lower_bound, sizeof(double)}, {workspace, need}};
+  if (int rc = check_no_alias("gmm_em", out, in, " (the caller ping-pongs two parameter sets)")) return rc;
   const GmmSlabs g = gmm_slabs(n, k);
   const int nblk = (int)ceil_div(n, GMM_T);
   double *lpn = (double *)workspace;

@@ -50,4 +50,43 @@ __device__ __forceinline__ double sum_partials(double *red, int nrows, RowFn row
 
 static inline int64_t grid_score_blocks(int64_t S) { return ceil_div(S > 0 ? S : 1, GS_T); }
 
+// ---- host side: what stdadk_grid_score_f32 and stdadk_quantile_diag_f32 ask of their arguments ----
+
+// S, nT and the row count S nT fit 31 bits (the kernels index rows with int)
+static inline bool grid_sizes_ok(int64_t S, int64_t nT) {
+  return S >= 0 && nT >= 0 && S < (1ll << 31) && nT < (1ll << 31) && S * nT < (1ll << 31);
+}
+
+// The checks after the NULL test, in this order: Q, the metric column (0 from a caller that has none), the interval
+// columns, the sizes, the workspace (`need` bytes, as `sizer` computes them).
+static inline int check_grid_args(const char *who, int64_t S, int64_t nT, int32_t Q, int32_t metric_col, int32_t lo_col,
+                                  int32_t hi_col, const void *workspace, size_t have, size_t need, const char *sizer) {
+  STDADK_REQUIRE(Q >= 1 && Q <= STDADK_MAX_Q, STDADK_E_ARG, "%s: Q=%d outside 1..%d", who, Q, STDADK_MAX_Q);
+  STDADK_REQUIRE(metric_col >= 0 && metric_col < Q, STDADK_E_ARG, "%s: metric_col=%d outside 0..%d", who, metric_col, Q - 1);
+  STDADK_REQUIRE((lo_col == -1 && hi_col == -1) || (lo_col >= 0 && hi_col < Q && lo_col < hi_col), STDADK_E_ARG,
+                 "%s: interval columns (%d, %d) must be (-1, -1) or 0 <= lo < hi < Q=%d", who, lo_col, hi_col, Q);
+  STDADK_REQUIRE(grid_sizes_ok(S, nT), STDADK_E_SHAPE, "%s: S*nT = %lld x %lld rows do not fit 31 bits", who, (long long)S,
+                 (long long)nT);
+  return check_workspace(who, workspace, have, need, sizer);
+}
+
+// the kernels' levels: the caller's Q, 0.5 each without any, 0.5 past Q
+static inline void fill_taus(float (&tau)[STDADK_MAX_Q], const float *taus_host, int Q) {
+  for (int q = 0; q < STDADK_MAX_Q; ++q) tau[q] = taus_host && q < Q ? taus_host[q] : 0.5f;
+}
+
+// STDADK_LAUNCH of the instantiation kern<Q> for Q in 1..STDADK_MAX_Q (checked before); the rest are its arguments
+#define STDADK_GRID_Q_CASE(kern, q, ...)   \
+  case q:                                  \
+    STDADK_LAUNCH(kern<q>, __VA_ARGS__);   \
+    break;
+#define STDADK_LAUNCH_FOR_Q(Q, kern, ...)                                                         \
+  switch (Q) {                                                                                    \
+    STDADK_GRID_Q_CASE(kern, 1, __VA_ARGS__) STDADK_GRID_Q_CASE(kern, 2, __VA_ARGS__)            \
+    STDADK_GRID_Q_CASE(kern, 3, __VA_ARGS__) STDADK_GRID_Q_CASE(kern, 4, __VA_ARGS__)            \
+    STDADK_GRID_Q_CASE(kern, 5, __VA_ARGS__) STDADK_GRID_Q_CASE(kern, 6, __VA_ARGS__)            \
+    STDADK_GRID_Q_CASE(kern, 7, __VA_ARGS__) STDADK_GRID_Q_CASE(kern, 8, __VA_ARGS__)            \
+  }
+static_assert(STDADK_MAX_Q == 8, "STDADK_LAUNCH_FOR_Q lists the instantiations");
+
 }  // namespace stdadk

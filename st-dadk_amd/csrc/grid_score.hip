@@ -176,7 +176,7 @@ __global__ __launch_bounds__(kWave) void grid_score_split_kernel(const double *_
 using namespace stdadk;
 
 extern "C" size_t stdadk_grid_score_workspace_bytes(int64_t S, int64_t nT) {
-  if (S < 0 || nT < 0 || S >= (1ll << 31) || nT >= (1ll << 31) || S * nT >= (1ll << 31)) return 0;
+  if (!grid_sizes_ok(S, nT)) return 0;
   const int64_t nblk = grid_score_blocks(S);
   return (size_t)nblk * (size_t)((nT > 0 ? nT : 1) * GS_TV + GS_XV) * sizeof(double);
 }
@@ -189,35 +189,19 @@ extern "C" int stdadk_grid_score_f32(const float *y_pred, const float *z, const 
   if (S == 0 || nT == 0) return 0;
   STDADK_REQUIRE(y_pred && z && split_acc && site_acc && time_acc && workspace, STDADK_E_ARG,
                  "grid_score: NULL pointer");
-  STDADK_REQUIRE(Q >= 1 && Q <= STDADK_MAX_Q, STDADK_E_ARG, "grid_score: Q=%d outside 1..%d", Q, STDADK_MAX_Q);
-  STDADK_REQUIRE(metric_col >= 0 && metric_col < Q, STDADK_E_ARG, "grid_score: metric_col=%d outside 0..%d", metric_col,
-                 Q - 1);
-  STDADK_REQUIRE((lo_col == -1 && hi_col == -1) || (lo_col >= 0 && hi_col < Q && lo_col < hi_col), STDADK_E_ARG,
-                 "grid_score: interval columns (%d, %d) must be (-1, -1) or 0 <= lo < hi < Q=%d", lo_col, hi_col, Q);
-  STDADK_REQUIRE(S < (1ll << 31) && nT < (1ll << 31) && S * nT < (1ll << 31), STDADK_E_SHAPE, "grid_score: S*nT = %lld x %lld rows do not fit 31 bits",
-                 (long long)S, (long long)nT);
-  const size_t need = stdadk_grid_score_workspace_bytes(S, nT);
-  STDADK_REQUIRE(workspace_bytes >= need, STDADK_E_WORKSPACE,
-                 "grid_score: workspace %zu < %zu bytes (stdadk_grid_score_workspace_bytes)", workspace_bytes, need);
-  STDADK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, STDADK_E_ALIGN, "grid_score: workspace not 8-byte aligned");
+  if (int rc = check_grid_args("grid_score", S, nT, Q, metric_col, lo_col, hi_col, workspace, workspace_bytes,
+                               stdadk_grid_score_workspace_bytes(S, nT), "stdadk_grid_score_workspace_bytes"))
+    return rc;
   const int nblk = (int)grid_score_blocks(S);
   GridScoreArgs a;
   a.yp = y_pred; a.z = z; a.split = split;
   a.S = (int)S; a.nT = (int)nT; a.mcol = metric_col; a.lo = lo_col; a.hi = hi_col;
-  for (int q = 0; q < STDADK_MAX_Q; ++q) a.tau[q] = taus_host && q < Q ? taus_host[q] : 0.5f;
+  fill_taus(a.tau, taus_host, Q);
   a.site_acc = site_acc;
   a.tpart = (double *)workspace;
   a.xpart = a.tpart + (size_t)nblk * nT * GS_TV;
   hipStream_t st = (hipStream_t)stream;
-  switch (Q) {
-#define STDADK_GS_CASE(q)                                                                              \
-  case q:                                                                                              \
-    STDADK_LAUNCH(grid_score_kernel<q>, dim3((unsigned)nblk), dim3(GS_T), 0, st, a);                   \
-    break;
-    STDADK_GS_CASE(1) STDADK_GS_CASE(2) STDADK_GS_CASE(3) STDADK_GS_CASE(4)
-    STDADK_GS_CASE(5) STDADK_GS_CASE(6) STDADK_GS_CASE(7) STDADK_GS_CASE(8)
-#undef STDADK_GS_CASE
-  }
+  STDADK_LAUNCH_FOR_Q(Q, grid_score_kernel, dim3((unsigned)nblk), dim3(GS_T), 0, st, a);
   STDADK_CHECK_LAUNCH("grid_score");
   STDADK_LAUNCH(grid_score_time_kernel, dim3((unsigned)nT + 1), dim3(GS_T), 0, st, (const double *)a.tpart,
                 (const double *)a.xpart, nblk, (int)nT, Q, lo_col >= 0 ? 1 : 0, time_acc, split_acc);

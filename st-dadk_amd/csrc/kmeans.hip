@@ -1,11 +1,11 @@
 // One iteration of size-constrained (balanced) k-means in two dimensions (stdadk_kmeans_balanced_iter_f64, see
 // include/stdadk.h): the EXACT constrained assignment on the centres given, then the means of the clusters.
 //
-// The costs c_ij = (x_i - mu_jx)^2 + (y_i - mu_jy)^2 are float64, every operation rounded once (km_cost, contraction
-// off, so that a host restatement forms the same bits).  The assignment works on q_ij = rint(c_ij 2^s), the costs on
-// one binary grid of spacing 2^-s <= max c 2^-51 held as 64-bit integers: path sums are then exact, and a cycle of
-// exact weight 0 -- duplicated points produce them all the time -- can never round to a negative one and keep
-// Bellman-Ford from settling.  An assignment optimal for q is within n max c 2^-51 of the optimum for c.
+// The costs c_ij = (x_i - mu_jx)^2 + (y_i - mu_jy)^2 are float64, every operation rounded once (sq_dist_f64 of
+// f64_block.h, so that a host restatement forms the same bits).  The assignment works on q_ij = rint(c_ij 2^s), the
+// costs on one binary grid of spacing 2^-s <= max c 2^-51 held as 64-bit integers: path sums are then exact, and a
+// cycle of exact weight 0 -- duplicated points produce them all the time -- can never round to a negative one and
+// keep Bellman-Ford from settling.  An assignment optimal for q is within n max c 2^-51 of the optimum for c.
 //
 // Launches, in order:
 //   km_point_kernel<false>  one thread per point, the centres through LDS in tiles of KM_KT: max_j c_ij, the
@@ -24,13 +24,13 @@
 //                           node by two integer minima; thread 0 walks the predecessors back and applies the path; the
 //                           rows of w of the clusters on the path are formed again by all threads.
 //   km_mean_kernel          workgroup j: the mean of the members of j, points in index order (thread t takes i = t mod
-//                           KM_T), then a fixed tree.
+//                           KM_T), then a fixed tree (block_sum_f64; the maxima go through block_max_f64).
 //   km_finish_kernel        ONE workgroup: inertia = sum_i c(x_i, mu_labels[i]), shift = sum_j |mu_out_j - mu_j|^2.
 // Every loop is bounded: augmentations by the total surplus (<= n), Bellman-Ford rounds by k + 1, the walk back by
 // k + 1; a bound hit writes status[0] != 0 and stops.  No workgroup waits on another.  No float atomics; the integer
 // atomics that hand out member slots decide only the ORDER of a member list, and every minimum over a list breaks
 // ties by point index, so the same call gives the same bits.
-#include "common.h"
+#include "f64_block.h"
 
 namespace stdadk {
 
@@ -43,12 +43,6 @@ static_assert(KM_MAX_K + 1 <= KM_AT && KM_KT == KM_T, "one node per thread; one 
 
 enum { KM_OK = 0, KM_AUGMENTATIONS = 1, KM_NEGATIVE_CYCLE = 2, KM_NO_DEFICIT = 3, KM_PRED_CYCLE = 4, KM_BAD_ARC = 5 };
 
-__device__ __forceinline__ double km_cost(double x, double y, double mx, double my) {
-#pragma clang fp contract(off)
-  const double dx = x - mx, dy = y - my;
-  const double a = dx * dx, b = dy * dy;
-  return a + b;
-}
 __device__ __forceinline__ long long km_quant(double c, int sh) { return llrint(ldexp(c, sh)); }
 
 // NEAREST = false: the workgroup's max c to part[blockIdx.x].  NEAREST = true: labels[i] = argmin_j q_ij.
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(KM_T) void km_point_kernel(const double *__restrict
     }
     __syncthreads();
     for (int t = 0; t < nt; ++t) {
-      const double c = km_cost(x, y, cen[t][0], cen[t][1]);
+      const double c = sq_dist_f64(x, y, cen[t][0], cen[t][1]);
       if (NEAREST) {
         const long long q = km_quant(c, sh);
         if (q < qbest) {
@@ -90,14 +84,8 @@ __global__ __launch_bounds__(KM_T) void km_point_kernel(const double *__restrict
   if (NEAREST) {
     if (live) labels[i] = jbest;
   } else {
-    red[tid] = live ? cmax : 0.0;
-    __syncthreads();
-#pragma unroll
-    for (int o = KM_T / 2; o > 0; o >>= 1) {
-      if (tid < o) red[tid] = red[tid] > red[tid + o] ? red[tid] : red[tid + o];
-      __syncthreads();
-    }
-    if (tid == 0) part[blockIdx.x] = red[0];
+    const double wmax = block_max_f64<KM_T>(red, live ? cmax : 0.0);
+    if (tid == 0) part[blockIdx.x] = wmax;
   }
 }
 
@@ -107,17 +95,11 @@ __global__ __launch_bounds__(KM_T) void km_scale_kernel(const double *__restrict
   const int tid = threadIdx.x;
   double m = 0.0;
   for (int b = tid; b < nblk; b += KM_T) m = part[b] > m ? part[b] : m;
-  red[tid] = m;
-  __syncthreads();
-#pragma unroll
-  for (int o = KM_T / 2; o > 0; o >>= 1) {
-    if (tid < o) red[tid] = red[tid] > red[tid + o] ? red[tid] : red[tid + o];
-    __syncthreads();
-  }
+  m = block_max_f64<KM_T>(red, m);
   if (tid == 0) {
     int e = 0;
-    if (red[0] > 0.0) frexp(red[0], &e);
-    shift[0] = red[0] > 0.0 ? 52 - e : 0;            // max c 2^s in [2^51, 2^52)
+    if (m > 0.0) frexp(m, &e);
+    shift[0] = m > 0.0 ? 52 - e : 0;                 // max c 2^s in [2^51, 2^52)
   }
 }
 
@@ -127,7 +109,7 @@ __global__ __launch_bounds__(KM_T) void km_q_kernel(const double *__restrict__ X
   const int e = blockIdx.x * KM_T + threadIdx.x;         // n k < 2^31 (km_sizes_ok)
   if (e >= n * k) return;
   const int i = e / k, j = e - i * k;
-  q[e] = km_quant(km_cost(X[2 * (size_t)i], X[2 * (size_t)i + 1], mu[2 * j], mu[2 * j + 1]), shift[0]);
+  q[e] = km_quant(sq_dist_f64(X[2 * (size_t)i], X[2 * (size_t)i + 1], mu[2 * j], mu[2 * j + 1]), shift[0]);
 }
 
 struct KmBalanceShared {
@@ -365,20 +347,6 @@ __global__ __launch_bounds__(KM_AT) void km_balance_kernel(int n, int k, int lo,
   }
 }
 
-// fixed tree over the KM_T threads of a workgroup; the sum comes back in every thread
-__device__ __forceinline__ double km_block_sum(double *red, double v) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-#pragma unroll
-  for (int o = KM_T / 2; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 __global__ __launch_bounds__(KM_T) void km_mean_kernel(const double *__restrict__ X, int n,
                                                        const int *__restrict__ labels, const double *__restrict__ mu,
                                                        double *__restrict__ mu_out) {
@@ -391,9 +359,9 @@ __global__ __launch_bounds__(KM_T) void km_mean_kernel(const double *__restrict_
       sy += X[2 * (size_t)i + 1];
       c += 1.0;
     }
-  sx = km_block_sum(red, sx);
-  sy = km_block_sum(red, sy);
-  c = km_block_sum(red, c);
+  sx = block_sum_f64<KM_T>(red, sx);
+  sy = block_sum_f64<KM_T>(red, sy);
+  c = block_sum_f64<KM_T>(red, c);
   if (tid == 0) {                                    // c >= lo >= 1 unless the assignment stopped on a bound (status)
     mu_out[2 * j] = c > 0.0 ? sx / c : mu[2 * j];
     mu_out[2 * j + 1] = c > 0.0 ? sy / c : mu[2 * j + 1];
@@ -408,11 +376,11 @@ __global__ __launch_bounds__(KM_T) void km_finish_kernel(const double *__restric
   double a = 0.0, s = 0.0;
   for (int i = tid; i < n; i += KM_T) {
     const int j = labels[i];
-    a += km_cost(X[2 * (size_t)i], X[2 * (size_t)i + 1], mu[2 * j], mu[2 * j + 1]);
+    a += sq_dist_f64(X[2 * (size_t)i], X[2 * (size_t)i + 1], mu[2 * j], mu[2 * j + 1]);
   }
-  for (int j = tid; j < k; j += KM_T) s += km_cost(mu_out[2 * j], mu_out[2 * j + 1], mu[2 * j], mu[2 * j + 1]);
-  a = km_block_sum(red, a);
-  s = km_block_sum(red, s);
+  for (int j = tid; j < k; j += KM_T) s += sq_dist_f64(mu_out[2 * j], mu_out[2 * j + 1], mu[2 * j], mu[2 * j + 1]);
+  a = block_sum_f64<KM_T>(red, a);
+  s = block_sum_f64<KM_T>(red, s);
   if (tid == 0) {
     stats[0] = a;
     stats[1] = s;
@@ -438,11 +406,6 @@ static inline KmLayout km_layout(int64_t n, int32_t k) {
   L.pos = o, o += (size_t)n * 4;
   L.bytes = align_up(o, 8);
   return L;
-}
-
-static inline bool km_overlaps(const void *p, size_t bytes, const void *q, size_t qbytes) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + qbytes && b < a + bytes;
 }
 
 }  // namespace stdadk
@@ -473,23 +436,13 @@ extern "C" int stdadk_kmeans_balanced_iter_f64(const double *X, int64_t n, int32
   STDADK_REQUIRE((int64_t)hi * k >= n, STDADK_E_SHAPE, "kmeans_balanced_iter: hi k = %d x %d is below n=%lld", hi, k,
                  (long long)n);
   const KmLayout L = km_layout(n, k);
-  STDADK_REQUIRE(workspace_bytes >= L.bytes, STDADK_E_WORKSPACE,
-                 "kmeans_balanced_iter: workspace %zu < %zu bytes (stdadk_kmeans_workspace_bytes)", workspace_bytes, L.bytes);
-  STDADK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, STDADK_E_ALIGN,
-                 "kmeans_balanced_iter: workspace not 8-byte aligned");
+  if (int rc = check_workspace("kmeans_balanced_iter", workspace, workspace_bytes, L.bytes, "stdadk_kmeans_workspace_bytes"))
+    return rc;
   const size_t kb = (size_t)k * 2 * sizeof(double);
-  const struct { const void *p; size_t bytes; } in[] = {{X, (size_t)n * 2 * sizeof(double)}, {mu, kb}},
-                                                out[] = {{mu_out, kb}, {labels, (size_t)n * sizeof(int32_t)},
-                                                         {stats, 2 * sizeof(double)}, {status, 2 * sizeof(int32_t)},
-                                                         {workspace, L.bytes}};
-  for (int o = 0; o < 5; ++o) {
-    for (int i = 0; i < 2; ++i)
-      STDADK_REQUIRE(!km_overlaps(out[o].p, out[o].bytes, in[i].p, in[i].bytes), STDADK_E_ARG,
-                     "kmeans_balanced_iter: an output aliases an input (the caller ping-pongs two sets of centres)");
-    for (int p = 0; p < o; ++p)
-      STDADK_REQUIRE(!km_overlaps(out[o].p, out[o].bytes, out[p].p, out[p].bytes), STDADK_E_ARG,
-                     "kmeans_balanced_iter: two outputs (or an output and the workspace) alias");
-  }
+  const ByteRange in[] = {{X, (size_t)n * 2 * sizeof(double)}, {mu, kb}},
+                  out[] = {{mu_out, kb}, {labels, (size_t)n * sizeof(int32_t)}, {stats, 2 * sizeof(double)},
+                           {status, 2 * sizeof(int32_t)}, {workspace, L.bytes}};
+  if (int rc = check_no_alias("kmeans_balanced_iter", out, in, " (the caller ping-pongs two sets of centres)")) return rc;
   char *base = (char *)workspace;
   long long *q = (long long *)(base + L.q), *w = (long long *)(base + L.w);
   double *part = (double *)(base + L.part);

@@ -23,10 +23,10 @@
 //      crossing row and publishes the candidate (row, coordinates) for the next step.  Exactly one thread owns each r_j;
 //      a slot nobody owns (only possible with u >= 1) keeps its preset, row n - 1.
 // The candidate slots are double-buffered by the step's parity; the next step's uniforms are loaded in B and reach LDS in C.
-// The first centre is step 0 with one candidate, `first`, and d = +inf.  Fixed orders throughout: the same call gives
-// the same bits, and two candidates with the same coordinates get the same pot_j.  pot == 0: every r_j is 0, thread 0
-// owns it and row 0 crosses.
-#include "common.h"
+// The first centre is step 0 with one candidate, `first`, and d = +inf.  The distance is sq_dist_f64 of f64_block.h.
+// Fixed orders throughout: the same call gives the same bits, and two candidates with the same coordinates get the same
+// pot_j.  pot == 0: every r_j is 0, thread 0 owns it and row 0 crosses.
+#include "f64_block.h"
 
 namespace stdadk {
 
@@ -38,13 +38,6 @@ constexpr int KPP_MAX_R = 10;              // rows per thread held in registers,
 constexpr int KPP_MAX_RUNS = 64;
 constexpr int KPP_MAX_K = 65536;
 static_assert(KPP_G * KPP_G == KPP_T && KPP_G <= kWave && KPP_MAX_L <= KPP_T / kWave, "one wave scans one candidate");
-
-__device__ __forceinline__ double kpp_dist(double x, double y, double cx, double cy) {
-#pragma clang fp contract(off)
-  const double dx = x - cx, dy = y - cy;
-  const double a = dx * dx, b = dy * dy;
-  return a + b;
-}
 
 // rows [tid R, (tid + 1) R) in registers; rows past n are (0, 0) with d = 0 and add 0.0 to every sum
 template <int R>
@@ -126,7 +119,7 @@ __global__ __launch_bounds__(KPP_T) void kmeanspp_kernel(const double *__restric
       const double cx = cand_x[cur][j], cy = cand_y[cur][j];
       double acc = 0.0;
       rows.each([&](int64_t, double x, double y, double &d) {
-        const double q = kpp_dist(x, y, cx, cy);
+        const double q = sq_dist_f64(x, y, cx, cy);
         acc += q < d ? q : d;
       });
       part[j * KPP_STRIDE + slot] = acc;
@@ -181,7 +174,7 @@ __global__ __launch_bounds__(KPP_T) void kmeanspp_kernel(const double *__restric
     const double W = part[best * KPP_STRIDE + slot], Gx = gxs[best][tid / KPP_G];
     double l = 0.0;
     rows.each([&](int64_t, double x, double y, double &d) {
-      const double q = kpp_dist(x, y, bx, by);
+      const double q = sq_dist_f64(x, y, bx, by);
       if (q < d) d = q;
       l += d;
     });
@@ -211,11 +204,6 @@ static inline bool kpp_sizes_ok(int64_t n, int32_t k, int32_t runs) {
   return n >= 1 && n < (1ll << 31) && k >= 1 && k <= KPP_MAX_K && k <= n && runs >= 1 && runs <= KPP_MAX_RUNS;
 }
 static inline bool kpp_in_registers(int64_t n) { return n <= (int64_t)KPP_T * KPP_MAX_R; }
-
-static inline bool kpp_overlaps(const void *p, size_t bytes, const void *q, size_t qbytes) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + qbytes && b < a + bytes;
-}
 
 template <class Rows>
 static int kpp_launch(const double *X, int64_t n, int32_t k, int32_t runs, int32_t L, const int32_t *first,
@@ -263,18 +251,10 @@ extern "C" int stdadk_kmeanspp_f64(const double *X, int64_t n, int32_t k, int32_
   STDADK_REQUIRE(!misaligned(first, 4) && !misaligned(idx_out, 4), STDADK_E_ALIGN,
                  "kmeanspp: first and idx_out must be 4-byte aligned");
   const size_t ub = k > 1 ? (size_t)runs * (size_t)(k - 1) * (size_t)L * sizeof(double) : 0;
-  const struct { const void *p; size_t bytes; } in[] = {{X, (size_t)n * 2 * sizeof(double)},
-                                                        {first, (size_t)runs * sizeof(int32_t)}, {u, ub}},
-                                                out[] = {{idx_out, (size_t)runs * k * sizeof(int32_t)},
-                                                         {pot_out, (size_t)runs * sizeof(double)}, {workspace, need}};
-  for (int o = 0; o < 3; ++o) {
-    for (int i = 0; i < 3; ++i)
-      STDADK_REQUIRE(in[i].bytes == 0 || !kpp_overlaps(out[o].p, out[o].bytes, in[i].p, in[i].bytes), STDADK_E_ARG,
-                     "kmeanspp: an output aliases an input");
-    for (int q = 0; q < o; ++q)
-      STDADK_REQUIRE(!kpp_overlaps(out[o].p, out[o].bytes, out[q].p, out[q].bytes), STDADK_E_ARG,
-                     "kmeanspp: two outputs (or an output and the workspace) alias");
-  }
+  const ByteRange in[] = {{X, (size_t)n * 2 * sizeof(double)}, {first, (size_t)runs * sizeof(int32_t)}, {u, ub}},
+                  out[] = {{idx_out, (size_t)runs * k * sizeof(int32_t)}, {pot_out, (size_t)runs * sizeof(double)},
+                           {workspace, need}};
+  if (int rc = check_no_alias("kmeanspp", out, in, "")) return rc;
   hipStream_t st = (hipStream_t)stream;
   double *dws = (double *)workspace;
   const int64_t per = ceil_div(n, KPP_T);

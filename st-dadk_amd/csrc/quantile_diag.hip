@@ -248,7 +248,7 @@ __global__ __launch_bounds__(kWave) void quantile_diag_split_kernel(const double
 using namespace stdadk;
 
 extern "C" size_t stdadk_quantile_diag_workspace_bytes(int64_t S, int64_t nT) {
-  if (S < 0 || nT < 0 || S >= (1ll << 31) || nT >= (1ll << 31) || S * nT >= (1ll << 31)) return 0;
+  if (!grid_sizes_ok(S, nT)) return 0;
   const int64_t nblk = grid_score_blocks(S), slices = nT > 0 ? nT : 1;
   return ((size_t)nblk * (size_t)(slices * QD_TV + QD_XV) + (size_t)slices * QD_TV) * sizeof(double);
 }
@@ -260,35 +260,20 @@ extern "C" int stdadk_quantile_diag_f32(const float *y_pred, const float *z, con
   STDADK_REQUIRE(S >= 0 && nT >= 0, STDADK_E_ARG, "quantile_diag: negative size");
   if (S == 0 || nT == 0) return 0;
   STDADK_REQUIRE(y_pred && z && split_acc && workspace, STDADK_E_ARG, "quantile_diag: NULL pointer");
-  STDADK_REQUIRE(Q >= 1 && Q <= STDADK_MAX_Q, STDADK_E_ARG, "quantile_diag: Q=%d outside 1..%d", Q, STDADK_MAX_Q);
-  STDADK_REQUIRE((lo_col == -1 && hi_col == -1) || (lo_col >= 0 && hi_col < Q && lo_col < hi_col), STDADK_E_ARG,
-                 "quantile_diag: interval columns (%d, %d) must be (-1, -1) or 0 <= lo < hi < Q=%d", lo_col, hi_col, Q);
-  STDADK_REQUIRE(S < (1ll << 31) && nT < (1ll << 31) && S * nT < (1ll << 31), STDADK_E_SHAPE,
-                 "quantile_diag: S*nT = %lld x %lld rows do not fit 31 bits", (long long)S, (long long)nT);
-  const size_t need = stdadk_quantile_diag_workspace_bytes(S, nT);
-  STDADK_REQUIRE(workspace_bytes >= need, STDADK_E_WORKSPACE,
-                 "quantile_diag: workspace %zu < %zu bytes (stdadk_quantile_diag_workspace_bytes)", workspace_bytes, need);
-  STDADK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, STDADK_E_ALIGN,
-                 "quantile_diag: workspace not 8-byte aligned");
+  if (int rc = check_grid_args("quantile_diag", S, nT, Q, 0, lo_col, hi_col, workspace, workspace_bytes,
+                               stdadk_quantile_diag_workspace_bytes(S, nT), "stdadk_quantile_diag_workspace_bytes"))
+    return rc;
   const int nblk = (int)grid_score_blocks(S);
   QuantileDiagArgs a;
   a.yp = y_pred; a.z = z; a.split = split;
   a.S = (int)S; a.nT = (int)nT; a.lo = lo_col; a.hi = hi_col;
-  for (int q = 0; q < STDADK_MAX_Q; ++q) a.tau[q] = taus_host && q < Q ? taus_host[q] : 0.5f;
+  fill_taus(a.tau, taus_host, Q);
   a.site_acc = site_acc;
   a.tpart = (double *)workspace;
   a.xpart = a.tpart + (size_t)nblk * nT * QD_TV;
   double *tsum = a.xpart + (size_t)nblk * QD_XV;
   hipStream_t st = (hipStream_t)stream;
-  switch (Q) {
-#define STDADK_QD_CASE(q)                                                                              \
-  case q:                                                                                              \
-    STDADK_LAUNCH(quantile_diag_kernel<q>, dim3((unsigned)nblk), dim3(GS_T), 0, st, a);                \
-    break;
-    STDADK_QD_CASE(1) STDADK_QD_CASE(2) STDADK_QD_CASE(3) STDADK_QD_CASE(4)
-    STDADK_QD_CASE(5) STDADK_QD_CASE(6) STDADK_QD_CASE(7) STDADK_QD_CASE(8)
-#undef STDADK_QD_CASE
-  }
+  STDADK_LAUNCH_FOR_Q(Q, quantile_diag_kernel, dim3((unsigned)nblk), dim3(GS_T), 0, st, a);
   STDADK_CHECK_LAUNCH("quantile_diag");
   STDADK_LAUNCH(quantile_diag_time_kernel, dim3((unsigned)nT + 1), dim3(GS_T), 0, st, (const double *)a.tpart,
                 (const double *)a.xpart, nblk, (int)nT, Q, tsum, time_acc, split_acc);

@@ -365,6 +365,28 @@ def _idx(t, what):
     return t.data_ptr(), t.numel()
 
 
+def _typed(what, tensor, name, dtype, shape):
+    """Address of a contiguous tensor of `dtype` and `shape` (None: any) on the current HIP device, for the wrappers of
+    the float64 side kernels; `what` names the calling wrapper in the error."""
+    if tensor.dtype != dtype or not _on_device(tensor) or not tensor.is_contiguous() \
+            or (shape is not None and tuple(tensor.shape) != shape):
+        of_shape = "" if shape is None else f" of shape {shape}"
+        raise RuntimeError(f"{what}: {name} must be a contiguous {dtype} tensor{of_shape} on the device, got "
+                           f"{tensor.dtype} {tuple(tensor.shape)} on {tensor.device}")
+    if tensor.is_cuda and tensor.device.index != _current_device():
+        raise RuntimeError(f"{what}: {name} lives on {tensor.device} but the current device is cuda:"
+                           f"{torch.cuda.current_device()}; call under torch.cuda.device({tensor.device.index})")
+    return tensor.data_ptr()
+
+
+def _workspace_bytes(symbol, why, *args):
+    """What the library's `symbol` answers for `args`; 0 means that it refuses them, `why` says what it accepts."""
+    n = getattr(lib(), symbol)(*args)
+    if n == 0:
+        raise RuntimeError(f"{symbol}: {why}")
+    return n
+
+
 # --------------------------------------------------------------------------------------------
 def rbf_build(coords, t, X, s_centers, s_bw, basis, t_centers, t_bw, out):
     """out[b,:] = [X | phi | psi]; `out` is (B, ld) fp32 with ld >= p+Ks+Kt.  Any of the three
@@ -464,10 +486,7 @@ def f32_pack_refresh(p, table):
 
 
 def mlp_workspace_bytes(desc, B):
-    n = lib().stdadk_mlp_workspace_bytes(C.byref(desc), B)
-    if n == 0:
-        raise RuntimeError("stdadk_mlp_workspace_bytes: invalid descriptor")
-    return n
+    return _workspace_bytes("stdadk_mlp_workspace_bytes", "invalid descriptor", C.byref(desc), B)
 
 
 def _mask_array(masks):
@@ -529,10 +548,7 @@ def step_uses_window(basis, desc, flags):
 
 
 def step_workspace_bytes(basis, desc, B, flags):
-    n = lib().stdadk_step_workspace_bytes(C.byref(basis), C.byref(desc), B, flags)
-    if n == 0:
-        raise RuntimeError("stdadk_step_workspace_bytes: invalid descriptors")
-    return n
+    return _workspace_bytes("stdadk_step_workspace_bytes", "invalid descriptors", C.byref(basis), C.byref(desc), B, flags)
 
 
 def forward(basis, desc, params, coords, t, X, B, y_pred, workspace, flags, training=False, seed=0,
@@ -727,10 +743,7 @@ EVAL_OBJECTIVE, EVAL_SSE, EVAL_SAE, EVAL_ROWS, EVAL_BATCHES, EVAL_CHECK, EVAL_SL
 
 
 def eval_workspace_bytes(basis, desc, B, flags):
-    n = lib().stdadk_eval_workspace_bytes(C.byref(basis), C.byref(desc), B, flags)
-    if n == 0:
-        raise RuntimeError("stdadk_eval_workspace_bytes: invalid descriptors")
-    return n
+    return _workspace_bytes("stdadk_eval_workspace_bytes", "invalid descriptors", C.byref(basis), C.byref(desc), B, flags)
 
 
 def eval_indexed(basis, desc, params, coords_all, t_all, X_all, y_all, idx, loss_desc, metric_col, batch_weight, acc,
@@ -751,18 +764,27 @@ GRID_N, GRID_SSE, GRID_SAE, GRID_COVER, GRID_WIDTH, GRID_CHECK, GRID_SLOTS = 0, 
 
 
 def grid_score_workspace_bytes(S, nT):
-    n = lib().stdadk_grid_score_workspace_bytes(S, nT)
-    if n == 0:
-        raise RuntimeError(f"stdadk_grid_score_workspace_bytes: bad grid {S} x {nT} (S*nT must stay below 2^31)")
-    return n
+    return _workspace_bytes("stdadk_grid_score_workspace_bytes", f"bad grid {S} x {nT} (S*nT must stay below 2^31)", S, nT)
 
 
-def _f64_acc(tensor, name, shape):
-    if tensor.dtype != torch.float64 or not _on_device(tensor) or not tensor.is_contiguous() \
-            or tuple(tensor.shape) != shape:
-        raise RuntimeError(f"grid_score: {name} must be a contiguous float64 tensor of shape {shape} on the device, "
-                           f"got {tensor.dtype} {tuple(tensor.shape)} on {tensor.device}")
-    return tensor.data_ptr()
+def _grid_args(what, y_pred, z, split, taus, workspace):
+    """The checks grid_score and quantile_diag share; returns nT, S, Q and the levels as a c_float array (or None)."""
+    if z.dim() != 2 or y_pred.dim() != 2:
+        raise RuntimeError(f"{what}: z must be (nT, S) and y_pred (nT*S, Q)")
+    nT, S = z.shape
+    Q = y_pred.shape[1]
+    if y_pred.shape[0] != nT * S:
+        raise RuntimeError(f"{what}: y_pred has {y_pred.shape[0]} rows, z is {nT} x {S}")
+    for name, x in (("y_pred", y_pred), ("z", z)):
+        if x.dtype != torch.float32:
+            raise RuntimeError(f"{what}: {name} must be float32, got {x.dtype}")
+    if split is not None and (split.dtype != torch.uint8 or tuple(split.shape) != (nT, S)):
+        raise RuntimeError(f"{what}: split must be uint8 of shape {(nT, S)}, got {split.dtype} {tuple(split.shape)}")
+    if taus is not None and len(taus) != Q:
+        raise RuntimeError(f"{what}: {Q} quantile levels expected, got {len(taus)}")
+    if workspace.dtype != torch.float64 or not _on_device(workspace) or not workspace.is_contiguous():
+        raise RuntimeError(f"{what}: workspace must be a contiguous float64 tensor on the device")
+    return nT, S, Q, (C.c_float * Q)(*[float(q) for q in taus]) if taus is not None else None
 
 
 def grid_score(y_pred, z, split, metric_col, taus, lo_col, hi_col, split_acc, site_acc, time_acc, workspace):
@@ -770,26 +792,12 @@ def grid_score(y_pred, z, split, metric_col, taus, lo_col, hi_col, split_acc, si
     value, split (nT, S) uint8 codes 0..3 or None; sums are ADDED into split_acc (4, GRID_SLOTS) and site_acc
     (4, S, 3) and ASSIGNED to time_acc (4, nT, 3), all float64 on the device.  taus: Q levels or None (0.5 each);
     lo_col / hi_col: the interval's columns or -1 / -1."""
-    if z.dim() != 2 or y_pred.dim() != 2:
-        raise RuntimeError("grid_score: z must be (nT, S) and y_pred (nT*S, Q)")
-    nT, S = z.shape
-    Q = y_pred.shape[1]
-    if y_pred.shape[0] != nT * S:
-        raise RuntimeError(f"grid_score: y_pred has {y_pred.shape[0]} rows, z is {nT} x {S}")
-    for name, x in (("y_pred", y_pred), ("z", z)):
-        if x.dtype != torch.float32:
-            raise RuntimeError(f"grid_score: {name} must be float32, got {x.dtype}")
-    if split is not None and (split.dtype != torch.uint8 or tuple(split.shape) != (nT, S)):
-        raise RuntimeError(f"grid_score: split must be uint8 of shape {(nT, S)}, got {split.dtype} {tuple(split.shape)}")
-    if taus is not None and len(taus) != Q:
-        raise RuntimeError(f"grid_score: {Q} quantile levels expected, got {len(taus)}")
-    if workspace.dtype != torch.float64 or not _on_device(workspace) or not workspace.is_contiguous():
-        raise RuntimeError("grid_score: workspace must be a contiguous float64 tensor on the device")
-    arr = (C.c_float * Q)(*[float(q) for q in taus]) if taus is not None else None
+    nT, S, Q, arr = _grid_args("grid_score", y_pred, z, split, taus, workspace)
+    acc = lambda t, name, shape: _typed("grid_score", t, name, torch.float64, shape)      # noqa: E731
     rc = lib().stdadk_grid_score_f32(
         _dev(y_pred, "y_pred"), _dev(z, "z"), _dev(split, "split"), S, nT, Q, int(metric_col), arr, int(lo_col),
-        int(hi_col), _f64_acc(split_acc, "split_acc", (4, GRID_SLOTS)), _f64_acc(site_acc, "site_acc", (4, S, 3)),
-        _f64_acc(time_acc, "time_acc", (4, nT, 3)), workspace.data_ptr(), workspace.numel() * 8, _stream())
+        int(hi_col), acc(split_acc, "split_acc", (4, GRID_SLOTS)), acc(site_acc, "site_acc", (4, S, 3)),
+        acc(time_acc, "time_acc", (4, nT, 3)), workspace.data_ptr(), workspace.numel() * 8, _stream())
     _check(rc, "stdadk_grid_score_f32")
 
 
@@ -799,10 +807,8 @@ QD_N, QD_BELOW, QD_PIT, QD_CROSS_ROWS, QD_PAIR, QD_DEPTH1, QD_DEPTH2, QD_CRPS, Q
 
 
 def quantile_diag_workspace_bytes(S, nT):
-    n = lib().stdadk_quantile_diag_workspace_bytes(S, nT)
-    if n == 0:
-        raise RuntimeError(f"stdadk_quantile_diag_workspace_bytes: bad grid {S} x {nT} (S*nT must stay below 2^31)")
-    return n
+    return _workspace_bytes("stdadk_quantile_diag_workspace_bytes", f"bad grid {S} x {nT} (S*nT must stay below 2^31)",
+                            S, nT)
 
 
 def quantile_diag(y_pred, z, split, taus, lo_col, hi_col, split_acc, site_acc, time_acc, workspace):
@@ -811,49 +817,18 @@ def quantile_diag(y_pred, z, split, taus, lo_col, hi_col, split_acc, site_acc, t
     into split_acc (4, QD_SLOTS) and site_acc (4, S, 4) and ASSIGNED to time_acc (4, nT, 4), all float64 on the
     device; site_acc and time_acc may each be None (skipped).  taus: Q levels or None (0.5 each); lo_col / hi_col: the
     interval's columns or -1 / -1."""
-    if z.dim() != 2 or y_pred.dim() != 2:
-        raise RuntimeError("quantile_diag: z must be (nT, S) and y_pred (nT*S, Q)")
-    nT, S = z.shape
-    Q = y_pred.shape[1]
-    if y_pred.shape[0] != nT * S:
-        raise RuntimeError(f"quantile_diag: y_pred has {y_pred.shape[0]} rows, z is {nT} x {S}")
-    for name, x in (("y_pred", y_pred), ("z", z)):
-        if x.dtype != torch.float32:
-            raise RuntimeError(f"quantile_diag: {name} must be float32, got {x.dtype}")
-    if split is not None and (split.dtype != torch.uint8 or tuple(split.shape) != (nT, S)):
-        raise RuntimeError(f"quantile_diag: split must be uint8 of shape {(nT, S)}, got {split.dtype} "
-                           f"{tuple(split.shape)}")
-    if taus is not None and len(taus) != Q:
-        raise RuntimeError(f"quantile_diag: {Q} quantile levels expected, got {len(taus)}")
-    if workspace.dtype != torch.float64 or not _on_device(workspace) or not workspace.is_contiguous():
-        raise RuntimeError("quantile_diag: workspace must be a contiguous float64 tensor on the device")
-    arr = (C.c_float * Q)(*[float(q) for q in taus]) if taus is not None else None
+    nT, S, Q, arr = _grid_args("quantile_diag", y_pred, z, split, taus, workspace)
+    acc = lambda t, name, shape: _typed("quantile_diag", t, name, torch.float64, shape)      # noqa: E731
     rc = lib().stdadk_quantile_diag_f32(
         _dev(y_pred, "y_pred"), _dev(z, "z"), _dev(split, "split"), S, nT, Q, arr, int(lo_col), int(hi_col),
-        _f64_acc(split_acc, "split_acc", (4, QD_SLOTS)),
-        None if site_acc is None else _f64_acc(site_acc, "site_acc", (4, S, 4)),
-        None if time_acc is None else _f64_acc(time_acc, "time_acc", (4, nT, 4)),
-        workspace.data_ptr(), workspace.numel() * 8, _stream())
+        acc(split_acc, "split_acc", (4, QD_SLOTS)), None if site_acc is None else acc(site_acc, "site_acc", (4, S, 4)),
+        None if time_acc is None else acc(time_acc, "time_acc", (4, nT, 4)), workspace.data_ptr(), workspace.numel() * 8,
+        _stream())
     _check(rc, "stdadk_quantile_diag_f32")
 
 
 def gmm_workspace_bytes(n, k):
-    nbytes = lib().stdadk_gmm_workspace_bytes(n, k)
-    if nbytes == 0:
-        raise RuntimeError(f"stdadk_gmm_workspace_bytes: bad sizes n={n}, k={k} (1 <= n < 2^31, 1 <= k <= 65536)")
-    return nbytes
-
-
-def _f64(tensor, name, shape):
-    """Address of a contiguous float64 tensor of `shape` on the current HIP device."""
-    if tensor.dtype != torch.float64 or not _on_device(tensor) or not tensor.is_contiguous() \
-            or (shape is not None and tuple(tensor.shape) != shape):
-        raise RuntimeError(f"gmm_em: {name} must be a contiguous float64 tensor{'' if shape is None else f' of shape {shape}'}"
-                           f" on the device, got {tensor.dtype} {tuple(tensor.shape)} on {tensor.device}")
-    if tensor.is_cuda and tensor.device.index != _current_device():
-        raise RuntimeError(f"gmm_em: {name} lives on {tensor.device} but the current device is cuda:"
-                           f"{torch.cuda.current_device()}; call under torch.cuda.device({tensor.device.index})")
-    return tensor.data_ptr()
+    return _workspace_bytes("stdadk_gmm_workspace_bytes", f"bad sizes n={n}, k={k} (1 <= n < 2^31, 1 <= k <= 65536)", n, k)
 
 
 def gmm_em(X, w, mu, var, reg_covar, w_out, mu_out, var_out, lower_bound, workspace):
@@ -863,10 +838,11 @@ def gmm_em(X, w, mu, var, reg_covar, w_out, mu_out, var_out, lower_bound, worksp
     if X.dim() != 2 or X.shape[1] != 2:
         raise RuntimeError(f"gmm_em: X must be (n, 2), got {tuple(X.shape)}")
     n, k = X.shape[0], w.shape[0] if w.dim() == 1 else -1
+    f64 = lambda t, name, shape: _typed("gmm_em", t, name, torch.float64, shape)      # noqa: E731
     rc = lib().stdadk_gmm_em_f64(
-        _f64(X, "X", (n, 2)), n, k, _f64(w, "w", (k,)), _f64(mu, "mu", (k, 2)), _f64(var, "var", (k,)),
-        float(reg_covar), _f64(w_out, "w_out", (k,)), _f64(mu_out, "mu_out", (k, 2)), _f64(var_out, "var_out", (k,)),
-        _f64(lower_bound, "lower_bound", (1,)), _f64(workspace, "workspace", None), workspace.numel() * 8, _stream())
+        f64(X, "X", (n, 2)), n, k, f64(w, "w", (k,)), f64(mu, "mu", (k, 2)), f64(var, "var", (k,)),
+        float(reg_covar), f64(w_out, "w_out", (k,)), f64(mu_out, "mu_out", (k, 2)), f64(var_out, "var_out", (k,)),
+        f64(lower_bound, "lower_bound", (1,)), f64(workspace, "workspace", None), workspace.numel() * 8, _stream())
     _check(rc, "stdadk_gmm_em_f64")
 
 
@@ -876,23 +852,8 @@ KMEANS_STATUS = {1: "more augmentations than points", 2: "Bellman-Ford did not s
 
 
 def kmeans_workspace_bytes(n, k):
-    nbytes = lib().stdadk_kmeans_workspace_bytes(n, k)
-    if nbytes == 0:
-        raise RuntimeError(f"stdadk_kmeans_workspace_bytes: bad sizes n={n}, k={k} (n >= 1, 1 <= k <= {KMEANS_MAX_K}, "
-                           f"n k < 2^31)")
-    return nbytes
-
-
-def _dev_typed(tensor, name, dtype, shape, what):
-    """Address of a contiguous tensor of `dtype` and `shape` on the current HIP device."""
-    if tensor.dtype != dtype or not _on_device(tensor) or not tensor.is_contiguous() \
-            or (shape is not None and tuple(tensor.shape) != shape):
-        raise RuntimeError(f"{what}: {name} must be a contiguous {dtype} tensor{'' if shape is None else f' of shape {shape}'}"
-                           f" on the device, got {tensor.dtype} {tuple(tensor.shape)} on {tensor.device}")
-    if tensor.is_cuda and tensor.device.index != _current_device():
-        raise RuntimeError(f"{what}: {name} lives on {tensor.device} but the current device is cuda:"
-                           f"{torch.cuda.current_device()}; call under torch.cuda.device({tensor.device.index})")
-    return tensor.data_ptr()
+    return _workspace_bytes("stdadk_kmeans_workspace_bytes",
+                            f"bad sizes n={n}, k={k} (n >= 1, 1 <= k <= {KMEANS_MAX_K}, n k < 2^31)", n, k)
 
 
 def kmeans_balanced_iter(X, mu, lo, hi, mu_out, labels, stats, status, workspace):
@@ -903,8 +864,8 @@ def kmeans_balanced_iter(X, mu, lo, hi, mu_out, labels, stats, status, workspace
     if X.dim() != 2 or X.shape[1] != 2:
         raise RuntimeError(f"kmeans_balanced_iter: X must be (n, 2), got {tuple(X.shape)}")
     n, k = X.shape[0], mu.shape[0] if mu.dim() == 2 else -1
-    f64 = lambda t, name, shape: _dev_typed(t, name, torch.float64, shape, "kmeans_balanced_iter")      # noqa: E731
-    i32 = lambda t, name, shape: _dev_typed(t, name, torch.int32, shape, "kmeans_balanced_iter")        # noqa: E731
+    f64 = lambda t, name, shape: _typed("kmeans_balanced_iter", t, name, torch.float64, shape)      # noqa: E731
+    i32 = lambda t, name, shape: _typed("kmeans_balanced_iter", t, name, torch.int32, shape)        # noqa: E731
     rc = lib().stdadk_kmeans_balanced_iter_f64(
         f64(X, "X", (n, 2)), n, k, f64(mu, "mu", (k, 2)), int(lo), int(hi), f64(mu_out, "mu_out", (k, 2)),
         i32(labels, "labels", (n,)), f64(stats, "stats", (2,)), i32(status, "status", (2,)),
@@ -916,11 +877,9 @@ KMEANSPP_MAX_K, KMEANSPP_MAX_RUNS, KMEANSPP_MAX_L = 65536, 64, 16        # KPP_M
 
 
 def kmeanspp_workspace_bytes(n, k, runs):
-    nbytes = lib().stdadk_kmeanspp_workspace_bytes(n, k, runs)
-    if nbytes == 0:
-        raise RuntimeError(f"stdadk_kmeanspp_workspace_bytes: bad sizes n={n}, k={k}, runs={runs} (1 <= n < 2^31, "
-                           f"1 <= k <= min(n, {KMEANSPP_MAX_K}), 1 <= runs <= {KMEANSPP_MAX_RUNS})")
-    return nbytes
+    return _workspace_bytes("stdadk_kmeanspp_workspace_bytes",
+                            f"bad sizes n={n}, k={k}, runs={runs} (1 <= n < 2^31, 1 <= k <= min(n, {KMEANSPP_MAX_K}), "
+                            f"1 <= runs <= {KMEANSPP_MAX_RUNS})", n, k, runs)
 
 
 def kmeanspp(X, first, u, idx_out, pot_out, workspace):
@@ -934,8 +893,8 @@ def kmeanspp(X, first, u, idx_out, pot_out, workspace):
         raise RuntimeError(f"kmeanspp: idx_out must be (runs, k) and u (runs, k - 1, L), got {tuple(idx_out.shape)} and "
                            f"{tuple(u.shape)}")
     n, (runs, k), L = X.shape[0], idx_out.shape, u.shape[2]
-    f64 = lambda t, name, shape: _dev_typed(t, name, torch.float64, shape, "kmeanspp")      # noqa: E731
-    i32 = lambda t, name, shape: _dev_typed(t, name, torch.int32, shape, "kmeanspp")        # noqa: E731
+    f64 = lambda t, name, shape: _typed("kmeanspp", t, name, torch.float64, shape)      # noqa: E731
+    i32 = lambda t, name, shape: _typed("kmeanspp", t, name, torch.int32, shape)        # noqa: E731
     rc = lib().stdadk_kmeanspp_f64(
         f64(X, "X", (n, 2)), n, k, runs, L, i32(first, "first", (runs,)), f64(u, "u", (runs, k - 1, L)),
         i32(idx_out, "idx_out", (runs, k)), f64(pot_out, "pot_out", (runs,)), f64(workspace, "workspace", None),

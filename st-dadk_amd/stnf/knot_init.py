@@ -48,6 +48,22 @@ def seed_parameters(points, idx, reg_covar):
     return w, mu, var
 
 
+def _check_points(who, points64, host_path):
+    """`points64` is (n, 2) float64 on a HIP device, or `who` refuses it; `host_path` says where the host path is."""
+    if points64.dtype != torch.float64 or points64.dim() != 2 or points64.shape[1] != 2:
+        raise RuntimeError(f"{who}: points must be (n, 2) float64, got {points64.dtype} {tuple(points64.shape)}")
+    if not points64.is_cuda:
+        raise RuntimeError(f"{who}: points must live on a HIP device (cuda:N), got {points64.device}; {host_path}")
+
+
+def _seed_rows(who, r, idx, k, unit):
+    """The k seed rows of restart r as an int64 array."""
+    idx = np.asarray(idx, np.int64)
+    if idx.shape != (k,):
+        raise ValueError(f"{who}: restart {r} has {idx.shape} seeds, {k} {unit} expected")
+    return idx
+
+
 def fit_spherical_gmm(points64, n_components, seed_indices, max_iter=100, tol=1e-3, reg_covar=1e-6):
     """EM for a spherical mixture of `n_components` Gaussians on points64 ((n, 2) float64 on a HIP device), one restart
     per index array of `seed_indices` (the k rows whose one-hot responsibilities start it), as GaussianMixture.fit
@@ -55,11 +71,7 @@ def fit_spherical_gmm(points64, n_components, seed_indices, max_iter=100, tol=1e
     then M) and stops when |lb - prev| < tol; the restart with the largest lower bound is kept, the first on a tie.
     Returns GmmFit(weights (k,), means (k, 2), variances (k,) float64 device tensors, lower_bound, per-restart n_iter,
     the chosen restart, per-restart lower bounds)."""
-    if points64.dtype != torch.float64 or points64.dim() != 2 or points64.shape[1] != 2:
-        raise RuntimeError(f"fit_spherical_gmm: points must be (n, 2) float64, got {points64.dtype} {tuple(points64.shape)}")
-    if not points64.is_cuda:
-        raise RuntimeError(f"fit_spherical_gmm: points must live on a HIP device (cuda:N), got {points64.device}; the "
-                           f"host path is sklearn's (init_device=None)")
+    _check_points("fit_spherical_gmm", points64, "the host path is sklearn's (init_device=None)")
     if len(seed_indices) == 0:
         raise ValueError("fit_spherical_gmm: no restart given")
     points64 = points64.contiguous()
@@ -72,9 +84,7 @@ def fit_spherical_gmm(points64, n_components, seed_indices, max_iter=100, tol=1e
     best, best_lb, best_params, n_iters, lbs = -1, -math.inf, None, [], []
     with torch.cuda.device(dev):
         for r, idx in enumerate(seed_indices):
-            idx = np.asarray(idx, np.int64)
-            if idx.shape != (k,):
-                raise ValueError(f"fit_spherical_gmm: restart {r} has {idx.shape} seeds, {k} components expected")
+            idx = _seed_rows("fit_spherical_gmm", r, idx, k, "components")
             cur = tuple(torch.from_numpy(a).to(dev) for a in seed_parameters(host, idx, reg_covar))
             nxt = new()
             lb, it = -math.inf, 0
@@ -150,9 +160,7 @@ def kmeanspp_stream(n, n_centers):
 def kmeanspp_seeds_device(points64, n_centers):
     """kmeanspp_seeds with the data-dependent part on the device: points64 (n, 2) float64 on a HIP device; per level one
     stdadk_kmeanspp_f64 call with runs = N_INIT on the stream of kmeanspp_stream and one read of the N_INIT x k rows."""
-    if points64.dtype != torch.float64 or points64.dim() != 2 or points64.shape[1] != 2 or not points64.is_cuda:
-        raise RuntimeError(f"kmeanspp_seeds_device: points must be (n, 2) float64 on a HIP device, got {points64.dtype} "
-                           f"{tuple(points64.shape)} on {points64.device}")
+    _check_points("kmeanspp_seeds_device", points64, "kmeanspp_seeds is the host path")
     points64 = points64.contiguous()
     dev, n = points64.device, points64.shape[0]
     for k in n_centers:
@@ -177,25 +185,32 @@ def seeds_by_level(pts, pts_dev, n_centers, seeding):
     return kmeanspp_seeds(pts, n_centers) if seeding == 'host' else kmeanspp_seeds_device(pts_dev, n_centers)
 
 
+def _knots_on_device(who, host_path, train_coords, n_centers, device, seeding, level_knots, admit=lambda n, k: None):
+    """What gmm_knots and balanced_kmeans_knots share.  The subsample is drawn first, then the seeds (both may draw from
+    the global numpy RNG); admit(n, k) may refuse a level before anything reaches the device; level_knots(points on the
+    device, k, the level's seeds) -> (centres (k, 2), bandwidths (k,)) float32 host tensors, concatenated in list order."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"{who}: a HIP device (cuda:N) is required, got {device}; {host_path}")
+    if seeding not in SEEDINGS:
+        raise ValueError(f"{who}: seeding must be one of {SEEDINGS}, got {seeding!r}")
+    pts = subsample(train_coords)
+    for k in n_centers:
+        admit(len(pts), k)
+    pts_dev = torch.from_numpy(pts).to(device)
+    seeds = seeds_by_level(pts, pts_dev, n_centers, seeding)
+    cs, bs = zip(*[level_knots(pts_dev, k, level_seeds) for k, level_seeds in zip(n_centers, seeds)])
+    return torch.cat(cs, dim=0), torch.cat(bs, dim=0)
+
+
 def gmm_knots(train_coords, n_centers, device, seeding='host'):
     """The reference's _init_gmm with the mixture fitted on `device`: (centres (sum k, 2), bandwidths (sum k,)) float32
     host tensors, levels concatenated in list order.  seeding: 'host' = sklearn's kmeans_plusplus, 'device' = the same
     random stream through stdadk_kmeanspp_f64."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"gmm_knots: a HIP device (cuda:N) is required, got {device}; init_device=None is the host path")
-    if seeding not in SEEDINGS:
-        raise ValueError(f"gmm_knots: seeding must be one of {SEEDINGS}, got {seeding!r}")
-    pts = subsample(train_coords)
-    pts_dev = torch.from_numpy(pts).to(device)
-    seeds = seeds_by_level(pts, pts_dev, n_centers, seeding)
-    cs, bs = [], []
-    for k, level_seeds in zip(n_centers, seeds):
+    def level(pts_dev, k, level_seeds):
         fit = fit_spherical_gmm(pts_dev, k, level_seeds, max_iter=100, tol=1e-3, reg_covar=1e-6)
-        c, b = knots_from_fit(fit.means.cpu().numpy(), fit.variances.cpu().numpy(), k)
-        cs.append(c)
-        bs.append(b)
-    return torch.cat(cs, dim=0), torch.cat(bs, dim=0)
+        return knots_from_fit(fit.means.cpu().numpy(), fit.variances.cpu().numpy(), k)
+    return _knots_on_device("gmm_knots", "init_device=None is the host path", train_coords, n_centers, device, seeding, level)
 
 
 def balanced_bounds(n, k):
@@ -213,11 +228,7 @@ def fit_balanced_kmeans(points64, k, seed_indices, max_iter=100, tol_factor=1e-4
     Returns KMeansFit(centers (k, 2) float64 and labels (n,) int32 device tensors, inertia, per-restart n_iter, the
     chosen restart, per-restart inertias).  `history`, a list, receives per restart the list of (inertia, shift,
     augmentations) of every iteration."""
-    if points64.dtype != torch.float64 or points64.dim() != 2 or points64.shape[1] != 2:
-        raise RuntimeError(f"fit_balanced_kmeans: points must be (n, 2) float64, got {points64.dtype} {tuple(points64.shape)}")
-    if not points64.is_cuda:
-        raise RuntimeError(f"fit_balanced_kmeans: points must live on a HIP device (cuda:N), got {points64.device}; "
-                           f"there is no host path (it needs the k_means_constrained package)")
+    _check_points("fit_balanced_kmeans", points64, "there is no host path (it needs the k_means_constrained package)")
     if len(seed_indices) == 0:
         raise ValueError("fit_balanced_kmeans: no restart given")
     points64 = points64.contiguous()
@@ -231,9 +242,7 @@ def fit_balanced_kmeans(points64, k, seed_indices, max_iter=100, tol_factor=1e-4
     best, best_inertia, best_out, n_iters, inertias = -1, math.inf, None, [], []
     with torch.cuda.device(dev):
         for r, idx in enumerate(seed_indices):
-            idx = np.asarray(idx, np.int64)
-            if idx.shape != (k,):
-                raise ValueError(f"fit_balanced_kmeans: restart {r} has {idx.shape} seeds, {k} clusters expected")
+            idx = _seed_rows("fit_balanced_kmeans", r, idx, k, "clusters")
             cur = torch.from_numpy(host[idx]).to(dev)
             nxt = torch.empty_like(cur)
             labels = torch.empty(n, device=dev, dtype=torch.int32)
@@ -275,21 +284,8 @@ def neighbour_bandwidths(centers, k, k0):
 def balanced_kmeans_knots(train_coords, n_centers, device, seeding='host'):
     """The reference's _init_kmeans_balanced with the fit of fit_balanced_kmeans on `device`: (centres (sum k, 2),
     bandwidths (sum k,)) float32 host tensors, levels concatenated in list order.  seeding as in gmm_knots."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"balanced_kmeans_knots: a HIP device (cuda:N) is required, got {device}; without "
-                           f"init_device the initialiser needs the k_means_constrained package")
-    if seeding not in SEEDINGS:
-        raise ValueError(f"balanced_kmeans_knots: seeding must be one of {SEEDINGS}, got {seeding!r}")
-    pts = subsample(train_coords)
-    for k in n_centers:
-        balanced_bounds(len(pts), k)
-    pts_dev = torch.from_numpy(pts).to(device)
-    seeds = seeds_by_level(pts, pts_dev, n_centers, seeding)
-    cs, bs = [], []
-    for k, level_seeds in zip(n_centers, seeds):
-        fit = fit_balanced_kmeans(pts_dev, k, level_seeds)
-        c = fit.centers.cpu().numpy()
-        cs.append(torch.from_numpy(c).float())
-        bs.append(torch.from_numpy(neighbour_bandwidths(c, k, n_centers[0])).float())
-    return torch.cat(cs, dim=0), torch.cat(bs, dim=0)
+    def level(pts_dev, k, level_seeds):
+        c = fit_balanced_kmeans(pts_dev, k, level_seeds).centers.cpu().numpy()
+        return torch.from_numpy(c).float(), torch.from_numpy(neighbour_bandwidths(c, k, n_centers[0])).float()
+    return _knots_on_device("balanced_kmeans_knots", "without init_device the initialiser needs the k_means_constrained "
+                            "package", train_coords, n_centers, device, seeding, level, admit=balanced_bounds)

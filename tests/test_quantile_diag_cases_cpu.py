@@ -316,6 +316,13 @@ def _record():
         "too_large": call(S=1 << 16, nT=1 << 15), "empty": call(S=0)}
     rec["need"] = [need, real.stdadk_quantile_diag_workspace_bytes(1 << 16, 1 << 15),
                    real.stdadk_quantile_diag_workspace_bytes(S, 0)]
+    # ---- the wrapper's own check of an accumulator: split_acc with grid_score's slots, not quantile_diag's
+    try:
+        N.quantile_diag(torch.zeros(nT * S, Q), torch.zeros(nT, S), None, None, -1, -1,
+                        torch.zeros(4, N.GRID_SLOTS, dtype=torch.float64), None, None, buf)
+        rec["wrong_split_acc"] = None
+    except RuntimeError as e:
+        rec["wrong_split_acc"] = str(e)
     # ---- the calls of score_grid / quantile_grid
     log = []
 
@@ -383,6 +390,14 @@ def test_entry_point_refusals_return_the_stated_codes():
         assert ref[key][0] == E[code] and word in ref[key][1], (key, ref[key])
     need, too_large, no_slices = rec["need"]
     assert need > 0 and need % 8 == 0 and too_large == 0 and no_slices > 0
+
+
+def test_wrapper_names_itself_when_it_refuses_an_accumulator():
+    """A split_acc of the wrong shape passed to _native.quantile_diag is reported as quantile_diag's, with the shape it
+    wants, and not as grid_score's (the two wrappers once shared a check that named only grid_score)."""
+    msg = _recorded()["wrong_split_acc"]
+    assert msg is not None and msg.startswith("quantile_diag: split_acc must be") and "grid_score" not in msg, msg
+    assert "of shape (4, 32)" in msg and "(4, 16)" in msg, msg
 
 
 @pytest.mark.parametrize("route", ["window", "materialising", "expanded"])
