@@ -759,6 +759,55 @@ int stdadk_quantile_diag_f32(const float *y_pred, const float *z, const uint8_t 
                              void *workspace, size_t workspace_bytes, stdadk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Empirical space-time variograms (added under ABI 10: new entry points only, so STDADK_ABI_VERSION stays 10): has a
+ * model captured the spatial and temporal STRUCTURE of the field?  The semivariograms gamma_z(h, u) of the field,
+ * gamma_p(h, u) of the prediction (a lower sill than gamma_z's: over-smoothing) and gamma_r(h, u) of the residual
+ * (flat: the structure was captured; rising: what is left, and at which range) as one pair reduction on the device
+ * over a WHOLE site x time grid, laid out as stdadk_grid_score_f32's:
+ *   y_pred [nT*S][ldy]  predictions, time-major: row = ti*S + s; p = y_pred[row][col].  NULL = the field only
+ *   z      [nT][S]      the field; split [nT][S] codes 0..3, NULL = all 0
+ *   coords [S][2]       the sites
+ *   edges2_host [n_bins+1]  a HOST array read during the call: the bin edges as SQUARED distances, strictly
+ *                       increasing, edges2[0] >= 0
+ * Entries and pairs.  An entry (t, s) is COUNTED when z[t][s] is finite and its split code is 0..3 (the rule of
+ * stdadk_grid_score_f32).  For lag u = 0 .. n_lags-1 and t = 0 .. nT-1-u a pair is a = (t, i), b = (t + u, j): at
+ * u = 0 the pairs i < j, each unordered pair once and never i = j; at u > 0 every ordered (i, j), i = j included (the
+ * purely temporal variogram at distance 0).  A pair counts in split c when both entries are counted and both carry
+ * code c; pairs across splits count nowhere.  Lags u >= nT have no pairs.
+ * Bins.  d2 = (x_i - x_j)^2 + (y_i - y_j)^2 is formed in float64 from the float32 coordinates, every operation rounded
+ * once (two differences, two products, one sum; no fused multiply-add).  The pair falls in bin b when
+ * edges2[b] <= d2 < edges2[b+1], otherwise it counts nowhere.  No square root is taken: the bin is decided by exact
+ * comparisons, so a host restatement lands every pair in the same bin.
+ * Slots.  acc [4][n_lags][n_bins][4] (split, lag, bin, slot), ASSIGNED: one call is one grid (lags reach across
+ * slices, so the call is not chunked in time):
+ *   N    the count of pairs
+ *   SZ   the sum of (z_a - z_b)^2
+ *   SP   the sum of (p_a - p_b)^2
+ *   SR   the sum of (r_a - r_b)^2, r = z - p formed in double
+ * Each difference and each square is formed in double from operands converted to double.  With y_pred NULL, SP and SR
+ * are written 0.  The semivariogram of a bin is SUM / (2 N).  The order of summation is the kernel's own but fixed
+ * (csrc/variogram.hip: a pair's slices in time order, a tile's pairs of one bin in thread order, a workgroup's tiles in
+ * order, the workgroups in order): every sum is of N non-negative terms, so it is within N 2^-52 of the exact sum,
+ * relative.  No atomics: the same call gives the same bits.  S = 0 or nT = 0 writes zeros.
+ * Errors: n_bins outside 1..64, n_lags outside 1..16, edges2 not strictly increasing or edges2[0] < 0, col outside
+ * 0..ldy-1 when y_pred is given, a NULL acc / workspace / edges2_host (or z / coords of a non-empty grid), an output
+ * (acc, the workspace) that aliases an input or the other output: STDADK_E_ARG; S*nT >= 2^31: STDADK_E_SHAPE; acc or
+ * the workspace not 8-byte aligned: STDADK_E_ALIGN; a workspace below stdadk_variogram_workspace_bytes(S, nT, n_bins,
+ * n_lags) (0 = bad sizes): STDADK_E_WORKSPACE.  No host read of device memory, no allocation, capturable.
+ * ------------------------------------------------------------------------------------------ */
+#define STDADK_VG_N 0
+#define STDADK_VG_SZ 1
+#define STDADK_VG_SP 2
+#define STDADK_VG_SR 3
+#define STDADK_VG_MAX_BINS 64
+#define STDADK_VG_MAX_LAGS 16
+size_t stdadk_variogram_workspace_bytes(int64_t S, int64_t nT, int32_t n_bins, int32_t n_lags);
+int stdadk_variogram_f32(const float *y_pred, int64_t ldy, int32_t col, const float *z, const uint8_t *split,
+                         const float *coords, int64_t S, int64_t nT, const double *edges2_host, int32_t n_bins,
+                         int32_t n_lags, double *acc, void *workspace, size_t workspace_bytes,
+                         stdadk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Knot initialiser (added under ABI 10: new entry points only, nothing existing changes, so STDADK_ABI_VERSION stays
  * 10): ONE EM iteration of the spherical Gaussian mixture in two dimensions behind `spatial_init_method: gmm`
  * (stnf/models/st_interp.py:187-266 fits sklearn.mixture.GaussianMixture(covariance_type='spherical') on the host),

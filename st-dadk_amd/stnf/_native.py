@@ -217,6 +217,10 @@ _SIGNATURES = {
     "stdadk_quantile_diag_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
                                            C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "stdadk_variogram_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "stdadk_variogram_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_int64, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
     "stdadk_gmm_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "stdadk_gmm_em_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -825,6 +829,41 @@ def quantile_diag(y_pred, z, split, taus, lo_col, hi_col, split_acc, site_acc, t
         None if time_acc is None else acc(time_acc, "time_acc", (4, nT, 4)), workspace.data_ptr(), workspace.numel() * 8,
         _stream())
     _check(rc, "stdadk_quantile_diag_f32")
+
+
+# slots per (split, lag, bin) of the float64 accumulator stdadk_variogram_f32 assigns (include/stdadk.h)
+VG_N, VG_SZ, VG_SP, VG_SR, VG_MAX_BINS, VG_MAX_LAGS = 0, 1, 2, 3, 64, 16
+
+
+def variogram_workspace_bytes(S, nT, n_bins, n_lags):
+    return _workspace_bytes("stdadk_variogram_workspace_bytes",
+                            f"bad sizes: grid {S} x {nT} (S*nT must stay below 2^31), n_bins={n_bins} (1..{VG_MAX_BINS}), "
+                            f"n_lags={n_lags} (1..{VG_MAX_LAGS})", S, nT, n_bins, n_lags)
+
+
+def variogram(y_pred, col, z, split, coords, edges2, n_lags, acc, workspace):
+    """stdadk_variogram_f32 on one whole grid: y_pred (nT*S, ld) float32 time-major whose column `col` is the
+    prediction, or None (the field only: SP = SR = 0); z (nT, S) float32 with NaN = no value; split (nT, S) uint8 codes
+    0..3 or None; coords (S, 2) float32; edges2: the n_bins + 1 SQUARED bin edges, host floats.  The pair counts and
+    sums of lags 0 .. n_lags - 1 are ASSIGNED to acc (4, n_lags, n_bins, 4), float64 on the device."""
+    if z.dim() != 2:
+        raise RuntimeError("variogram: z must be (nT, S)")
+    nT, S = z.shape
+    f32 = lambda t, name, shape: _typed("variogram", t, name, torch.float32, shape)      # noqa: E731
+    f64 = lambda t, name, shape: _typed("variogram", t, name, torch.float64, shape)      # noqa: E731
+    ldy = 0
+    if y_pred is not None:
+        if y_pred.dim() != 2 or y_pred.shape[0] != nT * S:
+            raise RuntimeError(f"variogram: y_pred must be (nT*S, ld) = ({nT * S}, ld), got {tuple(y_pred.shape)}")
+        ldy = y_pred.shape[1]
+    edges2 = [float(e) for e in edges2]
+    n_bins = len(edges2) - 1
+    rc = lib().stdadk_variogram_f32(
+        None if y_pred is None else f32(y_pred, "y_pred", None), ldy, int(col), f32(z, "z", (nT, S)),
+        None if split is None else _typed("variogram", split, "split", torch.uint8, (nT, S)),
+        f32(coords, "coords", (S, 2)), S, nT, (C.c_double * len(edges2))(*edges2), n_bins, int(n_lags),
+        f64(acc, "acc", (4, int(n_lags), n_bins, 4)), f64(workspace, "workspace", None), workspace.numel() * 8, _stream())
+    _check(rc, "stdadk_variogram_f32")
 
 
 def gmm_workspace_bytes(n, k):

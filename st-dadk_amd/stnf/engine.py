@@ -17,6 +17,7 @@ import ctypes
 import os
 import weakref
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -1401,6 +1402,50 @@ class Predictor:
         coords, t_values, z, levels, lo, hi = self._grid_args("quantile_grid", coords, t_values, z, split,
                                                               quantile_levels, interval)
         return self._score_chunks(coords, t_values, z, split, levels, lo, hi, max_rows, False, True)[0]
+
+    @torch.no_grad()
+    def variogram_grid(self, coords, t_values, z, split=None, edges=None, n_bins=15, max_dist=None, time_lags=1,
+                       sites=None, metric_col=None):
+        """Empirical space-time variograms of the field, of predict_grid and of their residual on the device
+        (stdadk_variogram_f32): coords (S,2), t_values (T,), z (T,S) float32 with NaN where the field has no value,
+        split (T,S) uint8 codes 0..3 or None (all 0).  The prediction is column `metric_col` (default the median
+        Q // 2).  Bins: `edges` as distances, default `n_bins` equal-width bins up to `max_dist` (default half the
+        diagonal of the bounding box of coords, which costs one small read of coords; pass either to avoid it);
+        `time_lags` L: lags 0 .. L - 1 in slices; `sites`: None = every site up to 4 096, beyond that 4 096 drawn by a
+        RandomState(0) of its own; 'all'; or an index array (utils.variogram.select_sites).
+        Predicts on coords[sites] only, chunk by chunk into one (T, S', Q) buffer -- lags reach across slices, so the
+        reduction is ONE library call on the whole buffer -- and reads the sums back once.  Returns
+        utils.variogram.variogram_curves' dict (count, gamma_z, gamma_pred, gamma_resid (4, L, B), edges, lags) plus
+        `acc` (4, L, B, 4), the sums themselves, and `sites`."""
+        from .utils import variogram as V
+        coords, t_values, z, _, _, _ = self._grid_args("variogram_grid", coords, t_values, z, split, None, None)
+        S, T = coords.shape[0], t_values.numel()
+        Q = self.model.output_dim
+        col = Q // 2 if metric_col is None else int(metric_col)
+        if not 0 <= col < Q:
+            raise ValueError(f"variogram_grid: metric_col={col} outside 0..{Q - 1}")
+        L = V._check_lags(time_lags)
+        if edges is None:
+            edges = V.variogram_edges(coords.cpu().numpy(), n_bins, max_dist)
+        edges, e2 = V._check_edges(edges)
+        idx = V.select_sites(S, sites)
+        if len(idx) == S and np.array_equal(idx, np.arange(S)):
+            cs, zs, ss = coords, z, split
+        else:
+            it = torch.from_numpy(idx).to(self.dev)
+            cs, zs = coords[it].contiguous(), z[:, it].contiguous()
+            ss = None if split is None else split[:, it].contiguous()
+        if ss is not None:
+            ss = ss.contiguous()
+        Sv = cs.shape[0]
+        buf = self._reused("vg_y", (T * Sv, Q))
+        if Sv > 0 and T > 0:
+            for _ in self._grid_chunks(cs, t_values, None, lambda t0, n: buf[t0 * Sv:(t0 + n) * Sv], self._reused):
+                pass
+        acc = V.device_variogram(buf, col, zs, ss, cs, e2, L, scratch=self._reused)      # the ONE host read
+        out = V.variogram_curves(acc, edges, np.arange(L))
+        out["acc"], out["sites"] = acc, idx
+        return out
 
     @torch.no_grad()
     def predict(self, coords, t, out=None):

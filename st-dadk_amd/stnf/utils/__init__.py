@@ -1,9 +1,11 @@
 """Host-side helpers of the training driver: seeding, error metrics, the EMA shadow.  Same public names
-as the reference package (its stnf/utils/__init__.py:4-14); only `grid_scores` on a device model reaches the device library."""
+as the reference package (its stnf/utils/__init__.py:4-14); only `grid_scores` on a device model and
+`field_variogram` on a HIP device reach the device library."""
 from . import ema as _ema
 from . import metrics as _metrics
 from . import predictions as _predictions
 from . import seed as _seed
+from . import variogram as _variogram
 
 set_seed = _seed.set_seed
 compute_metrics = _metrics.compute_metrics
@@ -12,5 +14,7 @@ print_metrics = _metrics.print_metrics
 ModelEMA = _ema.ModelEMA
 grid_scores = _predictions.grid_scores
 save_grid_scores_npz = _predictions.save_grid_scores_npz
+field_variogram = _variogram.field_variogram
+variogram_curves = _variogram.variogram_curves
 
 __all__ = sorted(n for n in dir() if not n.startswith('_'))

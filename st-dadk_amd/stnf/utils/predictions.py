@@ -249,7 +249,14 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
     With `quantile_diagnostics: true` in the config and a model that has quantile levels, the dict gains `quantile`
     (see quantile_diagnostics): reliability, PIT histogram, crossing rates and depths, CRPS per split, and the per-site
     and per-time CRPS / crossing / coverage maps.  On the device that is one more reduction of the same chunk buffer
-    (one forward per chunk) and still one host read; without the key nothing changes."""
+    (one forward per chunk) and still one host read; without the key nothing changes.
+    With `variogram: true` the dict gains `variogram`: per split name (other, train, valid, test) the empirical
+    space-time semivariograms count, gamma_z, gamma_pred, gamma_resid, each (L, B), of the field, of the metric column
+    and of their residual, with `edges` and `lags` (utils.variogram).  Keys: `variogram_bins` (15),
+    `variogram_max_dist` (half the diagonal of the coordinates' bounding box), `variogram_time_lags` (1: lag 0 only),
+    `variogram_sites` (every site up to 4 096, then 4 096 drawn by a RandomState(0) of its own; 'all'; an index array).
+    On the device that is one more pass over the chosen sites, one stdadk_variogram_f32 call and one more host read;
+    without the key nothing changes."""
     if getattr(model, "p", 0) != 0:
         raise ValueError("grid_scores: the dense grid has no covariates (p must be 0)")
     z = np.asarray(z_full.detach().cpu() if torch.is_tensor(z_full) else z_full)
@@ -290,23 +297,36 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
     if tuple(c.shape) != (S, 2):
         raise ValueError(f"grid_scores: coords must be ({S}, 2), got {tuple(c.shape)}")
     tv = _grid_times(T)
+    vg = None
+    if config.get("variogram", False):
+        from . import variogram as V
+        vg_lags = V._check_lags(config.get("variogram_time_lags", 1))
+        vg_edges, vg_e2 = V._check_edges(V.variogram_edges(c.cpu().numpy(), config.get("variogram_bins", 15),
+                                                           config.get("variogram_max_dist")))
+        vg_sites = V.select_sites(S, config.get("variogram_sites"))
     was_training = model.training
     model.eval()
     try:
         if dev.type == "cuda":
             from ..engine import Predictor
-            accs = Predictor(model).score_grid(c, tv.to(dev), torch.from_numpy(z.astype(np.float32)).to(dev),
-                                               torch.from_numpy(code).to(dev), quantile_levels=levels,
-                                               interval=interval, max_rows=max_rows, quantile=diag)
+            pr, zt, ct = Predictor(model), torch.from_numpy(z.astype(np.float32)).to(dev), torch.from_numpy(code).to(dev)
+            accs = pr.score_grid(c, tv.to(dev), zt, ct, quantile_levels=levels, interval=interval, max_rows=max_rows,
+                                 quantile=diag)
             flat = torch.cat([a.reshape(-1) for a in accs]).cpu().numpy()              # the ONE host read
             cuts = np.cumsum([a.numel() for a in accs])[:-1]
             sums = [part.reshape(a.shape) for part, a in zip(np.split(flat, cuts), accs)]
+            if config.get("variogram", False):
+                vg = pr.variogram_grid(c, tv.to(dev), zt, ct, edges=vg_edges, time_lags=vg_lags,
+                                       sites=vg_sites)["acc"]                          # (and the variogram's own)
         else:
             pred = torch.stack([model(torch.zeros(S, 0), c, torch.full((S, 1), float(tv[i]))) for i in range(T)])
             pred = pred.double().numpy()
             sums = list(_grid_sums_host(pred, z, code, levels, lo, hi))
             if diag:
                 sums += _quantile_sums_host(pred, z, code, levels, lo, hi)
+            if config.get("variogram", False):
+                vg = V.variogram_sums_host(pred[:, vg_sites, Q // 2].astype(np.float32), z[:, vg_sites].astype(np.float32),
+                                           code[:, vg_sites], c.numpy()[vg_sites], vg_e2, vg_lags)
         split_acc, site_acc, time_acc = sums[:3]
     finally:
         model.train(was_training)
@@ -320,14 +340,20 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
         out[f"{name}_mse_by_split"] = _ratio(acc[:, :, 0], acc[:, :, 2])
     if diag:
         out["quantile"] = quantile_diagnostics(*sums[3:], levels, interval is not None)
+    if vg is not None:
+        curves = V.variogram_curves(vg, vg_edges, np.arange(vg_lags))
+        out["variogram"] = {SPLIT_NAMES[k]: dict({name: curves[name][k] for name in
+                                                  ("count", "gamma_z", "gamma_pred", "gamma_resid")},
+                                                 edges=curves["edges"], lags=curves["lags"]) for k in (1, 2, 3, 0)}
     return out
 
 
 def save_grid_scores_npz(output_dir, scores):
     """Writes `<output_dir>/grid_scores.npz` from the dict of grid_scores and returns its path: the per-site and
     per-time arrays under their own names, every split metric as the 0-d array `splits/<split>/<metric>`, and the
-    quantile diagnostics, when present, as `quantile/<split>/<metric>` and `quantile/<map>`."""
-    arrs = {k: np.asarray(v) for k, v in scores.items() if k not in ("splits", "quantile")}
+    quantile diagnostics, when present, as `quantile/<split>/<metric>` and `quantile/<map>`, and the variograms, when
+    present, as `variogram/<split>/<name>`."""
+    arrs = {k: np.asarray(v) for k, v in scores.items() if k not in ("splits", "quantile", "variogram")}
     for name, metrics in scores["splits"].items():
         for k, v in metrics.items():
             arrs[f"splits/{name}/{k}"] = np.asarray(v)
@@ -338,6 +364,9 @@ def save_grid_scores_npz(output_dir, scores):
                 arrs[f"quantile/{name}/{k}"] = np.asarray(w)
         else:
             arrs[f"quantile/{name}"] = np.asarray(v)
+    for name, v in scores.get("variogram", {}).items():
+        for k, w in v.items():
+            arrs[f"variogram/{name}/{k}"] = np.asarray(w)
     os.makedirs(output_dir, exist_ok=True)
     path = os.path.join(str(output_dir), "grid_scores.npz")
     np.savez(path, **arrs)
