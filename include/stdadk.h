@@ -808,6 +808,86 @@ int stdadk_variogram_f32(const float *y_pred, int64_t ldy, int32_t col, const fl
                          stdadk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Basis diagnostics (added under ABI 10: new entry points only, so STDADK_ABI_VERSION stays 10): what did the BASIS
+ * do?  How much training data sits in each knot's support, which sites does no knot of a level cover, which basis
+ * functions did group lasso switch off.  stdadk_basis_diag_f32 is one sites x knots pair reduction on the device over
+ * the LIVE knot tables; stdadk_group_norms_f32 gives the first Linear's group norms the sparsity analysis starts from.
+ *   s_centers [Ks][2], s_bw [Ks]   float32, device: the tables as stdadk_basis_desc carries them (bandwidths, not
+ *                       their logarithms)
+ *   basis               STDADK_BASIS_*
+ *   level_sizes_host [n_levels]  a HOST array read during the call: the knot count of every level, each >= 0, summing
+ *                       to Ks; 1..STDADK_MAX_LEVELS levels.  Level l holds the knots after those of levels < l: grid
+ *                       and scattered tables alike
+ *   coords [S][2]       float32, device: the sites
+ *   w [S]               float64 or NULL (= all 1): the site's weight, e.g. its number of training observations
+ *   v [S]               float64 or NULL: a site value, e.g. its test MSE
+ *   rho                 the support radius in units of the scaled radius r, finite and > 0
+ * Pairs.  For site i and knot k, d2 = (x_i - cx_k)^2 + (y_i - cy_k)^2 is formed in float64 from the float32 operands,
+ * every operation rounded once (two differences, two products, one sum; no fused multiply-add).  With cal the double
+ * literal 1.0 (Wendland) / 0.223477 (Gaussian) / 0.654714 (triangular): den_k = (double)bw_k * cal,
+ * s_k = den_k * rho, R2_k = s_k * s_k, each rounded once.  The pair is IN SUPPORT iff d2 < R2_k: an exact comparison,
+ * so a host restatement makes the same decision for every pair (a NaN d2 is in no support and is no minimum).  For a
+ * pair in support r = sqrt(d2) / den_k and phi(r) is formed in double with the formulas of csrc/basis.h:
+ *   Wendland    r' = min(r, 1), om = 1 - r', om2 = om om, phi = (om2 om2 om2) ((35 r' + 18) r' + 3) / 3
+ *   Gaussian    exp(-0.5 r r)
+ *   triangular  max(1 - r, 0)
+ * Pairs out of support contribute nothing: for the Gaussian kind the tail beyond rho is dropped by contract.
+ * Outputs, float64, both ASSIGNED:
+ *   knot_acc [Ks][7], over the sites whose w_i is finite and > 0 (all of them without w):
+ *     N      the count of such sites in support
+ *     W      the sum of w
+ *     SPHI   the sum of w phi
+ *     SPHI2  the sum of (w phi) phi
+ *     SV     the sum of (w phi) v over the sites in support with a finite v
+ *     WV     the sum of w phi over the same sites: the phi-weighted mean of v around the knot is SV / WV
+ *     NEAR2  the minimum d2 to any such site, in support or not; +inf when there is none
+ *     Without v, SV = WV = 0.
+ *   site_acc [S][n_levels][3], for EVERY site whatever its weight, per level:
+ *     COVER  the count of the level's knots whose support holds the site
+ *     SPHI   the sum of phi over them
+ *     NEAR2  the minimum d2 to a knot of the level; +inf for a level without knots
+ * The order of summation is the kernel's own but fixed by the sizes alone (csrc/basis_diag.hip: of a knot's sites in a
+ * span each of four waves adds every fourth sub-chunk of 64 in site order, then the waves in order, then the spans in
+ * order; of a site's knots of a level each wave adds its quarter of every chunk of 256 in knot order, then the waves
+ * in order): every sum is of n non-negative terms (v aside), so it is within n 2^-52 of the exact sum, relative.  No atomics: the same call gives the
+ * same bits.  Ks = 0 writes the sites' neutral rows (0, 0, +inf), S = 0 the knots' (zeros, NEAR2 = +inf).
+ * Errors: S or Ks outside 0..2^31-1, an unknown basis, n_levels outside 1..STDADK_MAX_LEVELS, level sizes that are
+ * negative or do not sum to Ks, rho not finite or <= 0, a NULL level_sizes_host / workspace (or s_centers / s_bw /
+ * knot_acc with Ks > 0, coords / site_acc with S > 0), an output (knot_acc, site_acc, the workspace) that aliases an
+ * input or another output: STDADK_E_ARG; knot_acc, site_acc, w, v or the workspace not 8-byte aligned: STDADK_E_ALIGN; a
+ * workspace below stdadk_basis_diag_workspace_bytes(S, Ks) (0 = bad sizes): STDADK_E_WORKSPACE.  No host read of device
+ * memory, no allocation, capturable.
+ *
+ * stdadk_group_norms_f32: for the basis functions col0 .. col0 + n - 1 of the first Linear the float64 sum of squares
+ * of the function's group of H weights, ASSIGNED to out [n] (the norm is its square root; the spatial and the temporal
+ * block are adjacent columns after the p covariates, so one call covers both).  transposed = 0: W0 is (H, D) row-major
+ * with row stride ld >= col0 + n and the group is a COLUMN; transposed = 1 (the meaning of STDADK_FLAG_W0_T): W0 is
+ * (D, H) row-major with row stride ld >= H and the group is a ROW.  Each weight is converted to double and squared
+ * there; the order is fixed (a column's rows in order; a row's terms h, h + 64, ... per lane in order, the 64 lanes
+ * by a fixed tree).  n = 0 does nothing.  Errors: H < 1, col0 < 0, n < 0, col0 + n >= 2^31, transposed not 0 / 1, an
+ * ld shorter than a row, a NULL pointer, out inside W0: STDADK_E_ARG; out not 8-byte aligned: STDADK_E_ALIGN.
+ * ------------------------------------------------------------------------------------------ */
+#define STDADK_BD_KNOT_SLOTS 7
+#define STDADK_BD_K_N 0
+#define STDADK_BD_K_W 1
+#define STDADK_BD_K_SPHI 2
+#define STDADK_BD_K_SPHI2 3
+#define STDADK_BD_K_SV 4
+#define STDADK_BD_K_WV 5
+#define STDADK_BD_K_NEAR2 6
+#define STDADK_BD_SITE_SLOTS 3
+#define STDADK_BD_S_COVER 0
+#define STDADK_BD_S_SPHI 1
+#define STDADK_BD_S_NEAR2 2
+size_t stdadk_basis_diag_workspace_bytes(int64_t S, int64_t Ks);
+int stdadk_basis_diag_f32(const float *s_centers, const float *s_bw, int64_t Ks, int32_t basis,
+                          const int64_t *level_sizes_host, int32_t n_levels, const float *coords, int64_t S,
+                          const double *w, const double *v, double rho, double *knot_acc, double *site_acc,
+                          void *workspace, size_t workspace_bytes, stdadk_stream_t stream);
+int stdadk_group_norms_f32(const float *W0, int64_t ld, int32_t transposed, int32_t H, int64_t col0, int64_t n,
+                           double *out, stdadk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Knot initialiser (added under ABI 10: new entry points only, nothing existing changes, so STDADK_ABI_VERSION stays
  * 10): ONE EM iteration of the spherical Gaussian mixture in two dimensions behind `spatial_init_method: gmm`
  * (stnf/models/st_interp.py:187-266 fits sklearn.mixture.GaussianMixture(covariance_type='spherical') on the host),

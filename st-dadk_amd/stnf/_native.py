@@ -221,6 +221,12 @@ _SIGNATURES = {
     "stdadk_variogram_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_int64, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_size_t, C.c_void_p]),
+    "stdadk_basis_diag_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "stdadk_basis_diag_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_int32,
+                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "stdadk_group_norms_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                         C.c_void_p]),
     "stdadk_gmm_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "stdadk_gmm_em_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -864,6 +870,53 @@ def variogram(y_pred, col, z, split, coords, edges2, n_lags, acc, workspace):
         f32(coords, "coords", (S, 2)), S, nT, (C.c_double * len(edges2))(*edges2), n_bins, int(n_lags),
         f64(acc, "acc", (4, int(n_lags), n_bins, 4)), f64(workspace, "workspace", None), workspace.numel() * 8, _stream())
     _check(rc, "stdadk_variogram_f32")
+
+
+# slots of the float64 accumulators stdadk_basis_diag_f32 assigns (include/stdadk.h): per knot and per (site, level)
+BD_K_N, BD_K_W, BD_K_SPHI, BD_K_SPHI2, BD_K_SV, BD_K_WV, BD_K_NEAR2, BD_KNOT_SLOTS = 0, 1, 2, 3, 4, 5, 6, 7
+BD_S_COVER, BD_S_SPHI, BD_S_NEAR2, BD_SITE_SLOTS = 0, 1, 2, 3
+MAX_LEVELS = 8
+
+
+def basis_diag_workspace_bytes(S, Ks):
+    return _workspace_bytes("stdadk_basis_diag_workspace_bytes", f"bad sizes: S={S}, Ks={Ks} (each 0 .. 2^31-1)", S, Ks)
+
+
+def basis_diag(s_centers, s_bw, basis, level_sizes, coords, w, v, rho, knot_acc, site_acc, workspace):
+    """stdadk_basis_diag_f32: the sites x knots pair reduction on the knot tables s_centers (Ks, 2), s_bw (Ks,) float32
+    (bandwidths, not their logarithms) of kind `basis` ('wendland' / 'gaussian' / 'triangular'), `level_sizes` the knot
+    counts per level (host integers summing to Ks), coords (S, 2) float32, w / v (S,) float64 or None, `rho` the
+    support radius in units of the scaled radius.  ASSIGNS knot_acc (Ks, 7) and site_acc (S, n_levels, 3), float64 on
+    the device."""
+    f32 = lambda t, name, shape: _typed("basis_diag", t, name, torch.float32, shape)      # noqa: E731
+    f64 = lambda t, name, shape: _typed("basis_diag", t, name, torch.float64, shape)      # noqa: E731
+    if s_centers.dim() != 2 or coords.dim() != 2:
+        raise RuntimeError("basis_diag: s_centers must be (Ks, 2) and coords (S, 2)")
+    Ks, S = s_centers.shape[0], coords.shape[0]
+    sizes = [int(n) for n in level_sizes]
+    L = len(sizes)
+    rc = lib().stdadk_basis_diag_f32(
+        f32(s_centers, "s_centers", (Ks, 2)), f32(s_bw, "s_bw", (Ks,)), Ks, BASIS_KIND[basis],
+        (C.c_int64 * max(L, 1))(*sizes), L, f32(coords, "coords", (S, 2)), S,
+        None if w is None else f64(w, "w", (S,)), None if v is None else f64(v, "v", (S,)), float(rho),
+        f64(knot_acc, "knot_acc", (Ks, BD_KNOT_SLOTS)), f64(site_acc, "site_acc", (S, L, BD_SITE_SLOTS)),
+        f64(workspace, "workspace", None), workspace.numel() * 8, _stream())
+    _check(rc, "stdadk_basis_diag_f32")
+
+
+def group_norms(W0, transposed, H, col0, n, out):
+    """stdadk_group_norms_f32: out (n,) float64 = the sum of squares of the first Linear's group of H weights of the
+    basis functions col0 .. col0 + n - 1.  W0: the weight as stored, float32 with unit column stride: (H, D) with
+    transposed False (a group is a column), (D, H) with transposed True (a group is a row); its row stride is ld."""
+    if W0.dim() != 2 or (W0.stride(1) != 1 and W0.shape[1] > 1) or W0.dtype != torch.float32 or not _on_device(W0):
+        raise RuntimeError("group_norms: W0 must be a 2-D float32 tensor with unit column stride on the device")
+    if W0.shape[1 if transposed else 0] != H or not 0 <= col0 <= col0 + n <= W0.shape[0 if transposed else 1]:
+        raise RuntimeError(f"group_norms: columns {col0}..{col0 + n - 1} of H={H} do not fit W0 {tuple(W0.shape)} "
+                           f"(transposed={bool(transposed)})")
+    ld = W0.stride(0) if W0.shape[0] > 1 else max(W0.stride(0), W0.shape[1])      # (one row: its stride means nothing)
+    rc = lib().stdadk_group_norms_f32(W0.data_ptr(), ld, int(bool(transposed)), int(H), int(col0), int(n),
+                                      _typed("group_norms", out, "out", torch.float64, (int(n),)), _stream())
+    _check(rc, "stdadk_group_norms_f32")
 
 
 def gmm_workspace_bytes(n, k):

@@ -1448,6 +1448,45 @@ class Predictor:
         return out
 
     @torch.no_grad()
+    def basis_diagnostics(self, coords, weights=None, site_value=None, rho=None):
+        """What the basis did at the sites `coords` (S,2), on the device: stdadk_basis_diag_f32 on the LIVE knot tables
+        (the parameters this predictor predicts with: learnable centres and bandwidths as they are now, an EMA state
+        that was swapped in) and stdadk_group_norms_f32 on the first Linear as it is stored, either layout.  `weights`
+        (S,) the sites' weights, e.g. their training observations (None: all 1), `site_value` (S,) a site value such as
+        the test MSE (None: none), both taken as float64; `rho` the support radius in units of the scaled radius
+        (default utils.basis_diag.default_rho: 1 for Wendland and triangular, 1 / cal for the Gaussian).
+        Two library calls, scratch reused, ONE host read.  Returns host arrays: knot_acc (Ks, 7), site_acc
+        (S, n_levels, 3) (slots in include/stdadk.h), sumsq (Ks + Kt,) the sums of squares of the spatial then the
+        temporal groups, and the tables that were read, centers (Ks, 2) and bandwidths (Ks,) float32, plus rho and
+        level_sizes; utils.basis_diag.summarize turns them into the diagnostics."""
+        from .utils import basis_diag as BD
+        self._refresh()
+        m, sb = self.model, self.model.spatial_basis
+        coords = coords.contiguous().float()
+        S, Ks, Kt = coords.shape[0], m.k_spatial, m.k_temporal
+        sizes = list(sb.n_centers)
+        rho = BD.default_rho(m.spatial_basis_function) if rho is None else float(rho)
+        f64 = lambda x: None if x is None else x.to(self.dev, torch.float64).contiguous().view(-1)      # noqa: E731
+        centers, bw = sb.centers.detach().contiguous(), sb.bandwidths.detach().contiguous()
+        knot = self._reused("bd_knot", (Ks, N.BD_KNOT_SLOTS), torch.float64)
+        site = self._reused("bd_site", (S, len(sizes), N.BD_SITE_SLOTS), torch.float64)
+        ws = self._reused("bd_ws", (N.basis_diag_workspace_bytes(S, Ks) // 8,), torch.float64)
+        N.basis_diag(centers, bw, m.spatial_basis_function, sizes, coords, f64(weights), f64(site_value), rho, knot, site,
+                     ws)
+        w0 = m._body[0].weight.detach()
+        transposed = not w0.is_contiguous() and w0.t().is_contiguous()       # engine-owned (in,out) storage
+        if not transposed and not w0.is_contiguous():
+            w0 = w0.contiguous()
+        sumsq = self._reused("bd_sumsq", (Ks + Kt,), torch.float64)
+        N.group_norms(w0.t() if transposed else w0, transposed, w0.shape[0], m.p, Ks + Kt, sumsq)
+        flat = torch.cat([knot.view(-1), site.view(-1), sumsq, centers.view(-1).double(), bw.double()]).cpu().numpy()
+        cuts = np.cumsum([knot.numel(), site.numel(), sumsq.numel(), centers.numel()])
+        k_h, s_h, q_h, c_h, b_h = np.split(flat, cuts)                       # the ONE host read
+        return {"knot_acc": k_h.reshape(Ks, N.BD_KNOT_SLOTS), "site_acc": s_h.reshape(S, len(sizes), N.BD_SITE_SLOTS),
+                "sumsq": q_h, "centers": c_h.astype(np.float32).reshape(Ks, 2), "bandwidths": b_h.astype(np.float32),
+                "rho": rho, "level_sizes": sizes}
+
+    @torch.no_grad()
     def predict(self, coords, t, out=None):
         """coords (N,2), t (N,) or (N,1) on the device -> (N,Q) (written into `out` when given)."""
         if self.model.p != 0:

@@ -1,6 +1,7 @@
 """Host-side helpers of the training driver: seeding, error metrics, the EMA shadow.  Same public names
-as the reference package (its stnf/utils/__init__.py:4-14); only `grid_scores` on a device model and
-`field_variogram` on a HIP device reach the device library."""
+as the reference package (its stnf/utils/__init__.py:4-14); only `grid_scores` and `basis_diagnostics` on a device
+model and `field_variogram` on a HIP device reach the device library."""
+from . import basis_diag as _basis_diag
 from . import ema as _ema
 from . import metrics as _metrics
 from . import predictions as _predictions
@@ -16,5 +17,7 @@ grid_scores = _predictions.grid_scores
 save_grid_scores_npz = _predictions.save_grid_scores_npz
 field_variogram = _variogram.field_variogram
 variogram_curves = _variogram.variogram_curves
+basis_diagnostics = _basis_diag.basis_diagnostics
+save_basis_info_npz = _basis_diag.save_basis_info_npz
 
 __all__ = sorted(n for n in dir() if not n.startswith('_'))

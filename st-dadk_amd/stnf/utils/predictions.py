@@ -256,7 +256,11 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
     `variogram_max_dist` (half the diagonal of the coordinates' bounding box), `variogram_time_lags` (1: lag 0 only),
     `variogram_sites` (every site up to 4 096, then 4 096 drawn by a RandomState(0) of its own; 'all'; an index array).
     On the device that is one more pass over the chosen sites, one stdadk_variogram_f32 call and one more host read;
-    without the key nothing changes."""
+    without the key nothing changes.
+    With `basis_diagnostics: true` the dict gains `basis`: utils.basis_diag.basis_diagnostics' dict at the same sites,
+    the site weights being the training observations per site (`train_mask.sum(0)`) and the site value the test split's
+    per-site MSE computed here; `basis_rho` overrides the support radius.  On the device that is two more library calls
+    and one more host read; without the key nothing changes."""
     if getattr(model, "p", 0) != 0:
         raise ValueError("grid_scores: the dense grid has no covariates (p must be 0)")
     z = np.asarray(z_full.detach().cpu() if torch.is_tensor(z_full) else z_full)
@@ -306,6 +310,7 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
         vg_sites = V.select_sites(S, config.get("variogram_sites"))
     was_training = model.training
     model.eval()
+    pr = None
     try:
         if dev.type == "cuda":
             from ..engine import Predictor
@@ -345,6 +350,11 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
         out["variogram"] = {SPLIT_NAMES[k]: dict({name: curves[name][k] for name in
                                                   ("count", "gamma_z", "gamma_pred", "gamma_resid")},
                                                  edges=curves["edges"], lags=curves["lags"]) for k in (1, 2, 3, 0)}
+    if config.get("basis_diagnostics", False):
+        from .basis_diag import basis_diagnostics
+        out["basis"] = basis_diagnostics(model, c, train_mask=train_mask, config=config,
+                                         site_value=out["site_mse_by_split"][3], rho=config.get("basis_rho"),
+                                         predictor=pr)
     return out
 
 
@@ -352,8 +362,8 @@ def save_grid_scores_npz(output_dir, scores):
     """Writes `<output_dir>/grid_scores.npz` from the dict of grid_scores and returns its path: the per-site and
     per-time arrays under their own names, every split metric as the 0-d array `splits/<split>/<metric>`, and the
     quantile diagnostics, when present, as `quantile/<split>/<metric>` and `quantile/<map>`, and the variograms, when
-    present, as `variogram/<split>/<name>`."""
-    arrs = {k: np.asarray(v) for k, v in scores.items() if k not in ("splits", "quantile", "variogram")}
+    present, as `variogram/<split>/<name>`, and the basis diagnostics, when present, as `basis/<name>`."""
+    arrs = {k: np.asarray(v) for k, v in scores.items() if k not in ("splits", "quantile", "variogram", "basis")}
     for name, metrics in scores["splits"].items():
         for k, v in metrics.items():
             arrs[f"splits/{name}/{k}"] = np.asarray(v)
@@ -367,6 +377,8 @@ def save_grid_scores_npz(output_dir, scores):
     for name, v in scores.get("variogram", {}).items():
         for k, w in v.items():
             arrs[f"variogram/{name}/{k}"] = np.asarray(w)
+    for name, v in scores.get("basis", {}).items():
+        arrs[f"basis/{name}"] = np.asarray(v)
     os.makedirs(output_dir, exist_ok=True)
     path = os.path.join(str(output_dir), "grid_scores.npz")
     np.savez(path, **arrs)

@@ -56,7 +56,9 @@ def steps(m, B, eng_kw=None, q_cols=1, indexed=True):
         pr = Predictor(m, chunk=1024)
         pr.predict(c, t)
         pr.predict_grid(c[:37], torch.linspace(0, 1, 5))
-        calls += 2
+        # the basis diagnostics on the live tables and the first layer as stored (either layout): both side calls
+        pr.basis_diagnostics(c[:37], torch.ones(37, dtype=torch.float64), None)
+        calls += 3
     return eng
 
 

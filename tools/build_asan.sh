@@ -10,7 +10,7 @@ mkdir -p ../lib obj_asan
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="-O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -fsanitize=address,undefined -fno-gpu-sanitize -fno-sanitize-recover=undefined -fno-omit-frame-pointer"
 pids=()
-for f in rbf_build gemm_f32 mlp optim window tail loss knots step_finish fused_step dw_all sparsity eval grid_score quantile_diag variogram gmm kmeans kmeanspp; do
+for f in rbf_build gemm_f32 mlp optim window tail loss knots step_finish fused_step dw_all sparsity eval grid_score quantile_diag variogram basis_diag gmm kmeans kmeanspp; do
   if [ ! -f obj_asan/$f.o ] || [ -n "$(find . ../../include -maxdepth 1 \( -name '*.h' -o -name "$f.hip" \) -newer obj_asan/$f.o)" ]; then
     $HIPCC $FLAGS -c $f.hip -o obj_asan/$f.o &
     pids+=($!)
