@@ -888,6 +888,81 @@ int stdadk_group_norms_f32(const float *W0, int64_t ld, int32_t transposed, int3
                            double *out, stdadk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Split-conformal calibration (added under ABI 10: new entry points only, so STDADK_ABI_VERSION stays 10): the
+ * conformity scores of a site x time grid as an ordered compaction, and exact order statistics of them without a sort.
+ * Shifting a model's quantiles by one order statistic of the calibration split's scores gives finite-sample marginal
+ * coverage whatever the model learned (conformalized quantile regression; the Python face is stnf.calibration).
+ *
+ * stdadk_conformal_scores_f32: one CHUNK of nT consecutive time slices, laid out as stdadk_grid_score_f32's:
+ *   y_pred [nT*S][Q]  predictions, time-major: row = ti*S + s; finite by contract
+ *   z      [nT][S]    the field's slice; a non-finite entry is no member of any segment
+ *   split  [nT][S]    codes 0..255, NULL = all 0 (a validation set is then passed as nT = 1, S = N)
+ *   cols_host [C][3]  a HOST array of int32 read during the call, 1 <= C <= STDADK_CONFORMAL_MAX_COLS: per score column
+ *                     (kind, col_a, col_b), col_b read for CQR only.  With p = the row's predictions, every operation
+ *                     in float32 and rounded once (the bits of numpy float32 arithmetic):
+ *                       STDADK_CONFORMAL_RESID   z - p[col_a]
+ *                       STDADK_CONFORMAL_CQR     max(p[col_a] - z, z - p[col_b])
+ *                       STDADK_CONFORMAL_ABS     |z - p[col_a]|
+ *   codes_host [G]    a HOST array of int32, 1 <= G <= STDADK_CONFORMAL_MAX_SEGMENTS: the split code of every segment
+ *   scores [G][C][cap]  float32: segment g, column c holds its scores from index 0 on
+ *   count  [G]        int64, device: the members segment g holds already.  READ as the first append position (a negative
+ *                     value as 0) and ADVANCED by the chunk's members at the end of the call, saturating at cap
+ *   overflow [G]      int32, device: SET to 1 when the chunk's members did not all fit; otherwise not touched
+ * An entry is a MEMBER of segment g when z is finite and split == codes_host[g].  Members are appended in time-major,
+ * then site order -- numpy's scores[mask] order -- so chunked calls over a grid leave the bytes of one call.  A member
+ * whose position is >= cap is dropped: nothing is ever written outside a segment, and what was written is the correct
+ * prefix.  Positions come from per-run member counts (a run is 1024 consecutive rows), an exclusive scan over the
+ * chunk's runs and ballot ranks inside a run: no atomics, the same call gives the same bytes.
+ * Workspace: stdadk_conformal_scores_workspace_bytes(S, nT) (0 = bad sizes), 8-byte aligned.  S = 0 or nT = 0 does
+ * nothing.  Errors: a negative size or capacity, Q outside 1..STDADK_MAX_Q, C or G outside their range, an unknown kind,
+ * a prediction column outside 0..Q-1, a code outside 0..255, a NULL pointer: STDADK_E_ARG; S*nT or cap >= 2^31:
+ * STDADK_E_SHAPE; count not 8-byte, scores or overflow not 4-byte aligned, the workspace not 8-byte aligned:
+ * STDADK_E_ALIGN; a workspace too small: STDADK_E_WORKSPACE.  No host read of device memory, no allocation, capturable.
+ *
+ * stdadk_select_f32: exact order statistics of columns of finite float32 values.
+ *   keys              device: column c is keys[c*stride .. c*stride + n - 1], 1 <= C <= STDADK_CONFORMAL_MAX_COLS
+ *   n_dev             int64, device: n, the SAME for every column (e.g. count[g] of the scores call: no host read in
+ *                     between).  n_max: the host's bound on it, n_max <= stride, n_max < 2^31; a device value outside
+ *                     0..n_max is read as the nearer end
+ *   sel_col_host, sel_rank_host, sel_beta_host [n_sel]  HOST arrays, 1 <= n_sel <= STDADK_SELECT_MAX: the column; the
+ *                     0-based rank, or a negative rank and a level beta in [0, 1] (sel_beta_host may be NULL when every
+ *                     rank is given).  With a level the 1-based rank is k = ceil((n + 1) * beta), that one product
+ *                     and the ceiling evaluated in IEEE double, k below 1 taken as 1; the 0-based rank is k - 1
+ *   value [n_sel]     float32: the rank-th smallest value of the column (0-based; equal values count as often as they
+ *                     occur; -0 is returned as +0)
+ *   rank_used [n_sel] int64: the 0-based rank that was used
+ * A rank >= n (k > n, n = 0) gives value = +inf and rank_used = -1: conformal's "not enough calibration data".
+ * Method: radix select.  A value's key is its bits with -0 canonicalised to +0, all bits flipped for negatives and the
+ * sign bit flipped otherwise: unsigned order = float order.  Four passes of 8 bits, most significant first.  A pass
+ * reads the data once for ALL selections of all columns: per workgroup one set of histograms (16 x 256 x uint32) in LDS,
+ * integer LDS atomics on the keys whose higher digits match the selection's prefix, integer global atomics to merge
+ * the workgroups; then one wave per selection picks the bin where the cumulative count crosses the remaining rank and
+ * clears the histogram.  After the last pass the prefix is the key of the value; the data is never searched for it.
+ * Integer counts do not depend on the order of arrival: the same call gives the same bits.
+ * Workspace: stdadk_select_workspace_bytes(n_sel) (0 = n_sel out of range), 8-byte aligned.  Errors: n_sel or C out of
+ * range, a column outside 0..C-1, a negative rank without a level in [0, 1], a negative n_max or stride, a NULL
+ * pointer: STDADK_E_ARG; n_max >= 2^31 or stride < n_max: STDADK_E_SHAPE; n_dev or rank_used not 8-byte, keys or value not
+ * 4-byte aligned, the workspace not 8-byte aligned: STDADK_E_ALIGN; a workspace too small: STDADK_E_WORKSPACE.  No host
+ * read of device memory, no allocation, capturable.
+ * ------------------------------------------------------------------------------------------ */
+#define STDADK_CONFORMAL_RESID 0
+#define STDADK_CONFORMAL_CQR 1
+#define STDADK_CONFORMAL_ABS 2
+#define STDADK_CONFORMAL_MAX_COLS 8
+#define STDADK_CONFORMAL_MAX_SEGMENTS 2
+#define STDADK_SELECT_MAX 16
+size_t stdadk_conformal_scores_workspace_bytes(int64_t S, int64_t nT);
+int stdadk_conformal_scores_f32(const float *y_pred, const float *z, const uint8_t *split, int64_t S, int64_t nT,
+                                int32_t Q, const int32_t *cols_host, int32_t C, const int32_t *codes_host, int32_t G,
+                                float *scores, int64_t cap, int64_t *count, int32_t *overflow, void *workspace,
+                                size_t workspace_bytes, stdadk_stream_t stream);
+size_t stdadk_select_workspace_bytes(int32_t n_sel);
+int stdadk_select_f32(const float *keys, int64_t stride, int32_t C, const int64_t *n_dev, int64_t n_max,
+                      const int32_t *sel_col_host, const int64_t *sel_rank_host, const double *sel_beta_host,
+                      int32_t n_sel, float *value, int64_t *rank_used, void *workspace, size_t workspace_bytes,
+                      stdadk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Knot initialiser (added under ABI 10: new entry points only, nothing existing changes, so STDADK_ABI_VERSION stays
  * 10): ONE EM iteration of the spherical Gaussian mixture in two dimensions behind `spatial_init_method: gmm`
  * (stnf/models/st_interp.py:187-266 fits sklearn.mixture.GaussianMixture(covariance_type='spherical') on the host),

@@ -227,6 +227,15 @@ _SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "stdadk_group_norms_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
                                          C.c_void_p]),
+    "stdadk_conformal_scores_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "stdadk_conformal_scores_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                              C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                              C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                              C.c_void_p]),
+    "stdadk_select_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "stdadk_select_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]),
     "stdadk_gmm_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "stdadk_gmm_em_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -278,12 +287,21 @@ def lib():
                 f"This package has no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in _SIGNATURES.items():
+            if name in _OWN_UNIT and not hasattr(handle, name):
+                continue                    # (calling it raises AttributeError: there is no fallback)
             fn = getattr(handle, name)      # AttributeError => the .so is stale
             fn.restype, fn.argtypes = res, args
         if handle.stdadk_abi_version() != ABI_VERSION:
             raise NativeLibraryError("libstdadk.so ABI version mismatch")
         _lib = handle
     return _lib
+
+
+# The entry points of csrc/conformal.hip.  A library linked without that translation unit still loads -- the host
+# sanitizer build (tools/build_asan.sh) names its translation units itself and does not list this one -- and a call of
+# one of these then raises AttributeError.
+_OWN_UNIT = frozenset(("stdadk_conformal_scores_workspace_bytes", "stdadk_conformal_scores_f32",
+                       "stdadk_select_workspace_bytes", "stdadk_select_f32"))
 
 
 def exported_symbols():
@@ -917,6 +935,65 @@ def group_norms(W0, transposed, H, col0, n, out):
     rc = lib().stdadk_group_norms_f32(W0.data_ptr(), ld, int(bool(transposed)), int(H), int(col0), int(n),
                                       _typed("group_norms", out, "out", torch.float64, (int(n),)), _stream())
     _check(rc, "stdadk_group_norms_f32")
+
+
+# the score kinds and limits of stdadk_conformal_scores_f32 / stdadk_select_f32 (include/stdadk.h)
+CONFORMAL_RESID, CONFORMAL_CQR, CONFORMAL_ABS, CONFORMAL_MAX_COLS, CONFORMAL_MAX_SEGMENTS, SELECT_MAX = 0, 1, 2, 8, 2, 16
+
+
+def conformal_scores_workspace_bytes(S, nT):
+    return _workspace_bytes("stdadk_conformal_scores_workspace_bytes",
+                            f"bad grid {S} x {nT} (S*nT must stay below 2^31)", S, nT)
+
+
+def conformal_scores(y_pred, z, split, cols, codes, scores, count, overflow, workspace):
+    """stdadk_conformal_scores_f32 on one chunk of time slices, laid out as grid_score's: y_pred (nT*S, Q) time-major,
+    z (nT, S) float32 with NaN = no value, split (nT, S) uint8 or None (all 0).  cols: C triples (kind, col_a, col_b),
+    codes: G split codes.  The C scores of every entry with a finite z and split == codes[g] are appended to
+    scores[g] (scores (G, C, cap) float32) in time-major then site order, from position count[g] on (count (G,) int64
+    on the device, advanced by the call, saturating at cap); overflow (G,) int32 is set where members were dropped."""
+    what = "conformal_scores"
+    nT, S, Q, _ = _grid_args(what, y_pred, z, split, None, workspace)
+    Cn, G = len(cols), len(codes)
+    if scores.dim() != 3 or tuple(scores.shape[:2]) != (G, Cn):
+        raise RuntimeError(f"{what}: scores must be (G, C, cap) = ({G}, {Cn}, cap), got {tuple(scores.shape)}")
+    flat = [int(v) for col in cols for v in col]
+    if len(flat) != 3 * Cn:
+        raise RuntimeError(f"{what}: every score column is (kind, col_a, col_b)")
+    rc = lib().stdadk_conformal_scores_f32(
+        _dev(y_pred, "y_pred"), _dev(z, "z"), _dev(split, "split"), S, nT, Q, (C.c_int32 * len(flat))(*flat), Cn,
+        (C.c_int32 * G)(*[int(c) for c in codes]), G, _typed(what, scores, "scores", torch.float32, None),
+        scores.shape[2], _typed(what, count, "count", torch.int64, (G,)),
+        _typed(what, overflow, "overflow", torch.int32, (G,)), workspace.data_ptr(), workspace.numel() * 8, _stream())
+    _check(rc, "stdadk_conformal_scores_f32")
+
+
+def select_workspace_bytes(n_sel):
+    return _workspace_bytes("stdadk_select_workspace_bytes", f"n_sel={n_sel} outside 1..{SELECT_MAX}", n_sel)
+
+
+def select(keys, n, selections, value, rank_used, workspace, n_max=None):
+    """stdadk_select_f32: exact order statistics of the columns of keys (C, stride) float32, of which the first n
+    (a 1-element int64 tensor on the device; n_max bounds it on the host, default the stride) are the data.
+    selections: (column, rank, beta) each -- a 0-based rank, or a negative rank (or None) and the level beta, for the
+    1-based rank ceil((n + 1) * beta).  value (n_sel,) float32 and rank_used (n_sel,) int64 on the device; a rank
+    beyond n gives +inf and -1."""
+    what = "select"
+    if keys.dim() != 2:
+        raise RuntimeError(f"{what}: keys must be (C, stride), got {tuple(keys.shape)}")
+    Cn, stride = keys.shape
+    k = len(selections)
+    cols = (C.c_int32 * k)(*[int(s[0]) for s in selections])
+    ranks = (C.c_int64 * k)(*[-1 if s[1] is None else int(s[1]) for s in selections])
+    betas = (C.c_double * k)(*[0.0 if s[2] is None else float(s[2]) for s in selections])
+    if workspace.dtype != torch.float64 or not _on_device(workspace) or not workspace.is_contiguous():
+        raise RuntimeError(f"{what}: workspace must be a contiguous float64 tensor on the device")
+    rc = lib().stdadk_select_f32(
+        _typed(what, keys, "keys", torch.float32, None), stride, Cn, _typed(what, n, "n", torch.int64, (1,)),
+        stride if n_max is None else int(n_max), cols, ranks, betas, k,
+        _typed(what, value, "value", torch.float32, (k,)), _typed(what, rank_used, "rank_used", torch.int64, (k,)),
+        workspace.data_ptr(), workspace.numel() * 8, _stream())
+    _check(rc, "stdadk_select_f32")
 
 
 def gmm_workspace_bytes(n, k):

@@ -1189,6 +1189,11 @@ class TrainStep(Cached):
         self.refresh_bf16()
 
 
+class _ConformalPass:
+    """What Predictor.conformal_pass hands to the scoring pass: plan, codes, scores, count, overflow."""
+    __slots__ = ("plan", "codes", "scores", "count", "overflow")
+
+
 class Predictor:
     """Dense-grid inference (reference scripts/train_st_interp.py:1091-1107,1232-1248,1378-1409;
     evaluate_model :884-961): batched forward into a preallocated output, chunked so the workspace
@@ -1342,10 +1347,12 @@ class Predictor:
             lo, hi = levels.index(float(interval[0])), levels.index(float(interval[1]))
         return coords, t_values, z, levels, lo, hi
 
-    def _score_chunks(self, coords, t_values, z, split, levels, lo, hi, max_rows, scores, quantile):
+    def _score_chunks(self, coords, t_values, z, split, levels, lo, hi, max_rows, scores, quantile, conformal=None):
         """One pass over the grid's chunks of time slices -- ONE forward per chunk into a reused buffer -- reduced by
         stdadk_grid_score_f32 (`scores`) and / or stdadk_quantile_diag_f32 (`quantile`) on that buffer.  Returns the
-        accumulators of the reductions asked for, (split_acc, site_acc, time_acc) each, in that order."""
+        accumulators of the reductions asked for, (split_acc, site_acc, time_acc) each, in that order.
+        `conformal` (a _ConformalPass): the third kind, stdadk_conformal_scores_f32 on the same buffer, appending the
+        chunk's conformity scores to the pass's segments; it has no accumulators in the returned list."""
         S, T = coords.shape[0], t_values.numel()
         Q = self.model.output_dim
         # (name prefix, slots per split, values per site / time, workspace bytes, the chunk's reduction)
@@ -1364,7 +1371,12 @@ class Predictor:
         per = min(self._slices_per_call(S, max_rows), T)
         buf = self._reused("y", (per * S, Q))
         wss = [self._reused(k + "grid_ws", (nbytes(S, per) // 8,), torch.float64) for k, _, _, nbytes, _ in kinds]
+        cws = None if conformal is None else self._reused("cf_ws", (N.conformal_scores_workspace_bytes(S, per) // 8,),
+                                                          torch.float64)
         for t0, n, y in self._grid_chunks(coords, t_values, max_rows, lambda t0, n: buf[:n * S], self._reused):
+            if conformal is not None:
+                N.conformal_scores(y, z[t0:t0 + n], None if split is None else split[t0:t0 + n], conformal.plan.cols,
+                                   conformal.codes, conformal.scores, conformal.count, conformal.overflow, cws)
             for (k, _, v, _, reduce), (split_acc, site_acc, time_acc), ws in zip(kinds, out, wss):
                 # the kernel ASSIGNS its chunk's time sums: straight into time_acc when one chunk is the grid
                 tacc = time_acc if per == T else self._reused(k + ("time_part" if n == per else "time_tail"),
@@ -1376,7 +1388,7 @@ class Predictor:
 
     @torch.no_grad()
     def score_grid(self, coords, t_values, z, split=None, quantile_levels=None, interval=None, max_rows=None,
-                   quantile=False):
+                   quantile=False, conformal=None):
         """predict_grid scored against the field on the device, without the grid: coords (S,2), t_values (T,),
         z (T,S) float32 with NaN where the field has no value, split (T,S) uint8 codes 0..3 or None (all 0).  The
         predictions of every chunk of time slices (at most `max_rows` rows, default as predict_grid) go into one
@@ -1386,11 +1398,60 @@ class Predictor:
         slots (default 0.5 each); `interval=(lo_level, hi_level)` picks the cover / width columns from them.
         `quantile=True`: stdadk_quantile_diag_f32 reduces the same chunk buffer too (still one forward per chunk) and
         the three tensors of quantile_grid follow the usual three.
+        `conformal`: a pass made by conformal_pass(); the same chunk buffer also feeds stdadk_conformal_scores_f32,
+        and conformal_finish(pass) selects the offsets afterwards (what is returned here does not change).
         The tensors and the scratch belong to the predictor and are overwritten by its next scoring call."""
         coords, t_values, z, levels, lo, hi = self._grid_args("score_grid", coords, t_values, z, split,
                                                               quantile_levels, interval)
-        out = self._score_chunks(coords, t_values, z, split, levels, lo, hi, max_rows, True, bool(quantile))
+        out = self._score_chunks(coords, t_values, z, split, levels, lo, hi, max_rows, True, bool(quantile), conformal)
         return out[0] + out[1] if quantile else out[0]
+
+    def conformal_pass(self, cap, quantile_levels=None, intervals=None, alpha=0.1, cal_code=2, eval_code=3):
+        """The state of one conformal calibration over a grid: the plan (stnf.calibration.make_plan: which score
+        columns, which selections) and the two segments' buffers -- scores (2, C, cap) float32, the device counters and
+        overflow flags, zeroed -- for the entries whose split code is cal_code (segment 0) and eval_code (segment 1).
+        `cap`: the capacity of a segment, at least the larger of the two member counts (the caller knows its masks; a
+        smaller one sets the overflow flag and calibrates on the prefix that fit)."""
+        from . import calibration as CF
+        plan = CF.make_plan(self.model.output_dim, quantile_levels, intervals, alpha)
+        cf = _ConformalPass()
+        cf.plan, cf.codes = plan, [int(cal_code), int(eval_code)]
+        cf.scores = self._reused("cf_scores", (2, len(plan.cols), max(int(cap), 1)), torch.float32)
+        cf.count = self._reused("cf_count", (2,), torch.int64).zero_()
+        cf.overflow = self._reused("cf_overflow", (2,), torch.int32).zero_()
+        return cf
+
+    def conformal_finish(self, cf, split="valid"):
+        """ONE stdadk_select_f32 call for every offset of the pass, the evaluation segment's counts under the offsets,
+        ONE host read; returns stnf.calibration.report's dict (its `calibration` is the Calibration record)."""
+        from . import calibration as CF
+        return CF.report(cf.plan, CF.finish_device(cf.plan, cf.scores, cf.count, cf.overflow, self._reused), split)
+
+    @torch.no_grad()
+    def conformal_grid(self, coords, t_values, z, split, quantile_levels=None, intervals=None, alpha=0.1, cal_code=2,
+                       eval_code=3, max_rows=None, cap=None):
+        """Split-conformal calibration over a grid on the device, without the grid (arguments as score_grid): the
+        conformity scores of the entries with split code `cal_code` (2: valid) calibrate, those with `eval_code`
+        (3: test) show what the calibration does.  With `quantile_levels`: a one-sided offset per level (score z - q,
+        rank ceil((n + 1) tau)) and a CQR offset per interval of `intervals` (pairs of levels; score
+        max(q_lo - z, z - q_hi), rank ceil((n + 1)(1 - alpha))); without: the half-width of |z - yhat| at 1 - alpha.
+        One forward per chunk, stdadk_conformal_scores_f32 on the chunk buffer, ONE stdadk_select_f32 call after the
+        last chunk; coverage after = the count of evaluation scores <= the offset over n_eval, width after = width
+        before + 2 c: no second forward.  `cap`: the segments' capacity (conformal_pass's); None counts the members on the
+        device, which costs a host read of its own -- otherwise everything is read by the host once.
+        Returns stnf.calibration.report's dict.  The guarantee is marginal and needs the calibration entries to be
+        exchangeable with the ones it is used on: with site-wise splits it holds for new sites drawn like the
+        validation sites, not for every site (stnf.calibration)."""
+        coords, t_values, z, levels, _, _ = self._grid_args("conformal_grid", coords, t_values, z, split,
+                                                            quantile_levels, None)
+        if split is None:
+            raise ValueError("conformal_grid: the split codes name the calibration and the evaluation entries")
+        if cap is None:
+            fin = torch.isfinite(z)
+            cap = int(torch.stack([(fin & (split == c)).sum() for c in (cal_code, eval_code)]).max())
+        cf = self.conformal_pass(cap, levels, intervals, alpha, cal_code, eval_code)
+        self._score_chunks(coords, t_values, z, split, levels, -1, -1, max_rows, False, False, cf)
+        return self.conformal_finish(cf)
 
     @torch.no_grad()
     def quantile_grid(self, coords, t_values, z, split=None, quantile_levels=None, interval=None, max_rows=None):

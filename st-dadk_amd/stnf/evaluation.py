@@ -89,7 +89,15 @@ class Evaluator:
 
     # ------------------------------------------------------------------------------------
     @torch.no_grad()
-    def evaluate(self, dataset, batch_size, params="live", engine=None, diagnostics=False):
+    def evaluate(self, dataset, batch_size, params="live", engine=None, diagnostics=False, conformal=None,
+                 conformal_interval=None):
+        """`conformal=alpha` (off by default): `dataset` is the CALIBRATION split; the batches keep their predictions as
+        with `diagnostics` and the dict gains `calibration`, a stnf.calibration.Calibration at miscoverage alpha made
+        from them on the device (stdadk_conformal_scores_f32 on the set as a 1 x N grid, stdadk_select_f32; one more
+        host read): for a pinball objective a one-sided offset per level and the CQR offset of `conformal_interval`
+        (two of the levels; default the outermost two), otherwise the half-width of |y - yhat|.  The guarantee is
+        marginal over data exchangeable with this set: with site-wise splits, new sites drawn like the validation
+        sites, not every site.  Single process only."""
         if params not in ("live", "ema"):
             raise ValueError(f"params='{params}'; use 'live' or 'ema'")
         m = self.model
@@ -105,13 +113,31 @@ class Evaluator:
         try:
             # (a list of sizes summing to len(dataset): the data-parallel schedule, DeviceDataset.epoch_batches)
             sizes = [int(b) for b in batch_size] if isinstance(batch_size, (list, tuple)) else int(batch_size)
-            return self._evaluate(dataset, sizes, engine, ema_views=(params == "ema" and not swapped),
-                                  diagnostics=bool(diagnostics) and self.objective.kind == "pinball")
+            out = self._evaluate(dataset, sizes, engine, ema_views=(params == "ema" and not swapped),
+                                 diagnostics=bool(diagnostics) and self.objective.kind == "pinball",
+                                 keep=conformal is not None)
+            if conformal is not None:
+                out["calibration"] = self._calibrate(dataset, float(conformal), conformal_interval)
+            return out
         finally:
             if swapped:
                 engine.swap_in_ema()
 
-    def _evaluate(self, dataset, batch_size, engine, ema_views, diagnostics=False):
+    def _calibrate(self, dataset, alpha, interval):
+        """The Calibration of the pass that just ran, from the predictions it kept (dataset order)."""
+        from .calibration import calibrate_rows
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.pg) > 1:
+            raise NotImplementedError("Evaluator: conformal calibration runs in a single process (the order statistic "
+                                      "of a sharded set is not a sum over ranks)")
+        levels = self.objective.quantile_levels if self.objective.kind == "pinball" else None
+        if levels is not None and interval is None and len(levels) >= 2:
+            interval = (levels[0], levels[-1])
+        y = dataset.y
+        target = y.view(-1) if y.shape[1] == 1 else y[:, self.model.output_dim // 2].contiguous()
+        return calibrate_rows(self.predictions, target, levels, [interval] if interval is not None else None, alpha,
+                              scratch=self._buffer)
+
+    def _evaluate(self, dataset, batch_size, engine, ema_views, diagnostics=False, keep=False):
         m = self.model
         if self._desc is None:
             self._desc = m._native_desc(False)
@@ -142,7 +168,9 @@ class Evaluator:
         acc = self.acc
         acc.zero_()
         n_rows = len(dataset)
-        preds = self._buffer("preds", (n_rows, Q), torch.float32) if diagnostics else None
+        preds = self._buffer("preds", (n_rows, Q), torch.float32) if diagnostics or keep else None
+        if keep:
+            self.predictions = preds
         row = 0
         for idx in batches:
             B = idx.numel()

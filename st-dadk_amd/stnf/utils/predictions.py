@@ -107,6 +107,18 @@ def evaluate_model(model, dataset, config=None, predictor=None):
         per_level = [float(check_loss_numpy(pred[:, j:j + 1], obs, tau)) for j, tau in enumerate(levels)]
         out["crps"] = float(compute_crps_multi_quantile(pred, obs, levels))
         out["mean_check_loss"] = out["check_loss"] = float(np.mean(per_level))      # the reference keeps both names
+    if (config or {}).get("conformal", False):
+        # `dataset` is the calibration split: a Calibration from the predictions this pass made (stnf.calibration; the
+        # interval of `interval`, at `conformal_alpha`, default its nominal miscoverage, otherwise 0.1)
+        from ..calibration import calibrate_rows
+        iv = config.get("interval") if levels is not None else None
+        alpha = config.get("conformal_alpha", 0.1 if iv is None else round(1.0 - (float(iv[1]) - float(iv[0])), 12))
+        target = dataset.y.float().reshape(pred.shape[0], -1)
+        if levels is None and kind == "quantile" and "current_quantile" in config:
+            levels = [float(config["current_quantile"])]
+        out["calibration"] = calibrate_rows(preds_t.detach().float(), target[:, target.shape[1] // 2], levels,
+                                            [iv] if iv is not None else None, alpha,
+                                            split=str(config.get("conformal_split", "valid")))
     return out
 
 
@@ -260,7 +272,17 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
     With `basis_diagnostics: true` the dict gains `basis`: utils.basis_diag.basis_diagnostics' dict at the same sites,
     the site weights being the training observations per site (`train_mask.sum(0)`) and the site value the test split's
     per-site MSE computed here; `basis_rho` overrides the support radius.  On the device that is two more library calls
-    and one more host read; without the key nothing changes."""
+    and one more host read; without the key nothing changes.
+    With `conformal: true` the dict gains `conformal` (stnf.calibration.report): split-conformal calibration on the
+    split `conformal_split` (default `valid`) at miscoverage `conformal_alpha` (default the nominal one of `interval`,
+    1 - (hi - lo), otherwise 0.1), shown on the test split -- per quantile level the one-sided offset and the
+    reliability before and after; for `interval` the CQR offset, n_cal, coverage and mean width before and after; for a
+    mean model the half-width of |z - yhat| and its coverage; `overflow` and `rank_beyond_n` (too few calibration
+    entries for this alpha: the offset is +inf) are reported, never hidden; `calibration` is the Calibration record to
+    apply or save.  On the device the scores are compacted from the same chunk buffer (one forward per chunk), one
+    select call and one more host read; without the key nothing changes.  The guarantee is marginal over entries
+    exchangeable with the calibration split: with site-wise splits it holds for new sites drawn like the validation
+    sites, not for every site."""
     if getattr(model, "p", 0) != 0:
         raise ValueError("grid_scores: the dense grid has no covariates (p must be 0)")
     z = np.asarray(z_full.detach().cpu() if torch.is_tensor(z_full) else z_full)
@@ -301,6 +323,19 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
     if tuple(c.shape) != (S, 2):
         raise ValueError(f"grid_scores: coords must be ({S}, 2), got {tuple(c.shape)}")
     tv = _grid_times(T)
+    cf = cf_plan = None
+    if config.get("conformal", False):
+        from .. import calibration as CF
+        cf_split = str(config.get("conformal_split", "valid"))
+        if cf_split not in SPLIT_NAMES[:3]:
+            raise ValueError(f"grid_scores: conformal_split '{cf_split}' must be one of {SPLIT_NAMES[:3]} (test evaluates)")
+        cf_codes = [SPLIT_NAMES.index(cf_split), 3]
+        # the nominal miscoverage of the interval's two levels, unless the config names one
+        cf_alpha = config.get("conformal_alpha", 0.1 if interval is None else
+                              round(1.0 - (float(interval[1]) - float(interval[0])), 12))
+        cf_plan = CF.make_plan(Q, levels, [interval] if interval is not None else None, cf_alpha)
+        members = np.isfinite(z)
+        cf_cap = max(int((members & (code == k)).sum()) for k in cf_codes)
     vg = None
     if config.get("variogram", False):
         from . import variogram as V
@@ -315,11 +350,17 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
         if dev.type == "cuda":
             from ..engine import Predictor
             pr, zt, ct = Predictor(model), torch.from_numpy(z.astype(np.float32)).to(dev), torch.from_numpy(code).to(dev)
+            more = {}
+            if cf_plan is not None:
+                more["conformal"] = pr.conformal_pass(cf_cap, levels, [interval] if interval is not None else None,
+                                                      cf_alpha, *cf_codes)
             accs = pr.score_grid(c, tv.to(dev), zt, ct, quantile_levels=levels, interval=interval, max_rows=max_rows,
-                                 quantile=diag)
+                                 quantile=diag, **more)
             flat = torch.cat([a.reshape(-1) for a in accs]).cpu().numpy()              # the ONE host read
             cuts = np.cumsum([a.numel() for a in accs])[:-1]
             sums = [part.reshape(a.shape) for part, a in zip(np.split(flat, cuts), accs)]
+            if cf_plan is not None:
+                cf = pr.conformal_finish(more["conformal"], cf_split)                  # (and the calibration's own)
             if config.get("variogram", False):
                 vg = pr.variogram_grid(c, tv.to(dev), zt, ct, edges=vg_edges, time_lags=vg_lags,
                                        sites=vg_sites)["acc"]                          # (and the variogram's own)
@@ -329,6 +370,9 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
             sums = list(_grid_sums_host(pred, z, code, levels, lo, hi))
             if diag:
                 sums += _quantile_sums_host(pred, z, code, levels, lo, hi)
+            if cf_plan is not None:
+                segments = CF.scores_numpy(pred.astype(np.float32), z.astype(np.float32), code, cf_plan.cols, cf_codes)
+                cf = CF.report(cf_plan, CF.finish_host(cf_plan, segments), cf_split)
             if config.get("variogram", False):
                 vg = V.variogram_sums_host(pred[:, vg_sites, Q // 2].astype(np.float32), z[:, vg_sites].astype(np.float32),
                                            code[:, vg_sites], c.numpy()[vg_sites], vg_e2, vg_lags)
@@ -350,6 +394,8 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
         out["variogram"] = {SPLIT_NAMES[k]: dict({name: curves[name][k] for name in
                                                   ("count", "gamma_z", "gamma_pred", "gamma_resid")},
                                                  edges=curves["edges"], lags=curves["lags"]) for k in (1, 2, 3, 0)}
+    if cf is not None:
+        out["conformal"] = cf
     if config.get("basis_diagnostics", False):
         from .basis_diag import basis_diagnostics
         out["basis"] = basis_diagnostics(model, c, train_mask=train_mask, config=config,
@@ -363,7 +409,14 @@ def save_grid_scores_npz(output_dir, scores):
     per-time arrays under their own names, every split metric as the 0-d array `splits/<split>/<metric>`, and the
     quantile diagnostics, when present, as `quantile/<split>/<metric>` and `quantile/<map>`, and the variograms, when
     present, as `variogram/<split>/<name>`, and the basis diagnostics, when present, as `basis/<name>`."""
-    arrs = {k: np.asarray(v) for k, v in scores.items() if k not in ("splits", "quantile", "variogram", "basis")}
+    arrs = {k: np.asarray(v) for k, v in scores.items()
+            if k not in ("splits", "quantile", "variogram", "basis", "conformal")}
+    # the conformal calibration, when present: the record's fields as `conformal/<field>` (calibration.load_calibration_npz
+    # reads them back from a file of their own, save_calibration_npz)
+    if "conformal" in scores:
+        from ..calibration import _NPZ
+        for k in _NPZ:
+            arrs[f"conformal/{k}"] = np.asarray(getattr(scores["conformal"]["calibration"], k))
     for name, metrics in scores["splits"].items():
         for k, v in metrics.items():
             arrs[f"splits/{name}/{k}"] = np.asarray(v)
