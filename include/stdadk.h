@@ -963,6 +963,67 @@ int stdadk_select_f32(const float *keys, int64_t stride, int32_t C, const int64_
                       stdadk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Neighbour tables (added under ABI 10: new entry points only, so STDADK_ABI_VERSION stays 10): the k nearest of a set
+ * of sites, exactly, and a table applied to a field -- the baselines "copy the nearest observed site" and
+ * inverse-distance weighting (IDW) a model's scores stand next to (stnf.utils.baselines), and the nearest-site raster
+ * of a per-site map.
+ *
+ * stdadk_knn_f32: the search, brute force.
+ *   q [M][2]            float32, device: the targets
+ *   coords [S][2]       float32, device: the candidate sources
+ *   src [nM][S]         uint8, device, or NULL (= every site; nM must then be 1): slice m's sources are the sites with
+ *                       src != 0
+ *   k                   1 .. STDADK_KNN_MAX_K
+ *   exclude_self        0 / 1; 1 requires M == S and skips source j for target j (leave-one-site-out)
+ *   nbr_idx [nM][M][k]  int32, ASSIGNED
+ *   nbr_d2  [nM][M][k]  float64, ASSIGNED
+ * For target j and source i, d2 = (qx - cx)^2 + (qy - cy)^2 is formed in float64 from the float32 operands, every
+ * operation rounded once (two differences, two products, one sum; no fused multiply-add).  A NaN d2 is never a
+ * neighbour; a d2 of +inf is one like any other.  The neighbours of (m, j) are the k smallest sources of slice m in the
+ * TOTAL order (d2, source index) -- equal distances go to the lower index -- written in that order; a host
+ * restatement is np.lexsort((index, d2))[:k].  When fewer than k sources exist the tail is idx = -1, d2 = +inf.
+ * Because the order is total the answer does not depend on how the kernel partitions the sources (csrc/knn.hip: over
+ * four waves, and over source spans when targets x slices alone would leave the device idle): the same call gives the
+ * same bits, and so does any other launch plan.  M = 0 or nM = 0 writes nothing; S = 0 writes the neutral rows.
+ * Errors: M, S or nM outside 0..2^31-1, k outside 1..STDADK_KNN_MAX_K, exclude_self not 0 / 1 or set with M != S,
+ * src == NULL with nM != 1 (unless nM*S == 0: no flag to read), a NULL q / nbr_idx / nbr_d2 (with M, nM > 0), coords (with S > 0) or workspace, an output
+ * (nbr_idx, nbr_d2, the workspace) that aliases an input or another output: STDADK_E_ARG; nM*M*k >= 2^31:
+ * STDADK_E_SHAPE; nbr_d2 or the workspace not 8-byte, nbr_idx, q or coords not 4-byte aligned: STDADK_E_ALIGN; a
+ * workspace below stdadk_knn_workspace_bytes(M, S, nM, k) (0 = bad sizes): STDADK_E_WORKSPACE.  No host read of device
+ * memory, no allocation, capturable.
+ *
+ * stdadk_knn_apply_f32: a table applied to a field.
+ *   nbr_idx, nbr_d2 [nM][M][k_tab]   a table of the search; nM == 1 (one table for every slice) or nM == nT
+ *   k                   1 .. k_tab: the first k entries of a row are used (a prefix of the order is the order)
+ *   z [nT][S]           float32: the field's slices
+ *   power               0, 1, 2, 3 or 4
+ *   nearest [nT][M], idw [nT][M]     float32, ASSIGNED; either may be NULL (not both)
+ * For entry (ti, j) the row is that of slice m = (nM == 1 ? 0 : ti).  An entry of the row counts when 0 <= idx < S
+ * (the search's tail of -1 does not; an index >= S is never dereferenced).  No entry counts: NaN in both outputs.
+ *   nearest  z[ti][idx] of the first entry that counts, the bits copied.
+ *   idw      if the first entry that counts has d2 == 0: the mean of z over the leading run of entries with d2 == 0 --
+ *            the sum in double in row order, ONE division, rounded to float32 once.  Otherwise, over the entries that
+ *            count in row order, w = 1 (power 0), 1/sqrt(d2) (1), 1/d2 (2), 1/(d2 sqrt(d2)) (3), 1/(d2 d2) (4), every
+ *            operation an IEEE double operation rounded once (division and square root correctly rounded); then
+ *            num += w z and den += w sequentially (the product rounded, then the sum), and idw = (float)(num / den).
+ * numpy float64 restates every output bit for bit.  A non-finite z at a used neighbour propagates: callers exclude such
+ * entries through src.
+ * Errors: M, S, nT, nM or k_tab outside 0..2^31-1, nM not 1 and not nT, k outside 1..k_tab or k_tab above
+ * STDADK_KNN_MAX_K, power outside 0..4, a NULL table or z, or nearest and idw both NULL (with nT, M > 0), an output that
+ * aliases an input or the other output: STDADK_E_ARG; nT*M, nT*S or nM*M*k_tab >= 2^31: STDADK_E_SHAPE; nbr_d2 not
+ * 8-byte, nbr_idx, z, nearest or idw not 4-byte aligned: STDADK_E_ALIGN.  nT = 0 or M = 0 writes nothing.  No
+ * workspace, no host read of device memory, no allocation, capturable.
+ * ------------------------------------------------------------------------------------------ */
+#define STDADK_KNN_MAX_K 16
+size_t stdadk_knn_workspace_bytes(int64_t M, int64_t S, int64_t nM, int32_t k);
+int stdadk_knn_f32(const float *q, int64_t M, const float *coords, int64_t S, const uint8_t *src, int64_t nM, int32_t k,
+                   int32_t exclude_self, int32_t *nbr_idx, double *nbr_d2, void *workspace, size_t workspace_bytes,
+                   stdadk_stream_t stream);
+int stdadk_knn_apply_f32(const int32_t *nbr_idx, const double *nbr_d2, int64_t nM, int64_t M, int32_t k_tab, int32_t k,
+                         const float *z, int64_t nT, int64_t S, int32_t power, float *nearest, float *idw,
+                         stdadk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Knot initialiser (added under ABI 10: new entry points only, nothing existing changes, so STDADK_ABI_VERSION stays
  * 10): ONE EM iteration of the spherical Gaussian mixture in two dimensions behind `spatial_init_method: gmm`
  * (stnf/models/st_interp.py:187-266 fits sklearn.mixture.GaussianMixture(covariance_type='spherical') on the host),

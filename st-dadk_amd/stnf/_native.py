@@ -236,6 +236,11 @@ _SIGNATURES = {
     "stdadk_select_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    "stdadk_knn_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    "stdadk_knn_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "stdadk_knn_apply_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "stdadk_gmm_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "stdadk_gmm_em_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -297,11 +302,12 @@ def lib():
     return _lib
 
 
-# The entry points of csrc/conformal.hip.  A library linked without that translation unit still loads -- the host
-# sanitizer build (tools/build_asan.sh) names its translation units itself and does not list this one -- and a call of
-# one of these then raises AttributeError.
+# The entry points of csrc/conformal.hip and csrc/knn.hip.  A library linked without those translation units still
+# loads -- the host sanitizer build (tools/build_asan.sh) names its translation units itself and lists neither -- and a
+# call of one of these then raises AttributeError.
 _OWN_UNIT = frozenset(("stdadk_conformal_scores_workspace_bytes", "stdadk_conformal_scores_f32",
-                       "stdadk_select_workspace_bytes", "stdadk_select_f32"))
+                       "stdadk_select_workspace_bytes", "stdadk_select_f32",
+                       "stdadk_knn_workspace_bytes", "stdadk_knn_f32", "stdadk_knn_apply_f32"))
 
 
 def exported_symbols():
@@ -994,6 +1000,53 @@ def select(keys, n, selections, value, rank_used, workspace, n_max=None):
         _typed(what, value, "value", torch.float32, (k,)), _typed(what, rank_used, "rank_used", torch.int64, (k,)),
         workspace.data_ptr(), workspace.numel() * 8, _stream())
     _check(rc, "stdadk_select_f32")
+
+
+KNN_MAX_K = 16      # STDADK_KNN_MAX_K of include/stdadk.h
+
+
+def knn_workspace_bytes(M, S, nM, k):
+    return _workspace_bytes("stdadk_knn_workspace_bytes",
+                            f"bad sizes: M={M}, S={S}, nM={nM} (each 0 .. 2^31-1, nM*M*k below 2^31), k={k} "
+                            f"(1..{KNN_MAX_K})", M, S, nM, k)
+
+
+def knn(q, coords, src, k, exclude_self, nbr_idx, nbr_d2, workspace):
+    """stdadk_knn_f32: for every target of q (M, 2) float32 the k nearest sources among coords (S, 2) float32 in the
+    total order (d2, index), d2 in float64.  src: (nM, S) uint8, slice m's sources are the sites with src != 0, or None
+    (every site, one slice).  exclude_self (needs M == S) skips source j for target j.  ASSIGNS nbr_idx (nM, M, k) int32
+    and nbr_d2 (nM, M, k) float64 on the device; a row short of k sources ends in -1 / +inf."""
+    what = "knn"
+    if q.dim() != 2 or coords.dim() != 2:
+        raise RuntimeError(f"{what}: q must be (M, 2) and coords (S, 2)")
+    M, S = q.shape[0], coords.shape[0]
+    nM = 1 if src is None else src.shape[0]
+    k = int(k)
+    rc = lib().stdadk_knn_f32(
+        _typed(what, q, "q", torch.float32, (M, 2)), M, _typed(what, coords, "coords", torch.float32, (S, 2)), S,
+        None if src is None else _typed(what, src, "src", torch.uint8, (nM, S)), nM, k, int(bool(exclude_self)),
+        _typed(what, nbr_idx, "nbr_idx", torch.int32, (nM, M, k)), _typed(what, nbr_d2, "nbr_d2", torch.float64, (nM, M, k)),
+        _typed(what, workspace, "workspace", torch.float64, None), workspace.numel() * 8, _stream())
+    _check(rc, "stdadk_knn_f32")
+
+
+def knn_apply(nbr_idx, nbr_d2, k, z, power, nearest, idw):
+    """stdadk_knn_apply_f32: the table nbr_idx / nbr_d2 (nM, M, k_tab) of knn, nM == 1 or nM == nT, applied to the
+    slices z (nT, S) float32 with the first k entries of every row: ASSIGNS nearest (nT, M) (the nearest source's value)
+    and idw (nT, M) (inverse-distance weighting with w = d^-power, power 0..4; the mean over zero distances where there
+    are any), float32 on the device; either may be None.  NaN where a row holds no source."""
+    what = "knn_apply"
+    if nbr_idx.dim() != 3 or z.dim() != 2:
+        raise RuntimeError(f"{what}: the table must be (nM, M, k_tab) and z (nT, S)")
+    nM, M, k_tab = nbr_idx.shape
+    nT, S = z.shape
+    out = lambda t, name: None if t is None else _typed(what, t, name, torch.float32, (nT, M))      # noqa: E731
+    rc = lib().stdadk_knn_apply_f32(
+        _typed(what, nbr_idx, "nbr_idx", torch.int32, (nM, M, k_tab)),
+        _typed(what, nbr_d2, "nbr_d2", torch.float64, (nM, M, k_tab)), nM, M, k_tab, int(k),
+        _typed(what, z, "z", torch.float32, (nT, S)), nT, S, int(power), out(nearest, "nearest"), out(idw, "idw"),
+        _stream())
+    _check(rc, "stdadk_knn_apply_f32")
 
 
 def gmm_workspace_bytes(n, k):

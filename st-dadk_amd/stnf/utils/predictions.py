@@ -282,7 +282,17 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
     apply or save.  On the device the scores are compacted from the same chunk buffer (one forward per chunk), one
     select call and one more host read; without the key nothing changes.  The guarantee is marginal over entries
     exchangeable with the calibration split: with site-wise splits it holds for new sites drawn like the validation
-    sites, not for every site."""
+    sites, not for every site.
+    With `baselines: true` the dict gains `baseline` (utils.baselines.grid_baselines): the scores, on the same masks, of
+    NEAREST (copy the nearest training site observed at that time) and IDW (inverse-distance weighting over the
+    `baseline_k` (8) nearest, w = d^-`baseline_power` (2)), training entries leave-one-site-out, each with `splits`,
+    `site_mse`, `site_mse_by_split`, `time_mse`; `train_dist` (S,), the distance to the nearest other training site;
+    and `skill` {baseline: {split: 1 - mse_model / mse_baseline}} with `site_skill` (2, S), the same per site on the
+    test split (rows nearest, idw).  How to read it: a skill of 0 means the model is no better than the baseline, a
+    negative skill that it is WORSE than an interpolator of ten lines, 1 a perfect model; NaN where either MSE is NaN or
+    the baseline's is 0.  A training mask that is the same at every time costs one neighbour search for the whole
+    grid; otherwise one brute-force search per time slice (`train_mask` is needed either way).  Without the key nothing
+    changes."""
     if getattr(model, "p", 0) != 0:
         raise ValueError("grid_scores: the dense grid has no covariates (p must be 0)")
     z = np.asarray(z_full.detach().cpu() if torch.is_tensor(z_full) else z_full)
@@ -401,6 +411,11 @@ def grid_scores(model, z_full, coords, train_mask=None, valid_mask=None, test_ma
         out["basis"] = basis_diagnostics(model, c, train_mask=train_mask, config=config,
                                          site_value=out["site_mse_by_split"][3], rho=config.get("basis_rho"),
                                          predictor=pr)
+    if config.get("baselines", False):
+        from .baselines import grid_baselines, skill_scores
+        out["baseline"] = grid_baselines(z, c.cpu().numpy(), train_mask, valid_mask, test_mask, config=config,
+                                         device=dev if dev.type == "cuda" else None, max_rows=max_rows)
+        out["baseline"].update(skill_scores(out, out["baseline"]))
     return out
 
 
@@ -408,9 +423,18 @@ def save_grid_scores_npz(output_dir, scores):
     """Writes `<output_dir>/grid_scores.npz` from the dict of grid_scores and returns its path: the per-site and
     per-time arrays under their own names, every split metric as the 0-d array `splits/<split>/<metric>`, and the
     quantile diagnostics, when present, as `quantile/<split>/<metric>` and `quantile/<map>`, and the variograms, when
-    present, as `variogram/<split>/<name>`, and the basis diagnostics, when present, as `basis/<name>`."""
+    present, as `variogram/<split>/<name>`, and the basis diagnostics, when present, as `basis/<name>`, and the neighbour
+    baselines, when present, as `baseline/...` (e.g. `baseline/idw/splits/test/mse`, `baseline/skill/idw/test`)."""
     arrs = {k: np.asarray(v) for k, v in scores.items()
-            if k not in ("splits", "quantile", "variogram", "basis", "conformal")}
+            if k not in ("splits", "quantile", "variogram", "basis", "conformal", "baseline")}
+    # the neighbour baselines, when present: `baseline/<name>`, nested dicts joined by `/`
+    todo = [("baseline", scores["baseline"])] if "baseline" in scores else []
+    while todo:
+        name, v = todo.pop()
+        if isinstance(v, dict):
+            todo += [(f"{name}/{k}", w) for k, w in v.items()]
+        else:
+            arrs[name] = np.asarray(v)
     # the conformal calibration, when present: the record's fields as `conformal/<field>` (calibration.load_calibration_npz
     # reads them back from a file of their own, save_calibration_npz)
     if "conformal" in scores:
