@@ -1024,6 +1024,73 @@ int stdadk_knn_apply_f32(const int32_t *nbr_idx, const double *nbr_d2, int64_t n
                          stdadk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Local ordinary kriging on a neighbour table (added under ABI 10: new entry points only, so STDADK_ABI_VERSION stays
+ * 10): the baseline a geostatistics user asks for first (stnf.utils.kriging, stnf.utils.baselines), with a variance, so
+ * that Gaussian quantiles of it go through stdadk_grid_score_f32 and stdadk_quantile_diag_f32 unchanged.  One
+ * variogram model for the whole table (no anisotropy, no drift, no covariates, no global solve).
+ *
+ * stdadk_krige_weights_f64: per row of a table the ordinary-kriging weights and variance.
+ *   nbr_idx, nbr_d2 [nM][M][k_tab]   a table of stdadk_knn_f32 (device); the first k entries of a row are used
+ *   coords [S][2]       float32, device: the sites the indices name
+ *   model               STDADK_KRIGE_EXPONENTIAL rho = exp(-r), _SPHERICAL rho = 1 - r (1.5 - 0.5 r r) for d < range
+ *                       and 0 for d >= range, _GAUSSIAN rho = exp(-(r r)); d = sqrt(d2) and r = d / range correctly
+ *                       rounded, every further operation rounded once in the order written (t = 0.5 (r r), 1.5 - t,
+ *                       r (..), 1 - (..)); exp is the device library's (the host's differs in its last bits)
+ *   nugget, psill, range   the model: gamma(h) = nugget + psill (1 - rho(h)), i.e. covariance psill rho(h)
+ *   w [nM][M][k], var [nM][M]   float64, ASSIGNED
+ * ENTRIES.  Of row (m, j) the entries that COUNT are those of the first k with 0 <= idx < S (stdadk_knn_apply_f32's
+ * rule), taken in row order.  Two entries are COINCIDENT when the d2 between their sources, formed from `coords` as the
+ * search forms it (two differences, two products, one sum, each rounded once), is exactly 0.  Coincident entries form a
+ * group, represented by its first member; `members` is its size.  The unknowns of the row's system are the groups.
+ * SYSTEM.  K_ab = psill rho(d_ab) + [a == b] nugget / members_a (the diagonal is psill + nugget / members, one
+ * division, one sum; rho(0) = 1 is not evaluated), k_a = psill rho(d_a0) with d_a0 from nbr_d2.  The nugget is on the
+ * diagonal only: a target that coincides with a source does NOT reproduce it when nugget > 0 -- the prediction is of
+ * the smooth signal.
+ * SOLVE.  Cholesky K = L L^T in a FIXED order: every element is K_ab minus the products L_ac L_bc in increasing c, each
+ * product rounded, then each subtraction (no fused multiply-add), then one division by L_bb, or one square root on the
+ * diagonal.  L y = r for r = 1 and r = k the same way (r_a minus L_ac y_c in increasing c, one division); L^T x = y
+ * from the last unknown down, x_a = (y_a minus L_ca x_c in DECREASING c) / L_aa.  u = K^-1 1, v = K^-1 k.
+ * WEIGHTS.  mu = (sum v - 1) / sum u (sums in row order from 0), w = v - mu u, var = ((nugget + psill) - sum w_a k_a)
+ * - mu with the sum in row order: the variance of a new noisy observation, not clamped.  A group's weight is written
+ * to each of its members as w / members (one division); entries that do not count get w = 0.
+ * DEGENERATE ROWS.  No entry counts: w = 0, var = NaN.  A pivot (the value under the square root) that is <= 0 or not
+ * finite: every w of the row and var are NaN -- the row is singular and the call says so.
+ * Deterministic: no atomics, fixed orders; the same call gives the same bits.  With the spherical model numpy float64
+ * restates every bit (stnf.utils.kriging.kriging_weights_host).
+ * Errors: M, S or nM outside 0..2^31-1, model outside 0..2, nugget < 0, psill < 0, nugget + psill == 0, range <= 0 or
+ * any of them not finite, k outside 1..k_tab or k_tab outside 1..STDADK_KNN_MAX_K, a NULL pointer (with nM, M > 0;
+ * coords with S > 0), an output that aliases an input or the other output: STDADK_E_ARG; nM*M*k_tab >= 2^31:
+ * STDADK_E_SHAPE; nbr_d2, w or var not 8-byte, nbr_idx or coords not 4-byte aligned: STDADK_E_ALIGN.  M = 0 or nM = 0
+ * writes nothing.  No workspace, no host read of device memory, no allocation, capturable.
+ *
+ * stdadk_krige_apply_f32: the weights applied to a field, with Gaussian quantiles.
+ *   nbr_idx [nM][M][k_tab], w [nM][M][k], var [nM][M]   nM == 1 (one table for every slice) or nM == nT
+ *   z [nT][S]           float32: the field's slices
+ *   zq_host [Q]         float64 on the HOST, read during the call: the standard-normal quantile of every wanted
+ *                       level, 0 for the mean; 1 <= Q <= STDADK_KRIGE_MAX_COLS
+ *   out [nT*M][ldo]     float32, columns 0 .. Q-1 ASSIGNED, ldo >= Q: the y_pred layout of stdadk_grid_score_f32
+ * For entry (ti, j): p = sum_a w_a (double)z[ti][idx_a] over the entries that count in row order from 0 (each product
+ * rounded, then the sum), sd = sqrt(max(var, 0)), out[(ti M + j) ldo + c] = (float)(p + zq[c] sd) (the product
+ * rounded, then the sum, then the conversion).  A row with var NaN gives NaN in every column.  numpy float64 restates
+ * every bit, given w and var (stnf.utils.kriging.kriging_apply_host).
+ * Errors: M, S, nT or nM outside 0..2^31-1, nM not 1 and not nT, k or k_tab as above, Q outside 1..8, ldo < Q or
+ * >= 2^31, a NULL or non-finite zq_host, a NULL pointer (with nT, M > 0; z with S > 0), out aliasing an input:
+ * STDADK_E_ARG; nT*M, nT*S or nM*M*k_tab >= 2^31: STDADK_E_SHAPE; w or var not 8-byte, nbr_idx, z or out not 4-byte
+ * aligned: STDADK_E_ALIGN.  nT = 0 or M = 0 writes nothing.  No workspace, no host read of device memory, no
+ * allocation, capturable.
+ * ------------------------------------------------------------------------------------------ */
+#define STDADK_KRIGE_EXPONENTIAL 0
+#define STDADK_KRIGE_SPHERICAL 1
+#define STDADK_KRIGE_GAUSSIAN 2
+#define STDADK_KRIGE_MAX_COLS 8
+int stdadk_krige_weights_f64(const int32_t *nbr_idx, const double *nbr_d2, int64_t nM, int64_t M, int32_t k_tab,
+                             int32_t k, const float *coords, int64_t S, int32_t model, double nugget, double psill,
+                             double range, double *w, double *var, stdadk_stream_t stream);
+int stdadk_krige_apply_f32(const int32_t *nbr_idx, const double *w, const double *var, int64_t nM, int64_t M,
+                           int32_t k_tab, int32_t k, const float *z, int64_t nT, int64_t S, const double *zq_host,
+                           int32_t Q, float *out, int64_t ldo, stdadk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Knot initialiser (added under ABI 10: new entry points only, nothing existing changes, so STDADK_ABI_VERSION stays
  * 10): ONE EM iteration of the spherical Gaussian mixture in two dimensions behind `spatial_init_method: gmm`
  * (stnf/models/st_interp.py:187-266 fits sklearn.mixture.GaussianMixture(covariance_type='spherical') on the host),

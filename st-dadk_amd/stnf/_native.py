@@ -241,6 +241,12 @@ _SIGNATURES = {
                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "stdadk_knn_apply_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stdadk_krige_weights_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "stdadk_krige_apply_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_int32, C.c_void_p,
+                                         C.c_int64, C.c_void_p]),
     "stdadk_gmm_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "stdadk_gmm_em_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -302,12 +308,13 @@ def lib():
     return _lib
 
 
-# The entry points of csrc/conformal.hip and csrc/knn.hip.  A library linked without those translation units still
-# loads -- the host sanitizer build (tools/build_asan.sh) names its translation units itself and lists neither -- and a
+# The entry points of csrc/conformal.hip, csrc/knn.hip and csrc/krige.hip.  A library linked without those translation units still
+# loads -- the host sanitizer build (tools/build_asan.sh) names its translation units itself and lists none of them -- and a
 # call of one of these then raises AttributeError.
 _OWN_UNIT = frozenset(("stdadk_conformal_scores_workspace_bytes", "stdadk_conformal_scores_f32",
                        "stdadk_select_workspace_bytes", "stdadk_select_f32",
-                       "stdadk_knn_workspace_bytes", "stdadk_knn_f32", "stdadk_knn_apply_f32"))
+                       "stdadk_knn_workspace_bytes", "stdadk_knn_f32", "stdadk_knn_apply_f32",
+                       "stdadk_krige_weights_f64", "stdadk_krige_apply_f32"))
 
 
 def exported_symbols():
@@ -1047,6 +1054,48 @@ def knn_apply(nbr_idx, nbr_d2, k, z, power, nearest, idw):
         _typed(what, z, "z", torch.float32, (nT, S)), nT, S, int(power), out(nearest, "nearest"), out(idw, "idw"),
         _stream())
     _check(rc, "stdadk_knn_apply_f32")
+
+
+# the variogram models and the column limit of stdadk_krige_weights_f64 / stdadk_krige_apply_f32 (include/stdadk.h)
+KRIGE_EXPONENTIAL, KRIGE_SPHERICAL, KRIGE_GAUSSIAN, KRIGE_MAX_COLS = 0, 1, 2, 8
+
+
+def krige_weights(nbr_idx, nbr_d2, k, coords, model, nugget, psill, range_, w, var):
+    """stdadk_krige_weights_f64: for every row of the table nbr_idx / nbr_d2 (nM, M, k_tab) of knn the local
+    ordinary-kriging weights of its first k entries under the variogram model (KRIGE_*; nugget, psill, range) and the
+    kriging variance of a new noisy observation; coords (S, 2) float32 are the sites the indices name.  ASSIGNS
+    w (nM, M, k) and var (nM, M) float64 on the device: 0 / NaN where a row holds no source, all NaN where it is
+    singular."""
+    what = "krige_weights"
+    if nbr_idx.dim() != 3 or coords.dim() != 2:
+        raise RuntimeError(f"{what}: the table must be (nM, M, k_tab) and coords (S, 2)")
+    nM, M, k_tab = nbr_idx.shape
+    S, k = coords.shape[0], int(k)
+    rc = lib().stdadk_krige_weights_f64(
+        _typed(what, nbr_idx, "nbr_idx", torch.int32, (nM, M, k_tab)),
+        _typed(what, nbr_d2, "nbr_d2", torch.float64, (nM, M, k_tab)), nM, M, k_tab, k,
+        _typed(what, coords, "coords", torch.float32, (S, 2)), S, int(model), float(nugget), float(psill), float(range_),
+        _typed(what, w, "w", torch.float64, (nM, M, k)), _typed(what, var, "var", torch.float64, (nM, M)), _stream())
+    _check(rc, "stdadk_krige_weights_f64")
+
+
+def krige_apply(nbr_idx, w, var, k, z, zq, out):
+    """stdadk_krige_apply_f32: the weights w (nM, M, k) and variances var (nM, M) of krige_weights on the table nbr_idx
+    (nM, M, k_tab), nM == 1 or nM == nT, applied to the slices z (nT, S) float32.  zq: Q standard-normal quantiles (0 for
+    the mean).  ASSIGNS the first Q columns of out (nT*M, ldo) float32 on the device, grid_score's y_pred layout:
+    prediction + zq * sqrt(max(var, 0)); NaN where a row has no prediction."""
+    what = "krige_apply"
+    if nbr_idx.dim() != 3 or z.dim() != 2 or out.dim() != 2:
+        raise RuntimeError(f"{what}: the table must be (nM, M, k_tab), z (nT, S) and out (nT*M, ldo)")
+    nM, M, k_tab = nbr_idx.shape
+    nT, S = z.shape
+    k, Q = int(k), len(zq)
+    rc = lib().stdadk_krige_apply_f32(
+        _typed(what, nbr_idx, "nbr_idx", torch.int32, (nM, M, k_tab)), _typed(what, w, "w", torch.float64, (nM, M, k)),
+        _typed(what, var, "var", torch.float64, (nM, M)), nM, M, k_tab, k, _typed(what, z, "z", torch.float32, (nT, S)),
+        nT, S, (C.c_double * max(Q, 1))(*[float(v) for v in zq]), Q,
+        _typed(what, out, "out", torch.float32, (nT * M, out.shape[1])), out.shape[1], _stream())
+    _check(rc, "stdadk_krige_apply_f32")
 
 
 def gmm_workspace_bytes(n, k):

@@ -4,6 +4,7 @@ model and `field_variogram`, `grid_baselines` and `rasterize_nearest` on a HIP d
 from . import baselines as _baselines
 from . import basis_diag as _basis_diag
 from . import ema as _ema
+from . import kriging as _kriging
 from . import metrics as _metrics
 from . import predictions as _predictions
 from . import seed as _seed
@@ -24,5 +25,8 @@ grid_baselines = _baselines.grid_baselines
 rasterize_nearest = _baselines.rasterize_nearest
 knn_host = _baselines.knn_host
 knn_apply_host = _baselines.knn_apply_host
+fit_variogram = _variogram.fit_variogram
+kriging_weights_host = _kriging.kriging_weights_host
+kriging_apply_host = _kriging.kriging_apply_host
 
 __all__ = sorted(n for n in dir() if not n.startswith('_'))

@@ -18,7 +18,7 @@ numpy float64: the path of `device: cpu`.  The search is brute force; a table pe
 import numpy as np
 import torch
 
-from .predictions import SPLIT_NAMES, _grid_sums_host, _ratio, _split_metrics
+from .predictions import SPLIT_NAMES, _grid_sums_host, _quantile_sums_host, _ratio, _split_metrics, quantile_diagnostics
 
 MAX_K = 16                                      # STDADK_KNN_MAX_K of include/stdadk.h
 _EMPTY = np.uint64(0x7FF0000000000001)          # the key of no neighbour: above +inf's bits, at or below every NaN's
@@ -202,6 +202,81 @@ def _entry(split_acc, site_acc, time_acc):
     return out
 
 
+def _kriging_plan(config, k, z, c, code, device):
+    """What `baseline_kriging: true` asks for, from the config: the model and its parameters (given, or fitted to the
+    lag-0 field variogram of the training entries), the neighbours, and the columns of the prediction buffer -- the mean
+    as the level 0.5 among the ascending `kriging_levels`, so that the buffer is a quantile model's."""
+    from . import kriging as KR
+    from . import variogram as V
+    model = str(config.get("kriging_model", "exponential"))
+    code_m = KR.model_code(model)
+    kk = int(config.get("kriging_k", k))
+    if not 1 <= kk <= MAX_K:
+        raise ValueError(f"grid_baselines: kriging_k={kk} outside 1..{MAX_K}")
+    levels = [float(q) for q in config.get("kriging_levels") or []]
+    if len(levels) > KR.MAX_COLS - 1 or any(b <= a for a, b in zip(levels, levels[1:])):
+        raise ValueError(f"grid_baselines: kriging_levels must be at most {KR.MAX_COLS - 1} ascending levels, got {levels}")
+    KR.normal_quantiles(levels)                   # (refuses a level outside (0, 1))
+    mean_col = sum(q < 0.5 for q in levels)
+    taus = levels[:mean_col] + [0.5] + levels[mean_col:]
+    if config.get("kriging_params") is not None:
+        nugget, psill, range_ = KR.check_params(*config["kriging_params"])
+        fit = {"model": model, "nugget": nugget, "psill": psill, "range": range_, "wss": float("nan"), "bins_used": 0}
+    else:
+        curves = V.field_variogram(z, c, code=code, n_bins=config.get("variogram_bins", 15),
+                                   max_dist=config.get("variogram_max_dist"), time_lags=1,
+                                   sites=config.get("variogram_sites"), device=device)
+        fit = V.fit_variogram(curves["gamma_z"][1, 0], curves["count"][1, 0], curves["edges"], model)
+        KR.check_params(fit["nugget"], fit["psill"], fit["range"])
+    return {"model": model, "code": code_m, "k": kk, "levels": levels, "taus": taus, "zq": KR.normal_quantiles(taus),
+            "mean_col": mean_col, "interval": len(levels) >= 2, "fit": fit,
+            "params": (fit["nugget"], fit["psill"], fit["range"])}
+
+
+def _calibration_sums_host(pred, var, z, code):
+    """(4, 3) per split code: the entries with a finite z, a finite prediction and a variance > 0, the sum of their
+    variances and the sum of (z - prediction)^2 / variance."""
+    p, zz = pred.astype(np.float64), z.astype(np.float64)
+    v = np.broadcast_to(var, zz.shape)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ok = np.isfinite(zz) & np.isfinite(p) & (v > 0.0) & np.isfinite(v)
+        e2 = np.where(ok, (zz - p) ** 2 / np.where(ok, v, 1.0), 0.0)
+    out = np.zeros((4, 3))
+    for s in range(4):
+        m = ok & (code == s)
+        out[s] = m.sum(), np.where(m, v, 0.0).sum(), np.where(m, e2, 0.0).sum()
+    return out
+
+
+def _calibration_sums_device(pred, var, z, code):
+    """_calibration_sums_host on device tensors: (4, 3) float64 on the device."""
+    p, zz = pred.double(), z.double()
+    v = var.expand_as(zz)
+    ok = torch.isfinite(zz) & torch.isfinite(p) & (v > 0.0) & torch.isfinite(v)
+    one = torch.ones((), dtype=torch.float64, device=z.device)
+    e2 = torch.where(ok, (zz - p) ** 2 / torch.where(ok, v, one), 0.0 * one)
+    out = torch.zeros((4, 3), dtype=torch.float64, device=z.device)
+    for s in range(4):
+        m = ok & (code == s)
+        out[s, 0], out[s, 1], out[s, 2] = m.sum(), torch.where(m, v, 0.0 * one).sum(), torch.where(m, e2, 0.0 * one).sum()
+    return out
+
+
+def _kriging_entry(plan, accs, qd_split, cal, n_singular):
+    out = _entry(*accs)
+    out.update(model=plan["model"], k=plan["k"], nugget=plan["params"][0], psill=plan["params"][1],
+               range=plan["params"][2], variogram_fit=plan["fit"], n_singular=int(n_singular), mean_var={}, msse={})
+    cal = np.concatenate([cal.sum(axis=0, keepdims=True), cal])      # all, then the codes 0..3
+    for name, row in zip(("all", "other", "train", "valid", "test"), cal):
+        out["mean_var"][name], out["msse"][name] = float(_ratio(row[1], row[0])), float(_ratio(row[2], row[0]))
+    if plan["levels"]:
+        out["levels"] = np.asarray(plan["taus"], dtype=np.float64)
+        diag = quantile_diagnostics(qd_split, None, None, plan["taus"], plan["interval"])
+        for name, d in diag.items():
+            out["splits"][name].update({key: d[key] for key in ("crps", "reliability", "coverage") if key in d})
+    return out
+
+
 def grid_baselines(z_full, coords, train_mask, valid_mask=None, test_mask=None, config=None, device=None, max_rows=None):
     """The two neighbour baselines of a (T, S) field scored like a model's grid (grid_scores): at every entry NEAREST is
     the value, at the same time, of the nearest source site and IDW the inverse-distance weighted mean of the
@@ -218,7 +293,21 @@ def grid_baselines(z_full, coords, train_mask, valid_mask=None, test_mask=None, 
     Returns {"nearest": e, "idw": e, "k", "power", "shared_table", "train_dist"} with e = {"splits": grid_scores' metric
     dict per split (all, train, valid, test, other), "site_mse" (S,), "site_mse_by_split" (4, S), "time_mse" (T,)} and
     `train_dist` (S,) the distance from every site to the nearest OTHER site with any training observation (inf when
-    there is none)."""
+    there is none).
+
+    `baseline_kriging: true` adds a third entry, `kriging`: local ordinary kriging over the `kriging_k` (default
+    `baseline_k`) nearest sources of the same tables, under ONE variogram model `kriging_model` (exponential, spherical,
+    gaussian) -- `kriging_params` (nugget, psill, range), or else fitted by `fit_variogram` to the lag-0 field variogram
+    of the training entries (one `field_variogram` call with the `variogram_*` keys' defaults).  The weights are solved
+    once per table; the kriging variance (of a new noisy observation) makes the baseline probabilistic:
+    `kriging_levels` (ascending, at most 7) adds the Gaussian quantiles prediction + z_tau sd as columns, the mean among
+    them as level 0.5, and the per-split dicts gain `crps`, `reliability` and, with two levels or more, the `coverage`
+    of the interval between the lowest and the highest.  The entry has the shape of the other two plus `model`, `k`,
+    `nugget`, `psill`, `range`, `variogram_fit`, `n_singular` (table rows with sources whose system was singular: no
+    prediction there), and per split `mean_var` and `msse`, the mean of (z - prediction)^2 / variance over the entries
+    with a prediction and a variance > 0: about 1 when the variogram is right.  The nugget is on the diagonal only, so
+    the prediction is of the smooth signal.  Not built: universal and space-time kriging, anisotropy, a global solve,
+    covariates."""
     config = config or {}
     z = _host(z_full).astype(np.float32)
     c = _host(coords).astype(np.float32)
@@ -232,10 +321,15 @@ def grid_baselines(z_full, coords, train_mask, valid_mask=None, test_mask=None, 
     if not 1 <= k <= MAX_K or not 0 <= power <= 4:
         raise ValueError(f"grid_baselines: baseline_k={k} outside 1..{MAX_K} or baseline_power={power} outside 0..4")
     src = (_host(train_mask).astype(bool) & np.isfinite(z)).astype(np.uint8)
+    plan = _kriging_plan(config, k, z, c, code, device) if config.get("baseline_kriging", False) and S and T else None
+    k_tab = max(k, plan["k"]) if plan else k
+    nB = 3 if plan else 2
+    Qk = len(plan["taus"]) if plan else 0
+    cal, qd_split, n_singular = np.zeros((4, 3)), None, 0
     shared = T > 0 and bool((src == src[:1]).all()) and not config.get("baseline_per_time", False)
     per = max(1, min(T, (int(max_rows) if max_rows else _DEFAULT_ROWS) // max(S, 1)))
     any_src = src.any(axis=0, keepdims=True).astype(np.uint8)
-    accs = [[np.zeros((4, 16)), np.zeros((4, S, 3)), np.zeros((4, T, 3))] for _ in range(2)]
+    accs = [[np.zeros((4, 16)), np.zeros((4, S, 3)), np.zeros((4, T, 3))] for _ in range(nB)]
     train_d2 = np.full(S, np.inf)
     if S == 0 or T == 0:
         pass
@@ -246,12 +340,40 @@ def grid_baselines(z_full, coords, train_mask, valid_mask=None, test_mask=None, 
             f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)      # noqa: E731
             ct, zt, st, codet = (torch.from_numpy(a).to(dev) for a in (c, z, src, code))
             near_d2 = device_knn(ct, ct, torch.from_numpy(any_src).to(dev), 1, True)[1].reshape(S)
-            dacc = [(f64(4, N.GRID_SLOTS), f64(4, S, 3), f64(4, T, 3)) for _ in range(2)]
-            table = device_knn(ct, ct, st[:1], k, True) if shared else None
+            dacc = [(f64(4, N.GRID_SLOTS), f64(4, S, 3), f64(4, T, 3)) for _ in range(nB)]
+            table = device_knn(ct, ct, st[:1], k_tab, True) if shared else None
             ws = torch.empty(N.grid_score_workspace_bytes(S, per) // 8, dtype=torch.float64, device=dev)
+            extra = ()
+            if plan:
+                from .kriging import device_kriging_weights
+                solve = lambda tab: device_kriging_weights(tab[0], tab[1], plan["k"], ct, plan["code"], *plan["params"])      # noqa: E731
+                singular = lambda tab, var: (torch.isnan(var) & (tab[0][:, :, 0] >= 0)).sum().double().reshape(1)      # noqa: E731
+                dcal, dsing = f64(4, 3), f64(1)
+                dqd = f64(4, N.QD_SLOTS) if plan["levels"] else f64(0)
+                qws = torch.empty(N.quantile_diag_workspace_bytes(S, per) // 8, dtype=torch.float64, device=dev) \
+                    if plan["levels"] else None
+                if shared:
+                    wk, vk = solve(table)
+                    dsing += singular(table, vk)
             for t0 in range(0, T, per):
                 n = min(per, T - t0)
-                idx, d2 = table if shared else device_knn(ct, ct, st[t0:t0 + n], k, True)
+                idx, d2 = table if shared else device_knn(ct, ct, st[t0:t0 + n], k_tab, True)
+                if plan:
+                    if not shared:
+                        wk, vk = solve((idx, d2))
+                        dsing += singular((idx, d2), vk)
+                    predk = torch.empty((n * S, Qk), dtype=torch.float32, device=dev)
+                    N.krige_apply(idx, wk, vk, plan["k"], zt[t0:t0 + n], plan["zq"], predk)
+                    tacc = f64(4, n, 3)
+                    N.grid_score(predk, zt[t0:t0 + n], codet[t0:t0 + n], plan["mean_col"], plan["taus"],
+                                 0 if plan["interval"] else -1, Qk - 1 if plan["interval"] else -1,
+                                 dacc[2][0], dacc[2][1], tacc, ws)
+                    dacc[2][2][:, t0:t0 + n] = tacc
+                    if plan["levels"]:
+                        N.quantile_diag(predk, zt[t0:t0 + n], codet[t0:t0 + n], plan["taus"],
+                                        0 if plan["interval"] else -1, Qk - 1 if plan["interval"] else -1, dqd, None, None, qws)
+                    dcal += _calibration_sums_device(predk[:, plan["mean_col"]].reshape(n, S), vk, zt[t0:t0 + n],
+                                                     codet[t0:t0 + n])
                 pred = torch.empty((2, n, S), dtype=torch.float32, device=dev)
                 N.knn_apply(idx, d2, k, zt[t0:t0 + n], power, pred[0], pred[1])
                 for b in range(2):
@@ -259,35 +381,66 @@ def grid_baselines(z_full, coords, train_mask, valid_mask=None, test_mask=None, 
                     N.grid_score(pred[b].reshape(n * S, 1), zt[t0:t0 + n], codet[t0:t0 + n], 0, None, -1, -1,
                                  dacc[b][0], dacc[b][1], tacc, ws)
                     dacc[b][2][:, t0:t0 + n] = tacc
-            flat = torch.cat([a.reshape(-1) for a in (near_d2,) + dacc[0] + dacc[1]]).cpu().numpy()      # the ONE host read
+            if plan:
+                extra = (dcal, dsing, dqd)
+            flat = torch.cat([a.reshape(-1) for a in sum(dacc, (near_d2,)) + extra]).cpu().numpy()      # the ONE host read
         train_d2, flat = flat[:S], flat[S:]
-        for b in range(2):
+        for b in range(nB):
             for i, a in enumerate(accs[b]):
                 accs[b][i], flat = flat[:a.size].reshape(a.shape), flat[a.size:]
+        if plan:
+            cal, n_singular, qd_split = flat[:12].reshape(4, 3), flat[12], flat[13:].reshape(4, -1)
     else:
         train_d2 = knn_host(c, c, any_src, 1, True)[1].reshape(S)
-        table = knn_host(c, c, src[:1], k, True) if shared else None
+        table = knn_host(c, c, src[:1], k_tab, True) if shared else None
+        if plan:
+            from .kriging import kriging_apply_host, kriging_weights_host
+            solve = lambda tab: kriging_weights_host(tab[0], tab[1], plan["k"], c, plan["code"], *plan["params"])      # noqa: E731
+            singular = lambda tab, var: int((np.isnan(var) & (tab[0][:, :, 0] >= 0)).sum())      # noqa: E731
+            qd_split = np.zeros((4, 32))
+            lo, hi = (0, Qk - 1) if plan["interval"] else (-1, -1)
+            if shared:
+                wk, vk = solve(table)
+                n_singular += singular(table, vk)
         for t0 in range(0, T, per):
             n = min(per, T - t0)
-            idx, d2 = table if shared else knn_host(c, c, src[t0:t0 + n], k, True)
+            idx, d2 = table if shared else knn_host(c, c, src[t0:t0 + n], k_tab, True)
+            if plan:
+                if not shared:
+                    wk, vk = solve((idx, d2))
+                    n_singular += singular((idx, d2), vk)
+                predk = kriging_apply_host(idx, wk, vk, plan["k"], z[t0:t0 + n], plan["zq"])
+                mc = plan["mean_col"]
+                sp, si, ti = _grid_sums_host(predk[:, :, mc:mc + 1], z[t0:t0 + n], code[t0:t0 + n], None, -1, -1)
+                accs[2][0] += sp
+                accs[2][1] += si
+                accs[2][2][:, t0:t0 + n] = ti
+                if plan["levels"]:
+                    # (the levels as the device takes them: float32)
+                    qd_split += _quantile_sums_host(predk, z[t0:t0 + n], code[t0:t0 + n],
+                                                    np.asarray(plan["taus"], dtype=np.float32).astype(np.float64), lo, hi)[0]
+                cal += _calibration_sums_host(predk[:, :, mc], vk, z[t0:t0 + n], code[t0:t0 + n])
             for b, pred in enumerate(knn_apply_host(idx, d2, k, z[t0:t0 + n], power)):
                 sp, si, ti = _grid_sums_host(pred[:, :, None], z[t0:t0 + n], code[t0:t0 + n], None, -1, -1)
                 accs[b][0] += sp
                 accs[b][1] += si
                 accs[b][2][:, t0:t0 + n] = ti
-    return {"nearest": _entry(*accs[0]), "idw": _entry(*accs[1]), "k": k, "power": power, "shared_table": shared,
-            "train_dist": np.sqrt(train_d2)}
+    out = {"nearest": _entry(*accs[0]), "idw": _entry(*accs[1]), "k": k, "power": power, "shared_table": shared,
+           "train_dist": np.sqrt(train_d2)}
+    if plan:
+        out["kriging"] = _kriging_entry(plan, accs[2], qd_split, cal, n_singular)
+    return out
 
 
 def skill_scores(model_scores, baseline):
     """What grid_scores adds to grid_baselines' dict: `skill` {baseline: {split: 1 - mse_model / mse_baseline}} and
-    `site_skill` (2, S), the same ratio per site on the test split, rows nearest, idw.  NaN where either MSE is NaN or
-    the baseline's is 0.  A skill of 0 is no better than the baseline, a negative skill is worse, 1 is a perfect model."""
+    `site_skill` (2, S), the same ratio per site on the test split, rows nearest, idw -- and kriging, a third name and a
+    third row, when the dict has that entry.  NaN where either MSE is NaN or the baseline's is 0.  A skill of 0 is no better than the baseline, a negative skill is worse, 1 is a perfect model."""
     def skill(model_mse, base_mse):
         model_mse, base_mse = np.asarray(model_mse, dtype=np.float64), np.asarray(base_mse, dtype=np.float64)
         ok = np.isfinite(model_mse) & np.isfinite(base_mse) & (base_mse != 0)
         return np.where(ok, 1.0 - model_mse / np.where(ok, base_mse, 1.0), np.nan)
-    names = ("nearest", "idw")
+    names = ("nearest", "idw") + (("kriging",) if "kriging" in baseline else ())
     return {"skill": {b: {s: float(skill(m["mse"], baseline[b]["splits"][s]["mse"]))
                           for s, m in model_scores["splits"].items()} for b in names},
             "site_skill": np.stack([skill(model_scores["site_mse_by_split"][3], baseline[b]["site_mse_by_split"][3])

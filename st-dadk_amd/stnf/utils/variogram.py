@@ -168,3 +168,73 @@ def field_variogram(z, coords, code=None, edges=None, n_bins=15, max_dist=None, 
     out = variogram_curves(acc, edges, np.arange(L))
     out["sites"] = idx
     return out
+
+
+VARIOGRAM_MODELS = ("exponential", "spherical", "gaussian")
+
+
+def variogram_structure(model, h, range_):
+    """The structure function g of a variogram model, gamma(h) = nugget + psill * g(h / range): exponential
+    1 - exp(-r), spherical 1.5 r - 0.5 r^3 below the range and 1 beyond it, gaussian 1 - exp(-r^2); float64."""
+    if model not in VARIOGRAM_MODELS:
+        raise ValueError(f"variogram: model '{model}' must be one of {VARIOGRAM_MODELS}")
+    r = np.asarray(h, dtype=np.float64) / float(range_)
+    if model == "exponential":
+        return 1.0 - np.exp(-r)
+    if model == "gaussian":
+        return 1.0 - np.exp(-(r * r))
+    return np.where(r < 1.0, 1.5 * r - 0.5 * r * r * r, 1.0)
+
+
+def _wls_nonneg(g, y, w):
+    """min sum w (y - c0 - c g)^2 over c0, c >= 0 in closed form: the interior solution where both are >= 0, otherwise
+    the better of the two boundary solutions (c0 = 0; c = 0).  Returns (c0, c, weighted residual sum)."""
+    wss = lambda c0, c: float(np.sum(w * (y - c0 - c * g) ** 2))      # noqa: E731
+    sw, sg, sy = float(np.sum(w)), float(np.sum(w * g)), float(np.sum(w * y))
+    sgg, sgy = float(np.sum(w * g * g)), float(np.sum(w * g * y))
+    det = sw * sgg - sg * sg
+    if det > 0.0:
+        c = (sw * sgy - sg * sy) / det
+        c0 = (sy - c * sg) / sw
+        if c0 >= 0.0 and c >= 0.0:
+            return c0, c, wss(c0, c)
+    only_c = max(sgy / sgg, 0.0) if sgg > 0.0 else 0.0
+    only_c0 = max(sy / sw, 0.0)
+    a, b = wss(0.0, only_c), wss(only_c0, 0.0)
+    return (0.0, only_c, a) if a <= b else (only_c0, 0.0, b)
+
+
+def fit_variogram(gamma, n, edges, model="exponential", ranges=None):
+    """A variogram model fitted to ONE empirical curve as variogram_curves returns it: `gamma` and the pair counts `n`
+    per bin, and the B + 1 bin `edges`; a bin's distance is its midpoint, bins with n == 0 or a non-finite gamma are
+    skipped.  gamma(h) = nugget + psill * g(h / range) with g of `model` (variogram_structure).  Deterministic, no
+    optimiser: for every candidate range of a fixed ladder -- `ranges`, default 64 log-spaced values from a quarter of
+    the first bin's midpoint to twice the last edge -- the weighted least-squares (nugget, psill) >= 0 in closed form,
+    weights n; the candidate with the smallest weighted residual sum wins, ties go to the smaller range.  Returns
+    {"model", "nugget", "psill", "range", "wss", "bins_used"}.  Fewer than 3 usable bins, or every gamma 0: ValueError."""
+    if model not in VARIOGRAM_MODELS:
+        raise ValueError(f"fit_variogram: model '{model}' must be one of {VARIOGRAM_MODELS}")
+    gamma = np.asarray(gamma, dtype=np.float64).reshape(-1)
+    n = np.asarray(n, dtype=np.float64).reshape(-1)
+    edges = np.asarray(edges, dtype=np.float64).reshape(-1)
+    if len(edges) != len(gamma) + 1 or len(n) != len(gamma):
+        raise ValueError(f"fit_variogram: {len(gamma)} bins need {len(gamma) + 1} edges and {len(gamma)} counts, got "
+                         f"{len(edges)} and {len(n)}")
+    use = (n > 0) & np.isfinite(gamma)
+    if int(use.sum()) < 3:
+        raise ValueError(f"fit_variogram: {int(use.sum())} usable bins, at least 3 are needed")
+    h, y, w = (0.5 * (edges[:-1] + edges[1:]))[use], gamma[use], n[use]
+    if not (y != 0.0).any():
+        raise ValueError("fit_variogram: every gamma is 0 (a constant field has no variogram to fit)")
+    if ranges is None:
+        ranges = np.geomspace(0.25 * 0.5 * (edges[0] + edges[1]), 2.0 * edges[-1], 64)
+    ranges = np.sort(np.asarray(ranges, dtype=np.float64).reshape(-1))
+    if len(ranges) == 0 or not (ranges > 0.0).all() or not np.isfinite(ranges).all():
+        raise ValueError("fit_variogram: the candidate ranges must be positive and finite")
+    best = None
+    for a in ranges:                              # ascending: a tie keeps the smaller range
+        c0, c, wss = _wls_nonneg(variogram_structure(model, h, a), y, w)
+        if best is None or wss < best[3]:
+            best = (c0, c, float(a), wss)
+    return {"model": model, "nugget": best[0], "psill": best[1], "range": best[2], "wss": best[3],
+            "bins_used": int(use.sum())}
