@@ -1024,6 +1024,29 @@ int stdadk_knn_apply_f32(const int32_t *nbr_idx, const double *nbr_d2, int64_t n
                          stdadk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same table by a cell-binned search (added under ABI 10: new entry points only, so STDADK_ABI_VERSION stays 10).
+ *
+ * stdadk_knn_cells_f32 takes exactly the parameter list of stdadk_knn_f32 and, for every input that entry accepts,
+ * ASSIGNS the same nbr_idx and nbr_d2, bit for bit: NaN and inf coordinates, short rows (-1 / +inf), S = 0 and slices
+ * without sources, exclude_self, and the rows in the caller's target order included.  It refuses the same inputs with
+ * the same codes; its workspace is stdadk_knn_cells_workspace_bytes(M, S, nM, k) (0 = bad sizes; below it:
+ * STDADK_E_WORKSPACE).  No host read of device memory, no allocation, capturable: the plan follows from M, S, nM and k
+ * or is computed on the device.
+ * The plan (csrc/knn_cells.hip): the sites are binned once into a uniform grid over the box of their finite coordinates,
+ * the side chosen from S alone; the targets are sorted by cell; a wave of 64 cell-adjacent targets walks the cells of
+ * its rectangle and then one frame of cells per ring.  A source is skipped only when a lower bound of its d2, formed by
+ * the same rounded operations from the exact extreme coordinate not yet met, is STRICTLY above the target's current
+ * k-th distance; an equal bound visits, and a NaN or inf target visits everything.  The order inside a cell may differ
+ * from run to run; the table cannot, because the order (d2, source index) is total.  What it costs is decided by the
+ * data: sites spread evenly over their box are its case; a slice that uses few of the sites, or sites in a few tight
+ * clusters, walks many rings (or crowded cells) and can be slower than the brute-force call.
+ * ------------------------------------------------------------------------------------------ */
+size_t stdadk_knn_cells_workspace_bytes(int64_t M, int64_t S, int64_t nM, int32_t k);
+int stdadk_knn_cells_f32(const float *q, int64_t M, const float *coords, int64_t S, const uint8_t *src, int64_t nM,
+                         int32_t k, int32_t exclude_self, int32_t *nbr_idx, double *nbr_d2, void *workspace,
+                         size_t workspace_bytes, stdadk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Local ordinary kriging on a neighbour table (added under ABI 10: new entry points only, so STDADK_ABI_VERSION stays
  * 10): the baseline a geostatistics user asks for first (stnf.utils.kriging, stnf.utils.baselines), with a variance, so
  * that Gaussian quantiles of it go through stdadk_grid_score_f32 and stdadk_quantile_diag_f32 unchanged.  One

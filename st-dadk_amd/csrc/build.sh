@@ -14,7 +14,7 @@ stale() {  # stale <object> <source>
   return 1
 }
 pids=()
-for f in rbf_build gemm_f32 mlp optim window tail loss knots step_finish fused_step dw_all sparsity eval grid_score quantile_diag variogram basis_diag conformal knn krige gmm kmeans kmeanspp; do
+for f in rbf_build gemm_f32 mlp optim window tail loss knots step_finish fused_step dw_all sparsity eval grid_score quantile_diag variogram basis_diag conformal knn knn_cells krige gmm kmeans kmeanspp; do
   if stale obj/$f.o $f.hip; then
     $HIPCC $FLAGS -c $f.hip -o obj/$f.o &
     pids+=($!)

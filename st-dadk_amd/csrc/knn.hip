@@ -21,12 +21,11 @@
 // A distance is carried as its KEY, the bit pattern of the double read as an unsigned integer: d2 is a sum of two
 // squares, never negative and never -0, so unsigned order is numeric order, +inf included; every NaN pattern is at or
 // above KN_EMPTY (the pattern after +inf's), the key of an empty slot, and `key < last` lets no NaN in.  The order being
-// total, the partition over waves and spans cannot change a bit of the answer.
-#include "f64_block.h"
+// total, the partition over waves and spans cannot change a bit of the answer.  The key, the list insertion, the row
+// store and the argument checks live in knn_common.h: knn_cells.hip returns the same table and shares them.
+#include "knn_common.h"
 
 namespace stdadk {
-
-typedef unsigned long long u64;
 
 constexpr int KN_Q = 4;                        // waves per workgroup
 constexpr int KN_T = KN_Q * kWave;             // threads per workgroup
@@ -35,26 +34,7 @@ constexpr int KN_SC = 256;                     // sources staged per LDS chunk
 constexpr int KN_SQ = KN_SC / KN_Q;            // a wave's share of a staged chunk
 constexpr int KN_FILL = 1024;                  // workgroups below which the sources are cut into spans
 constexpr int KN_MAX_SPANS = 64;               // source spans (partial rows per target) at the most
-constexpr u64 KN_EMPTY = 0x7ff0000000000001ull;      // key of an empty slot: above +inf, at or below every NaN
-constexpr int KN_NONE = 0x7fffffff;            // index of an empty slot: above every source index
 static_assert(KN_SC == KN_T, "one staged source per thread");
-static_assert(STDADK_KNN_MAX_K == 16, "list sizes 1, 2, 4, 8, 16");
-
-// (c, i) into the ascending list: every slot from the first one it is below moves up one, the last falls out.  TOTAL:
-// below means (key, index) below; otherwise key strictly below (the caller meets equal keys in index order).
-template <int KT, bool TOTAL>
-__device__ __forceinline__ void knn_insert(u64 (&key)[KT], int (&ix)[KT], u64 c, int i) {
-  bool below[KT];
-#pragma unroll
-  for (int j = 0; j < KT; ++j) below[j] = c < key[j] || (TOTAL && c == key[j] && i < ix[j]);
-#pragma unroll
-  for (int j = KT - 1; j > 0; --j) {
-    key[j] = below[j - 1] ? key[j - 1] : below[j] ? c : key[j];
-    ix[j] = below[j - 1] ? ix[j - 1] : below[j] ? i : ix[j];
-  }
-  key[0] = below[0] ? c : key[0];
-  ix[0] = below[0] ? i : ix[0];
-}
 
 struct KnnArgs {
   const float *q, *coords;
@@ -69,9 +49,7 @@ struct KnnArgs {
 
 // slot e of a finished list as the table holds it
 __device__ __forceinline__ void knn_store(const KnnArgs &a, size_t at, u64 key, int ix) {
-  const bool none = ix == KN_NONE;
-  a.nbr_idx[at] = none ? -1 : ix;
-  a.nbr_d2[at] = none ? __builtin_inf() : __longlong_as_double((long long)key);
+  knn_store_slot(a.nbr_idx, a.nbr_d2, at, key, ix);
 }
 
 template <int KT>
@@ -236,12 +214,6 @@ static inline KnSpans knn_spans(int64_t M, int64_t S, int64_t nM) {
   return KnSpans{ceil_div(chunks, per), per * KN_SC};
 }
 
-static inline bool knn_sizes_ok(int64_t M, int64_t S, int64_t nM, int32_t k) {
-  const int64_t lim = 1ll << 31;
-  return M >= 0 && S >= 0 && nM >= 0 && M < lim && S < lim && nM < lim && k >= 1 && k <= STDADK_KNN_MAX_K &&
-         nM * M < lim && nM * M * k < lim;
-}
-
 }  // namespace stdadk
 
 using namespace stdadk;
@@ -256,34 +228,10 @@ extern "C" size_t stdadk_knn_workspace_bytes(int64_t M, int64_t S, int64_t nM, i
 extern "C" int stdadk_knn_f32(const float *q, int64_t M, const float *coords, int64_t S, const uint8_t *src, int64_t nM,
                               int32_t k, int32_t exclude_self, int32_t *nbr_idx, double *nbr_d2, void *workspace,
                               size_t workspace_bytes, stdadk_stream_t stream) {
-  const int64_t lim = 1ll << 31;
-  STDADK_REQUIRE(M >= 0 && S >= 0 && nM >= 0 && M < lim && S < lim && nM < lim, STDADK_E_ARG,
-                 "knn: M=%lld, S=%lld, nM=%lld must be 0 .. 2^31-1", (long long)M, (long long)S, (long long)nM);
-  STDADK_REQUIRE(k >= 1 && k <= STDADK_KNN_MAX_K, STDADK_E_ARG, "knn: k=%d outside 1..%d", k, STDADK_KNN_MAX_K);
-  STDADK_REQUIRE(exclude_self == 0 || (exclude_self == 1 && M == S), STDADK_E_ARG,
-                 "knn: exclude_self=%d must be 0, or 1 with M == S (M=%lld, S=%lld)", exclude_self, (long long)M,
-                 (long long)S);
-  STDADK_REQUIRE(src || nM == 1 || nM == 0 || S == 0, STDADK_E_ARG,
-                 "knn: src == NULL (every site a source) needs nM == 1, got %lld", (long long)nM);
-  STDADK_REQUIRE(nM * M < lim && nM * M * k < lim, STDADK_E_SHAPE, "knn: nM*M*k = %lld x %lld x %d must stay below 2^31",
-                 (long long)nM, (long long)M, k);
-  const bool rows = M > 0 && nM > 0;
-  STDADK_REQUIRE((!rows || (q && nbr_idx && nbr_d2)) && (S == 0 || coords) && workspace, STDADK_E_ARG,
-                 "knn: NULL pointer");
-  STDADK_REQUIRE(((reinterpret_cast<uintptr_t>(nbr_d2)) & 7) == 0, STDADK_E_ALIGN, "knn: nbr_d2 not 8-byte aligned");
-  STDADK_REQUIRE(((reinterpret_cast<uintptr_t>(nbr_idx) | reinterpret_cast<uintptr_t>(q) |
-                   reinterpret_cast<uintptr_t>(coords)) & 3) == 0,
-                 STDADK_E_ALIGN, "knn: nbr_idx, q or coords not 4-byte aligned");
-  if (int rc = check_workspace("knn", workspace, workspace_bytes, stdadk_knn_workspace_bytes(M, S, nM, k),
-                               "stdadk_knn_workspace_bytes"))
+  if (int rc = knn_check_call("knn", q, M, coords, S, src, nM, k, exclude_self, nbr_idx, nbr_d2, workspace, workspace_bytes,
+                              stdadk_knn_workspace_bytes(M, S, nM, k), "stdadk_knn_workspace_bytes"))
     return rc;
-  const size_t n_out = (size_t)(nM * M) * k;
-  const ByteRange out[3] = {{nbr_idx, n_out * sizeof(int32_t)}, {nbr_d2, n_out * sizeof(double)}, {workspace, workspace_bytes}};
-  const ByteRange in[3] = {{q, (size_t)M * 2 * sizeof(float)},
-                           {coords, (size_t)S * 2 * sizeof(float)},
-                           {src, src ? (size_t)nM * S : 0}};
-  if (int rc = check_no_alias("knn", out, in, "")) return rc;
-  if (!rows) return 0;
+  if (M == 0 || nM == 0) return 0;
 
   const KnSpans sp = knn_spans(M, S, nM);
   KnnArgs a;

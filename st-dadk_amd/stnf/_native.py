@@ -241,6 +241,9 @@ _SIGNATURES = {
                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "stdadk_knn_apply_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "stdadk_knn_cells_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    "stdadk_knn_cells_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "stdadk_krige_weights_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                            C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),
@@ -308,12 +311,13 @@ def lib():
     return _lib
 
 
-# The entry points of csrc/conformal.hip, csrc/knn.hip and csrc/krige.hip.  A library linked without those translation units still
+# The entry points of csrc/conformal.hip, csrc/knn.hip, csrc/knn_cells.hip and csrc/krige.hip.  A library linked without those translation units still
 # loads -- the host sanitizer build (tools/build_asan.sh) names its translation units itself and lists none of them -- and a
 # call of one of these then raises AttributeError.
 _OWN_UNIT = frozenset(("stdadk_conformal_scores_workspace_bytes", "stdadk_conformal_scores_f32",
                        "stdadk_select_workspace_bytes", "stdadk_select_f32",
                        "stdadk_knn_workspace_bytes", "stdadk_knn_f32", "stdadk_knn_apply_f32",
+                       "stdadk_knn_cells_workspace_bytes", "stdadk_knn_cells_f32",
                        "stdadk_krige_weights_f64", "stdadk_krige_apply_f32"))
 
 
@@ -1018,23 +1022,40 @@ def knn_workspace_bytes(M, S, nM, k):
                             f"(1..{KNN_MAX_K})", M, S, nM, k)
 
 
-def knn(q, coords, src, k, exclude_self, nbr_idx, nbr_d2, workspace):
-    """stdadk_knn_f32: for every target of q (M, 2) float32 the k nearest sources among coords (S, 2) float32 in the
-    total order (d2, index), d2 in float64.  src: (nM, S) uint8, slice m's sources are the sites with src != 0, or None
-    (every site, one slice).  exclude_self (needs M == S) skips source j for target j.  ASSIGNS nbr_idx (nM, M, k) int32
-    and nbr_d2 (nM, M, k) float64 on the device; a row short of k sources ends in -1 / +inf."""
-    what = "knn"
+def _knn_call(what, symbol, q, coords, src, k, exclude_self, nbr_idx, nbr_d2, workspace):
+    """The one parameter list of the two searches, checked and passed to `symbol`."""
     if q.dim() != 2 or coords.dim() != 2:
         raise RuntimeError(f"{what}: q must be (M, 2) and coords (S, 2)")
     M, S = q.shape[0], coords.shape[0]
     nM = 1 if src is None else src.shape[0]
     k = int(k)
-    rc = lib().stdadk_knn_f32(
+    rc = getattr(lib(), symbol)(
         _typed(what, q, "q", torch.float32, (M, 2)), M, _typed(what, coords, "coords", torch.float32, (S, 2)), S,
         None if src is None else _typed(what, src, "src", torch.uint8, (nM, S)), nM, k, int(bool(exclude_self)),
         _typed(what, nbr_idx, "nbr_idx", torch.int32, (nM, M, k)), _typed(what, nbr_d2, "nbr_d2", torch.float64, (nM, M, k)),
         _typed(what, workspace, "workspace", torch.float64, None), workspace.numel() * 8, _stream())
-    _check(rc, "stdadk_knn_f32")
+    _check(rc, symbol)
+
+
+def knn(q, coords, src, k, exclude_self, nbr_idx, nbr_d2, workspace):
+    """stdadk_knn_f32: for every target of q (M, 2) float32 the k nearest sources among coords (S, 2) float32 in the
+    total order (d2, index), d2 in float64.  src: (nM, S) uint8, slice m's sources are the sites with src != 0, or None
+    (every site, one slice).  exclude_self (needs M == S) skips source j for target j.  ASSIGNS nbr_idx (nM, M, k) int32
+    and nbr_d2 (nM, M, k) float64 on the device; a row short of k sources ends in -1 / +inf."""
+    _knn_call("knn", "stdadk_knn_f32", q, coords, src, k, exclude_self, nbr_idx, nbr_d2, workspace)
+
+
+def knn_cells_workspace_bytes(M, S, nM, k):
+    return _workspace_bytes("stdadk_knn_cells_workspace_bytes",
+                            f"bad sizes: M={M}, S={S}, nM={nM} (each 0 .. 2^31-1, nM*M*k below 2^31), k={k} "
+                            f"(1..{KNN_MAX_K})", M, S, nM, k)
+
+
+def knn_cells(q, coords, src, k, exclude_self, nbr_idx, nbr_d2, workspace):
+    """stdadk_knn_cells_f32: knn's arguments and knn's table, bit for bit, by a cell-binned search (the sites binned
+    into a uniform grid, a wave of cell-adjacent targets walking rings of cells until no neighbour can be gained); the
+    workspace is knn_cells_workspace_bytes'."""
+    _knn_call("knn_cells", "stdadk_knn_cells_f32", q, coords, src, k, exclude_self, nbr_idx, nbr_d2, workspace)
 
 
 def knn_apply(nbr_idx, nbr_d2, k, z, power, nearest, idw):

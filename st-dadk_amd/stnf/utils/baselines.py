@@ -13,7 +13,9 @@ step the reference's summary maps take through scipy.interpolate.griddata(method
 (scripts/train_st_interp.py:1265-1270, :2764-2769).
 
 The tables come from the device library (a HIP device) or from `knn_host` / `knn_apply_host`, the same contracts in
-numpy float64: the path of `device: cpu`.  The search is brute force; a table per time slice costs one search per slice.
+numpy float64: the path of `device: cpu`.  The device search is brute force (`search="brute"`, the default) or
+cell-binned (`search="cells"`, config key `baseline_search`): the same table bit for bit, the second without meeting
+every pair, which is what a table per time slice otherwise costs.
 """
 import numpy as np
 import torch
@@ -23,6 +25,13 @@ from .predictions import SPLIT_NAMES, _grid_sums_host, _quantile_sums_host, _rat
 MAX_K = 16                                      # STDADK_KNN_MAX_K of include/stdadk.h
 _EMPTY = np.uint64(0x7FF0000000000001)          # the key of no neighbour: above +inf's bits, at or below every NaN's
 _DEFAULT_ROWS = 1 << 20                         # rows (time slices x sites) per chunk when max_rows is not given
+SEARCHES = ("brute", "cells")                   # stdadk_knn_f32, stdadk_knn_cells_f32: one table
+
+
+def _check_method(who, search):
+    if search not in SEARCHES:
+        raise ValueError(f"{who}: search must be one of {SEARCHES}, got {search!r}")
+    return search
 
 
 def _keys(q, c):
@@ -157,26 +166,30 @@ def _hip(device):
     return device is not None and torch.device(device).type == "cuda"
 
 
-def device_knn(q, coords, src, k, exclude_self):
-    """One stdadk_knn_f32 call on device tensors; returns the table (nbr_idx, nbr_d2) on the device."""
+def device_knn(q, coords, src, k, exclude_self, search="brute"):
+    """One stdadk_knn_f32 call (`search="cells"`: stdadk_knn_cells_f32, the same table) on device tensors; returns the
+    table (nbr_idx, nbr_d2) on the device."""
     from .. import _native as N
+    sizer, call = (N.knn_workspace_bytes, N.knn) if _check_method("device_knn", search) == "brute" else \
+        (N.knn_cells_workspace_bytes, N.knn_cells)
     M, S = q.shape[0], coords.shape[0]
     nM = 1 if src is None else src.shape[0]
     idx = torch.empty((nM, M, k), dtype=torch.int32, device=q.device)
     d2 = torch.empty((nM, M, k), dtype=torch.float64, device=q.device)
-    ws = torch.empty(N.knn_workspace_bytes(M, S, nM, k) // 8, dtype=torch.float64, device=q.device)
-    N.knn(q, coords, src, k, exclude_self, idx, d2, ws)
+    ws = torch.empty(sizer(M, S, nM, k) // 8, dtype=torch.float64, device=q.device)
+    call(q, coords, src, k, exclude_self, idx, d2, ws)
     return idx, d2
 
 
-def _search(q, coords, src, k, exclude_self, device):
-    """The table as host arrays, by the device library or by knn_host."""
+def _search(q, coords, src, k, exclude_self, device, search="brute"):
+    """The table as host arrays, by the device library (either search) or by knn_host."""
+    _check_method("search", search)
     if not _hip(device):
         return knn_host(q, coords, src, k, exclude_self)
     dev = torch.device(device)
     to = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)      # noqa: E731
     with torch.cuda.device(dev):
-        idx, d2 = device_knn(to(q, np.float32), to(coords, np.float32), to(src, np.uint8), k, exclude_self)
+        idx, d2 = device_knn(to(q, np.float32), to(coords, np.float32), to(src, np.uint8), k, exclude_self, search)
         return idx.cpu().numpy(), d2.cpu().numpy()
 
 
@@ -287,7 +300,9 @@ def grid_baselines(z_full, coords, train_mask, valid_mask=None, test_mask=None, 
     If the source set is the same at every time (the reference's site-wise observation and split methods) ONE table
     serves the whole grid; otherwise a table per time slice, in chunks of at most `max_rows` rows (time slices x
     sites): one brute-force search per slice, which is what the per-time route costs.  `baseline_per_time: true` forces
-    that route.  `device`: a HIP device runs stdadk_knn_f32 / stdadk_knn_apply_f32 and scores each chunk's two
+    that route.  `baseline_search`: "brute" (default) or "cells" -- every device search of the call (the shared table,
+    the per-time chunks, `train_dist`) through stdadk_knn_cells_f32, the same tables bit for bit; the host route ignores
+    it.  `device`: a HIP device runs stdadk_knn_f32 / stdadk_knn_apply_f32 and scores each chunk's two
     predictions with stdadk_grid_score_f32 into float64 accumulators read ONCE; otherwise numpy float64 on the host.
 
     Returns {"nearest": e, "idw": e, "k", "power", "shared_table", "train_dist"} with e = {"splits": grid_scores' metric
@@ -320,6 +335,7 @@ def grid_baselines(z_full, coords, train_mask, valid_mask=None, test_mask=None, 
     k, power = int(config.get("baseline_k", 8)), int(config.get("baseline_power", 2))
     if not 1 <= k <= MAX_K or not 0 <= power <= 4:
         raise ValueError(f"grid_baselines: baseline_k={k} outside 1..{MAX_K} or baseline_power={power} outside 0..4")
+    search = _check_method("grid_baselines: baseline_search", config.get("baseline_search", "brute"))
     src = (_host(train_mask).astype(bool) & np.isfinite(z)).astype(np.uint8)
     plan = _kriging_plan(config, k, z, c, code, device) if config.get("baseline_kriging", False) and S and T else None
     k_tab = max(k, plan["k"]) if plan else k
@@ -339,9 +355,9 @@ def grid_baselines(z_full, coords, train_mask, valid_mask=None, test_mask=None, 
         with torch.cuda.device(dev):
             f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)      # noqa: E731
             ct, zt, st, codet = (torch.from_numpy(a).to(dev) for a in (c, z, src, code))
-            near_d2 = device_knn(ct, ct, torch.from_numpy(any_src).to(dev), 1, True)[1].reshape(S)
+            near_d2 = device_knn(ct, ct, torch.from_numpy(any_src).to(dev), 1, True, search)[1].reshape(S)
             dacc = [(f64(4, N.GRID_SLOTS), f64(4, S, 3), f64(4, T, 3)) for _ in range(nB)]
-            table = device_knn(ct, ct, st[:1], k_tab, True) if shared else None
+            table = device_knn(ct, ct, st[:1], k_tab, True, search) if shared else None
             ws = torch.empty(N.grid_score_workspace_bytes(S, per) // 8, dtype=torch.float64, device=dev)
             extra = ()
             if plan:
@@ -357,7 +373,7 @@ def grid_baselines(z_full, coords, train_mask, valid_mask=None, test_mask=None, 
                     dsing += singular(table, vk)
             for t0 in range(0, T, per):
                 n = min(per, T - t0)
-                idx, d2 = table if shared else device_knn(ct, ct, st[t0:t0 + n], k_tab, True)
+                idx, d2 = table if shared else device_knn(ct, ct, st[t0:t0 + n], k_tab, True, search)
                 if plan:
                     if not shared:
                         wk, vk = solve((idx, d2))
@@ -447,14 +463,15 @@ def skill_scores(model_scores, baseline):
                                     for b in names])}
 
 
-def rasterize_nearest(coords, values, resolution=200, bounds=(0, 1), device=None):
+def rasterize_nearest(coords, values, resolution=200, bounds=(0, 1), device=None, search="brute"):
     """Per-site values on a raster by the nearest site: coords (S, 2), values (S,) or (C, S); `resolution` n or
     (ny, nx); `bounds` (lo, hi) for both axes or ((x_lo, x_hi), (y_lo, y_hi)).  The nodes are np.linspace over the
     bounds as float32, in row-major `meshgrid` order (node [iy, ix] = (x[ix], y[iy])); the sources of a row of `values`
     are the sites where it is finite; ties go to the lower site index.  Returns (raster, x, y): raster (C, ny, nx), or
     (ny, nx) for one-dimensional values, float32, NaN where a row has no finite value.  This is the reference's
     griddata(..., method="nearest") step for its averaged-MSE and observation-density maps, as one k = 1 search on the
-    device (`device`: a HIP device) or knn_host."""
+    device (`device`: a HIP device; `search`: "brute" or "cells", the same raster) or knn_host."""
+    _check_method("rasterize_nearest", search)
     c = _host(coords).astype(np.float32)
     v = _host(values).astype(np.float32)
     one = v.ndim == 1
@@ -469,9 +486,9 @@ def rasterize_nearest(coords, values, resolution=200, bounds=(0, 1), device=None
     nodes = np.stack([xg.reshape(-1), yg.reshape(-1)], axis=1)
     fin = np.isfinite(v)
     if fin.all():                                  # one table serves every row
-        idx = np.broadcast_to(_search(nodes, c, None, 1, False, device)[0], (len(v), ny * nx, 1))
+        idx = np.broadcast_to(_search(nodes, c, None, 1, False, device, search)[0], (len(v), ny * nx, 1))
     else:
-        idx = _search(nodes, c, fin.astype(np.uint8), 1, False, device)[0]
+        idx = _search(nodes, c, fin.astype(np.uint8), 1, False, device, search)[0]
     idx = idx[:, :, 0]
     some = idx >= 0
     raster = np.where(some, np.take_along_axis(v, np.where(some, idx, 0), axis=1) if len(c) else np.float32(0),
